@@ -69,6 +69,10 @@ def parse_args():
     ap.add_argument("--fixed-rays", action="store_true", help="replay one ray set every step (round-1 behaviour; diagnostics)")
     ap.add_argument("--host-rays", action="store_true", help="hand every step's rays over from the host loop (randint + rg_get_rays + gather + copies between replays) "
                                                                 "instead of drawing them inside the captured step (rg_sample_rays)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="", help="after the timed steps, write what the last timed step computed to DIR/<name>.npy (float32): "
+                                                                     "the arrays the step returned and the parameters it left behind (a fixed, seeded sample of "
+                                                                     "each large table); the same arguments give the same inputs, so two builds compare file by file "
+                                                                     "(bench_outputs/ is a DIR git ignores)")
     return ap.parse_args()
 
 
@@ -741,6 +745,42 @@ def emit(line, real_stdout):
     os.dup2(2, 1)
 
 
+# --------------------------------------------------------------------------------------------- --dump-outputs
+
+DUMP_LIMIT = 64 << 20       # bytes of all the files of one dump together
+DUMP_WHOLE = 1 << 18        # a parameter of at most this many elements is written whole ...
+DUMP_SAMPLE = 1 << 14       # ... a larger one as this many elements at fixed positions (np.random.RandomState(0), sorted; the same for every build)
+STEP_OUTPUTS = ("pred_rgb", "gt_rgb", "content_pred_rgb", "lossi", "lossw", "loss")     # trainer.train_step's return tuple
+
+
+def dump_arrays(model=None, **tensors):
+    """name -> float32 host copy of every tensor given (None skipped), plus `param.<name>` for every parameter of `model` (whole, or `.sample`d).
+    Tensors without elements (e.g. the parameter vector of the SH encoder, which has no weights) are left out; a scalar is written as shape (1,)."""
+    out = {k: np.atleast_1d(v.detach().float().cpu().numpy()) for k, v in tensors.items() if torch.is_tensor(v) and v.numel() > 0}
+    positions = {}
+    for name, p in (model.named_parameters() if model is not None else ()):
+        flat = p.detach().reshape(-1)
+        if flat.numel() == 0:
+            continue
+        if flat.numel() <= DUMP_WHOLE:
+            out[f"param.{name}"] = flat.float().cpu().numpy()
+            continue
+        if flat.numel() not in positions:
+            positions[flat.numel()] = torch.from_numpy(np.sort(np.random.RandomState(0).choice(flat.numel(), DUMP_SAMPLE, replace=False)))
+        out[f"param.{name}.sample"] = flat[positions[flat.numel()].to(flat.device)].float().cpu().numpy()
+    return out
+
+
+def write_dump(directory, arrays):
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT:
+        raise SystemExit(f"--dump-outputs: {total} bytes, more than the {DUMP_LIMIT} allowed")
+    os.makedirs(directory, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+    print(f"[bench] --dump-outputs: {len(arrays)} arrays, {total} bytes -> {directory}", file=sys.stderr)
+
+
 # --------------------------------------------------------------------------------------------- the training-step benchmark
 
 def bench_training(args, scene, real_stdout, secondary=None):
@@ -866,6 +906,11 @@ def bench_training(args, scene, real_stdout, secondary=None):
     if dp.exchange_active():
         coll_us["between_graph_segments_of_the_replays"] = dp.collective_times_us()
         dp.time_collectives(False)
+    if args.dump_outputs:      # the last timed step's results (a replayed graph's outputs are overwritten by the next replay: copied now)
+        if getattr(loop, "opt_shard", None) is not None:
+            loop.gather_codebook(optimizer_state=False)          # (every rank: the tables of the other ranks' bits)
+        if rank == 0:
+            write_dump(args.dump_outputs, dump_arrays(model, **dict(zip(STEP_OUTPUTS, out))))
     loss_value = float(out[5].detach())
     loss_parts = (float(out[3].detach()), float(out[4].detach()))
     # Replicated quantities must be the same number on every rank: the watermark loss (every rank decodes the same all-gathered blocks) and
@@ -1172,12 +1217,14 @@ def bench_fern(args, real_stdout):
     for _ in range(max(args.warmup, 1)):
         one_image()
     torch.cuda.synchronize()
-    steps = max(1, min(args.steps, 10))
+    steps = max(1, args.steps)
     t0 = time.perf_counter()
     for _ in range(steps):
         img, decoded = one_image()
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs:
+        write_dump(args.dump_outputs, dump_arrays(image=img, decoded=decoded))
     acc.update(decoded.permute(1, 0), msg[None].to(dev))
     n_chunks = (H * W + 4095) // 4096
     emit({"metric": "full-image watermarked render + decoder eval (fern, 48-bit msg)", "value": steps / elapsed, "unit": "images/s", "n_gpus": 1, "steps": steps,

@@ -84,6 +84,72 @@ def test_dropin_shadows_only_the_hot_path_modules(tmp_path):
     assert "DROPIN_OK" in out.stdout, out.stderr[-3000:]
 
 
+# A stand-in for the upstream checkout, written by the test: the module layout the drop-in directory relies on, nothing of the upstream code.  The
+# hot-path modules raise on import (they must be shadowed); the others leave a mark that shows whose function ran.
+STAND_IN = {
+    "nerf/__init__.py": "",
+    "nerf/utils_wtmk.py": "import os\nimport numpy as np\n\ndef get_rays(poses, intrinsics, H, W, N=-1, error_map=None, patch_size=1):\n"
+                          "    return {'upstream': (H, W, N)}\n\ndef srgb_to_linear(x):\n    return x\n",
+    "nerf/utils_wtmk_disen.py": "import os\nimport numpy as np\nimport torch.optim as optim\nfrom .utils_wtmk import get_rays\n\n"
+                                "def seed_everything(seed):\n    return seed\n\nclass PSNRMeter:\n    pass\n\nclass BIT_ACC:\n    pass\n\n"
+                                "class Trainer:\n    def __init__(self, model):\n        self.model = model\n\n"
+                                "    def train_step(self, data):\n        return 'upstream'\n\n    def save_checkpoint(self):\n        return 'upstream'\n",
+    "nerf/provider_wtmk.py": "from .utils_wtmk import get_rays\n",
+    **{f: "raise ImportError('the drop-in directory must shadow this module')\n"
+       for f in ("nerf/network_wtmk_tcnn.py", "nerf/renderer_wtmk.py", "nerf/hidden_models.py", "raymarching/__init__.py", "hash_encoding.py",
+                 "hash_encoding_wtmk_bit.py", "activation.py")},
+}
+
+STAND_IN_SCRIPT = r'''
+import os, sys
+import nerf, nerf.network_wtmk_tcnn, raymarching, hash_encoding, hash_encoding_wtmk_bit, activation
+import nerf_signature_amd.network as ours
+assert issubclass(nerf.network_wtmk_tcnn.NeRFNetwork, ours.NeRFNetwork)
+assert hash_encoding.HashEmbedder.__module__ == "nerf_signature_amd.hash_encoding"
+assert hash_encoding_wtmk_bit.HashEmbedder.__module__ == "nerf_signature_amd.hash_encoding_wtmk_bit"
+assert raymarching.__file__.startswith(ROOT) and callable(raymarching.march_rays_train)
+import nerf.utils_wtmk_disen as u
+import nerf._reference_utils_wtmk_disen as ref_u
+assert ref_u.__file__.startswith(UP) and u.__file__.startswith(ROOT), (ref_u.__file__, u.__file__)
+for name in ("os", "np", "optim", "seed_everything", "PSNRMeter", "BIT_ACC", "get_rays"):
+    assert getattr(u, name) is getattr(ref_u, name), name
+import nerf_signature_amd.trainer as our_trainer
+off = os.environ.get("NERFSIG_DROPIN_OFF") == "train_step"
+if off:
+    assert u.Trainer is ref_u.Trainer
+else:
+    assert u.Trainer.__mro__[1] is ref_u.Trainer and u.Trainer.train_step is our_trainer.reference_trainer_train_step
+    assert {k for k in vars(u.Trainer) if not k.startswith("__")} == {"train_step"}
+    assert u.Trainer(None).save_checkpoint() == "upstream"
+import nerf.provider_wtmk as prov
+assert prov.__file__.startswith(UP)
+import nerf.utils_wtmk as uw, nerf._reference_utils_wtmk as ref_uw
+assert uw.__file__.startswith(ROOT) and ref_uw.__file__.startswith(UP) and prov.get_rays is uw.get_rays and uw.get_rays is not ref_uw.get_rays
+assert {k for k in vars(ref_uw) if not k.startswith("_") and getattr(uw, k, None) is not getattr(ref_uw, k)} == {"get_rays"}
+import torch
+assert uw.get_rays(torch.eye(4)[None], [50.0, 50.0, 8.0, 8.0], 16, 16, 10) == {"upstream": (16, 16, 10)}      # CPU poses: the upstream function
+print("DROPIN_OK")
+'''
+
+
+@pytest.mark.parametrize("switched_off", [False, True])
+def test_dropin_shadows_a_stand_in_upstream_tree(tmp_path, switched_off):
+    """The shadowing rules on their own, without the upstream checkout: the hot-path modules resolve to this package, every other module to the
+    upstream tree behind the drop-in directory, and the two shadowing modules re-export the upstream module with ONE name replaced (Trainer.train_step,
+    get_rays for GPU poses); NERFSIG_DROPIN_OFF=train_step re-exports the upstream Trainer itself."""
+    up = tmp_path / "upstream"
+    for rel, text in STAND_IN.items():
+        (up / rel).parent.mkdir(parents=True, exist_ok=True)
+        (up / rel).write_text(text)
+    env = dict(os.environ, PYTHONDONTWRITEBYTECODE="1", PYTHONPATH=os.pathsep.join([os.path.join(ROOT, "nerf_signature_amd", "dropin"), ROOT, str(up)]))
+    env.pop("NERFSIG_DROPIN_OFF", None)
+    if switched_off:
+        env["NERFSIG_DROPIN_OFF"] = "train_step"
+    script = STAND_IN_SCRIPT.replace("UP", repr(str(up))).replace("ROOT", repr(ROOT))
+    out = subprocess.run([sys.executable, "-B", "-c", script], env=env, capture_output=True, text=True, cwd=str(tmp_path), timeout=300)
+    assert "DROPIN_OK" in out.stdout, out.stderr[-3000:]
+
+
 @pytest.mark.skipif(not os.path.isdir(REF), reason="reference checkout not present")
 def test_dropin_trainer_shadow_can_be_switched_off(tmp_path):
     """NERFSIG_DROPIN_OFF=train_step: the shadow module re-exports the reference's Trainer itself."""

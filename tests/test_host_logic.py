@@ -838,6 +838,31 @@ def _strings(o):
             yield from _strings(v)
 
 
+def test_bench_dump_outputs_writes_float32_arrays_at_fixed_sample_positions(tmp_path):
+    """bench.py --dump-outputs: one float32 .npy per returned tensor and per parameter, never empty and never 0-d; a parameter above DUMP_WHOLE elements is written as DUMP_SAMPLE elements at
+    positions that depend on its size alone (two builds compare file by file); a dump above DUMP_LIMIT is refused before anything is written."""
+    bench = _load_bench()
+    torch.manual_seed(0)
+    model = torch.nn.Module()
+    model.small = torch.nn.Parameter(torch.randn(3, 4, dtype=torch.float64))
+    model.big = torch.nn.Parameter(torch.arange(bench.DUMP_WHOLE + 7, dtype=torch.float32))
+    loss = torch.tensor(0.25)
+    model.no_weights = torch.nn.Parameter(torch.zeros(0))          # (the SH encoder's parameter vector: no elements, no file)
+    arrays = bench.dump_arrays(model, loss=loss, rgb=torch.ones(2, 3, dtype=torch.float16), missing=None, nothing=torch.zeros(0, 3))
+    assert set(arrays) == {"loss", "rgb", "param.small", "param.big.sample"}
+    bench.write_dump(str(tmp_path / "d"), arrays)
+    got = {f[:-4]: np.load(tmp_path / "d" / f) for f in os.listdir(tmp_path / "d")}
+    assert set(got) == set(arrays) and all(a.dtype == np.float32 and a.ndim >= 1 and a.size > 0 for a in got.values())
+    assert got["loss"].shape == (1,) and got["loss"][0] == np.float32(0.25) and got["rgb"].shape == (2, 3)
+    np.testing.assert_array_equal(got["param.small"], model.small.detach().reshape(-1).float().numpy())
+    pos = got["param.big.sample"]                    # the parameter holds its own indices: the sample shows the positions
+    assert pos.shape == (bench.DUMP_SAMPLE,) and np.all(np.diff(pos) > 0) and pos[-1] < bench.DUMP_WHOLE + 7
+    np.testing.assert_array_equal(bench.dump_arrays(model)["param.big.sample"], pos)
+    with pytest.raises(SystemExit):
+        bench.write_dump(str(tmp_path / "too_big"), {"x": np.zeros(bench.DUMP_LIMIT // 4 + 1, np.float32)})
+    assert not (tmp_path / "too_big").exists()
+
+
 def test_static_live_rows_bound_every_row_a_level_can_touch():
     """stage1.live_rows (the packed data-parallel exchange of the coarse levels): the rows the oracle's encoder gathers from -- for points all over [0, 1]^3, corners and
     faces of the box included -- lie inside the static set; the set is the hash of the level's (res + 2)^3 grid corners (hash_encoding.py:11-22), sorted and unique;
