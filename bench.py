@@ -5,6 +5,8 @@ message).
     python bench.py --gpus N --steps K --warmup W          # N > 1: starts its own N rank processes (one per GPU, RCCL)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
     python bench.py --config counter|fern                  # secondary workloads (BASELINE.json configs 3 and 5), not the headline
+    python bench.py --full                                 # + everything beyond the headline figure (secondaries, fixed-blocks variant, kernel times /
+                                                           #   roofline, CPU baseline); a plain run sets up, warms up, times, dumps (--dump-outputs) and prints
 
 One step = the loop body of the reference's train_one_epoch (nerf/utils_wtmk_disen.py:1164-1181) on synthetic scene S0
 (SURVEY.md 8(d)): a NEW pose and 4096 new random pixels (rays generated on the device, rg_get_rays; ground truth gathered
@@ -51,16 +53,19 @@ def parse_args():
     ap.add_argument("--config", choices=["hotdog", "counter", "fern"], default="hotdog", help="hotdog = the headline (BASELINE configs 2/4); counter / fern = secondary lines")
     ap.add_argument("--poses", type=int, default=8, help="pre-rendered clean views the per-step poses rotate through")
     ap.add_argument("--dry-launch", action="store_true", help="start the N rank processes over gloo, run the collectives of a step on CPU tensors, no kernels")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="also measure what the headline figure does not need: the secondary workloads, the fixed-blocks variant, the "
+                                                         "per-kernel HIP-event pass behind `roofline` / `roofline_mlp` and the CPU baseline (a plain run leaves them out)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--cpu-threads", type=int, default=0, help="torch intra-op threads of the CPU baseline (default: the CPUs this process may use, at most 32)")
-    ap.add_argument("--no-variant", action="store_true", help="skip the fixed-blocks variant that the default N = 1 run times behind the headline")
+    ap.add_argument("--no-variant", action="store_true", help="--full: skip the fixed-blocks variant that an N = 1 run times behind the headline")
     ap.add_argument("--dry-device-count", type=int, default=0, help="--dry-launch: the number of GPUs the node is taken to have (default: one per rank; 1 shows the clash report)")
     ap.add_argument("--launched-by", default="", help=argparse.SUPPRESS)          # set by this file's own launcher / supervisor for the rank processes it starts
     ap.add_argument("--launch-attempt", default="", help=argparse.SUPPRESS)
-    ap.add_argument("--no-secondary", action="store_true", help="skip the secondary workloads (BASELINE configs 3 and 5, one rank of eight emulated) that the default N = 1 run "
+    ap.add_argument("--no-secondary", action="store_true", help="--full: skip the secondary workloads (BASELINE configs 3 and 5, one rank of eight emulated) that an N = 1 run "
                                                                   "times in child processes BEFORE this process touches the GPU and reports under `secondary`")
-    ap.add_argument("--windows", type=int, default=3, help="timed windows of --steps steps each: `value` / `ms_per_step` come from the FIRST (the contract's K steps); "
-                                                            "median / min / max over all of them are reported under `timing`")
+    ap.add_argument("--windows", type=int, default=None, help="timed windows of --steps steps each: `value` / `ms_per_step` come from the FIRST (the contract's K steps); "
+                                                               "median / min / max over all of them are reported under `timing` (default: 3 with --full or "
+                                                               "--dump-outputs -- the dump is taken behind the last window -- 1 otherwise)")
     ap.add_argument("--no-overlap", action="store_true", help="issue the content render on the main stream instead of overlapping it with the block render / decoder")
     ap.add_argument("--no-fused-adam", action="store_true", help="torch's multi-tensor instead of its fused Adam kernel for the decoder parameters")
     ap.add_argument("--no-graph", action="store_true", help="run the loop body eagerly instead of replaying the captured hipGraph")
@@ -73,7 +78,10 @@ def parse_args():
                                                                      "the arrays the step returned and the parameters it left behind (a fixed, seeded sample of "
                                                                      "each large table); the same arguments give the same inputs, so two builds compare file by file "
                                                                      "(bench_outputs/ is a DIR git ignores)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.windows is None:
+        args.windows = 3 if (args.full or args.dump_outputs) else 1
+    return args
 
 
 def _run_ranks(args, n, extra_env, timeout_s, capture, extra_argv=()):
@@ -553,7 +561,7 @@ def _run_secondary(argv, limit_s, extra_env=None):
 
 
 def run_secondaries(args):
-    """What else the driver's run should put on record, each timed by a fresh child process, one after the other, started and finished BEFORE this
+    """What else a --full run puts on record, each timed by a fresh child process, one after the other, started and finished BEFORE this
     process initialises the GPU (a process that has touched the device must not start others on this pool, and the headline must not share
     the GPU with them); a failing child costs its own entry only:
       quality        the reference's whole run on this path -- 1000 captured steps with README.md:45's hyper-parameters, then Trainer.test_bitacc over 200
@@ -577,8 +585,8 @@ def run_secondaries(args):
     k = str(min(args.steps, 50))
     jobs = (("quality", [os.path.join(ROOT, "tools", "converge.py"), "graphed", "--steps", "1000", "--messages", "200"]),
             ("quality_two_ranks_gloo", [os.path.join(ROOT, "tools", "converge.py"), "dp2", "--steps", "1000", "--messages", "100"]),
-            ("counter", [os.path.abspath(__file__), "--config", "counter", "--steps", k, "--warmup", str(min(args.warmup, 5)), "--no-cpu-baseline", "--no-secondary", "--windows", "1"]),
-            ("fern", [os.path.abspath(__file__), "--config", "fern", "--steps", "5", "--warmup", "1", "--no-secondary"]),
+            ("counter", [os.path.abspath(__file__), "--config", "counter", "--steps", k, "--warmup", str(min(args.warmup, 5)), "--full", "--no-cpu-baseline", "--no-secondary", "--windows", "1"]),
+            ("fern", [os.path.abspath(__file__), "--config", "fern", "--steps", "5", "--warmup", "1", "--full", "--no-secondary"]),
             ("rank_emulation", [os.path.join(ROOT, "tools", "emulate_ranks.py"), "--steps", k]),
             ("eager_reference_trainer_shape", [os.path.join(ROOT, "tools", "trainer_shape.py"), "--steps", "330", "--both", "--evaluate"]),
             ("eval_loop", [os.path.join(ROOT, "tools", "eval_bench.py")]),
@@ -927,7 +935,9 @@ def bench_training(args, scene, real_stdout, secondary=None):
         if not ranks_agree:
             print(f"[bench] rank {rank}: replicated quantities differ between the ranks (max {hi.tolist()}, min {lo.tolist()})", file=sys.stderr)
 
-    if not args.no_graph:
+    # per-kernel times: an eager run times its kernels inside the timed steps; a captured run (replays run no Python) only in the --full pass below
+    kernels_timed = args.no_graph or args.full
+    if args.full and not args.no_graph:
         # the same kernels, launched eagerly so that HIP events can bracket them (live, same process, same inputs)
         # ... on ONE stream, back to back: the events then bracket each kernel alone, with the device busy before and after it.  (With the
         # step's streams the content render's kernels run beside the block render's: the MLP forward read 65 us instead of 57.  Draining the
@@ -962,7 +972,7 @@ def bench_training(args, scene, real_stdout, secondary=None):
     # gathered per step (GraphedWatermarkLoop(fixed_blocks=True); bit-identical renders, tests/test_gpu_fixed.py).  NOT the headline:
     # `value` above is the step that recomputes everything every step, like the reference.
     variant = None
-    if world == 1 and scene == "hotdog" and not (args.no_graph or args.fixed_blocks or args.fixed_rays or args.host_rays or args.no_variant) and not dp.exchange_active():
+    if args.full and world == 1 and scene == "hotdog" and not (args.no_graph or args.fixed_blocks or args.fixed_rays or args.host_rays or args.no_variant) and not dp.exchange_active():
         try:
             loop.close()
             loop2 = trainer.GraphedWatermarkLoop(model, optimizer, render_kwargs, data, overlap_content=not args.no_overlap, content_headroom=0.25, content_sampler=sampler,
@@ -1023,7 +1033,7 @@ def bench_training(args, scene, real_stdout, secondary=None):
     achieved = pts_big * gather_launch / enc_s if enc_s > 0 else 0.0
     traffic, l1_model, traffic_source = None, None, None
     pmc = os.path.join(ROOT, "profiles", "pmc_traffic.json")
-    if os.path.exists(pmc):
+    if kernels_timed and os.path.exists(pmc):
         try:   # HBM bytes per launch of the same kernel on the same inputs, from a separate rocprofv3 --pmc run (profiles/)
             counters = json.load(open(pmc))
             traffic = counters.get("k_encode_planes_hbm_bytes_per_launch")
@@ -1108,7 +1118,9 @@ def bench_training(args, scene, real_stdout, secondary=None):
                                  "recomputed every step (march, 17-level gather, scatter plan), like the reference",
             "loss": loss_value, "loss_image": loss_parts[0], "loss_watermark": loss_parts[1],
         },
-        "roofline": {
+    }
+    if kernels_timed:
+        line["roofline"] = {
             "kernel": "k_encode_planes",
             # what the counters show bounds this launch: the CU's vector-L1 (tag lookups + L2->L1 line fills), not HBM -- the 68 MiB working set is
             # L2 / Infinity-Cache resident.  `achieved` / `peak` / `frac` stay priced against the HBM peak (the figure north_star's ">= 40 % HBM-read
@@ -1149,24 +1161,23 @@ def bench_training(args, scene, real_stdout, secondary=None):
             "backward_mlp_plus_scatter": {"avg_s": bwd_s + sct_s, "k_field_bwd_s": bwd_s, "scatter_s": sct_s, "plan_s_off_path": plan_s},
             "whole_step": {"implemented_bytes_per_step": step_bytes, "achieved_GBps": step_bytes / (ms * 1e-3) / 1e9, "frac": step_bytes / (ms * 1e-3) / HBM_PEAK,
                            "note": "all kernels of the step (march, decoder, compositing, losses included in the time, not in the bytes)"},
-        },
-    }
-    # the MLP kernel against the matrix-core roof (north_star: "MFMA utilisation on the MLP against chip peak").
-    rows = float(mlp_rows) if mlp_rows else pts_big
-    mfma_per_wave, kind = nv.mlp_mfma_per_wave()
-    issued_flop = rows / 32.0 * mfma_per_wave * 32768
-    line["roofline_mlp"] = {
-        "kernel": f"k_field_fwd<planes> (sigma MLP + SH + colour MLP, {nv.mlp_precision_name()}) on the same launch",
-        "bound": "mfma", "achieved": (issued_flop / mlp_s / 1e12) if mlp_s > 0 else 0.0, "peak": MFMA_PEAK[kind] / 1e12, "unit": "TFLOP/s",
-        "frac": (issued_flop / mlp_s / MFMA_PEAK[kind]) if mlp_s > 0 else 0.0, "avg_launch_s": mlp_s,
-        "algorithmic_TFLOPs": (float(max(n_block, n_content)) * 20480 / mlp_s / 1e12) if mlp_s > 0 else 0.0,
-        "frac_algorithmic": (float(max(n_block, n_content)) * 20480 / mlp_s / MFMA_PEAK[kind]) if mlp_s > 0 else 0.0,
-        "mfma_per_32_points": mfma_per_wave,
-        "note": "achieved = issued MFMA FLOP/s (v_mfma_f32_32x32x16: 32768 FLOP each); algorithmic = 20 480 FLOP per point (SURVEY.md 8(d))",
-    }
+        }
+        # the MLP kernel against the matrix-core roof (north_star: "MFMA utilisation on the MLP against chip peak").
+        rows = float(mlp_rows) if mlp_rows else pts_big
+        mfma_per_wave, kind = nv.mlp_mfma_per_wave()
+        issued_flop = rows / 32.0 * mfma_per_wave * 32768
+        line["roofline_mlp"] = {
+            "kernel": f"k_field_fwd<planes> (sigma MLP + SH + colour MLP, {nv.mlp_precision_name()}) on the same launch",
+            "bound": "mfma", "achieved": (issued_flop / mlp_s / 1e12) if mlp_s > 0 else 0.0, "peak": MFMA_PEAK[kind] / 1e12, "unit": "TFLOP/s",
+            "frac": (issued_flop / mlp_s / MFMA_PEAK[kind]) if mlp_s > 0 else 0.0, "avg_launch_s": mlp_s,
+            "algorithmic_TFLOPs": (float(max(n_block, n_content)) * 20480 / mlp_s / 1e12) if mlp_s > 0 else 0.0,
+            "frac_algorithmic": (float(max(n_block, n_content)) * 20480 / mlp_s / MFMA_PEAK[kind]) if mlp_s > 0 else 0.0,
+            "mfma_per_32_points": mfma_per_wave,
+            "note": "achieved = issued MFMA FLOP/s (v_mfma_f32_32x32x16: 32768 FLOP each); algorithmic = 20 480 FLOP per point (SURVEY.md 8(d))",
+        }
     if variant is not None:
         line["config"]["fixed_blocks_variant"] = variant
-    if world == 1 and not args.no_cpu_baseline and scene == "hotdog":
+    if args.full and world == 1 and not args.no_cpu_baseline and scene == "hotdog":
         line["cpu_baseline"] = cpu_baseline(model, D, full_step_points=pts_step, threads=args.cpu_threads)
     if secondary is not None:
         quality = secondary.pop("quality", None)
@@ -1252,7 +1263,7 @@ def main():
     real_stdout = os.dup(1)
     os.dup2(2, 1)
     secondary = None
-    if (args.gpus == 1 and args.config == "hotdog" and not in_rank and not (args.no_secondary or args.no_graph or args.fixed_blocks or args.fixed_rays or args.host_rays)):
+    if (args.full and args.gpus == 1 and args.config == "hotdog" and not in_rank and not (args.no_secondary or args.no_graph or args.fixed_blocks or args.fixed_rays or args.host_rays)):
         secondary = run_secondaries(args)        # child processes, BEFORE anything here touches the GPU
     if args.config == "fern":
         bench_fern(args, real_stdout)

@@ -827,6 +827,30 @@ def test_bench_line_stays_below_the_drivers_tail_whatever_the_record_holds(tmp_p
     assert len(json.dumps(short)) <= bench.LINE_LIMIT and "secondary" in short["dropped_for_length"] and "roofline" in short and "cpu_baseline" in short
 
 
+def test_bench_plain_run_does_only_what_the_headline_needs(monkeypatch):
+    """`bench.py --gpus 1 --steps K --warmup W` starts no secondary child and times one window; --full starts the secondaries and keeps three windows, and
+    so does --dump-outputs (the dump has always been taken behind the third window); an explicit --windows wins."""
+    import sys
+    bench = _load_bench()
+    calls = []
+    monkeypatch.setattr(bench, "run_secondaries", lambda args: calls.append("secondaries") or {})
+    monkeypatch.setattr(bench, "bench_training", lambda args, scene, real_stdout, secondary=None: calls.append((args.windows, args.full, secondary is not None)))
+    for name in ("RANK", "WORLD_SIZE"):
+        monkeypatch.delenv(name, raising=False)
+    want = {(): [(1, False, False)], ("--full",): ["secondaries", (3, True, True)], ("--dump-outputs", "d"): [(3, False, False)],
+            ("--full", "--no-secondary", "--windows", "2"): [(2, True, False)]}
+    for extra, expected in want.items():
+        del calls[:]
+        monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "20", "--warmup", "5", *extra])
+        saved = os.dup(1)
+        try:
+            bench.main()
+        finally:
+            os.dup2(saved, 1)
+            os.close(saved)
+        assert calls == expected, (extra, calls)
+
+
 def _strings(o):
     if isinstance(o, str):
         yield o

@@ -1,6 +1,7 @@
 #!/bin/bash
 # usage (GPU box): tools/_ab_env.sh VAR "a b ..." [reps]  -> same-box A/B of the bench step under VAR=a, VAR=b, ...
-cd $GRAFT_REPO_ROOT
+root=$(cd "$(dirname "$0")/.." && pwd); cd "$root"
+mkdir -p "${RESULTS_DIR:-results}"; res=$(cd "${RESULTS_DIR:-results}" && pwd)      # where the runs' files go
 var=$1; vals=$2; reps=${3:-3}
 get() { python -c "
 import json,sys
@@ -8,7 +9,7 @@ l=[x for x in open(sys.argv[1]) if x.startswith('{')][-1]; d=json.loads(l); prin
 for rep in $(seq $reps); do
 for v in $vals; do
   export $var=$v
-  timeout -k 10 200 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-secondary --windows 3 > gpurun_out/ab_env.json 2> gpurun_out/ab_env.err || { echo "$var=$v FAILED"; tail -3 gpurun_out/ab_env.err; continue; }
-  get gpurun_out/ab_env.json "$var=$v"
+  timeout -k 10 200 python bench.py --steps 20 --warmup 5 --full --no-cpu-baseline --no-secondary --windows 3 > $res/ab_env.json 2> $res/ab_env.err || { echo "$var=$v FAILED"; tail -3 $res/ab_env.err; continue; }
+  get $res/ab_env.json "$var=$v"
 done
 done

@@ -14,7 +14,7 @@ failed = 0
 for k in range(pairs):
     for cap in modes:
         env = dict(base, NERFSIG_CAPTURE_COLLECTIVES=cap, MASTER_PORT=str(29655 + (k * 2 + int(cap)) % 40))
-        out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "30", "--warmup", "5", "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=300)
+        out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "30", "--warmup", "5", "--full", "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=300)
         line = [l for l in out.stdout.splitlines() if l.startswith("{")]
         if out.returncode != 0 or not line:
             failed += 1
