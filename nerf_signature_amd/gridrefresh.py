@@ -18,6 +18,7 @@ import torch
 
 from . import _native as nv
 from . import fieldops as fo
+from .capture import SegmentedCapture
 
 
 class DeviceGridRefresh:
@@ -84,22 +85,16 @@ class DeviceGridRefresh:
             raise RuntimeError("DeviceGridRefresh: the model's grid changed shape or device since this object was built")
         form = "full" if m.iter_density < 16 else "partial"
         window = int(window) if (count_ring is not None and window) else 0
-        key = (form, window, packed.data_ptr(), m.density_grid.data_ptr(), m.density_bitfield.data_ptr(), 0 if count_ring is None else count_ring.data_ptr())
+        # every address a launch of the body takes that is not this object's own: a re-allocated tensor must not be read through a graph that holds the old one
+        key = (form, window, packed.data_ptr(), m.density_grid.data_ptr(), m.density_bitfield.data_ptr(), 0 if count_ring is None else count_ring.data_ptr(),
+               step_dev.data_ptr() if window else 0, tuple(t.data_ptr() for t in m.encoder.tables()))
         if key in self.graphs:
             self.graphs[key].replay()
         elif self.capture and key in self.seen:
-            g = torch.cuda.CUDAGraph()
             if self.stream is None:
                 self.stream = torch.cuda.Stream()
-            torch.cuda.synchronize()
-            self.stream.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(self.stream):
-                g.capture_begin(capture_error_mode="thread_local")
-                try:
-                    self._body(form, window, count_ring, step_dev, packed)
-                finally:
-                    g.capture_end()
-            torch.cuda.current_stream().wait_stream(self.stream)
+            g = SegmentedCapture(stream=self.stream)      # (one segment: the body has no collectives)
+            g.capture(lambda: self._body(form, window, count_ring, step_dev, packed))
             self.graphs[key] = g
             g.replay()
         else:

@@ -30,7 +30,7 @@ from . import _native as nv
 from . import dp
 from . import fieldops as fo
 from . import tcnn_compat as tcnn
-from .capture import SegmentedCapture
+from .capture import SegmentedCapture, warm_up
 from .optim import _bump_versions
 from .hash_encoding import HashEmbedder
 from .raymarching import padded_point_count
@@ -600,46 +600,15 @@ class GraphedCleanLoop:
             # scatter's owners only -- no stale view is left behind
             p.grad = None if (self.fused_table_adam and i < 16) else g.view_as(p)
         nv.call("mlp_pack_weights", nv.ptr(self.model.sigma_net.params.detach()), nv.ptr(self.model.color_net.params.detach()), nv.ptr(self.packed), nv.stream())
-        # warm-up on a side stream (Adam state in its capturable format, module loading, RCCL's lazy set-up); it must not train
-        snap = self._snapshot()
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            for _ in range(2):
-                self._whole_step()
-        torch.cuda.current_stream().wait_stream(side)
-        torch.cuda.synchronize()
-        self._restore(snap)
+        # warm-up (Adam state in its capturable format, module loading, RCCL's lazy set-up); it must not train
+        warm_up(self._whole_step, 2, self.optimizer, self.params,
+                extra=(self.step_dev, self.count_ring, self.loss_ring, self.noises, *(self.ema_shadow or ())))
+        # the restored weights' operand image
+        nv.call("mlp_pack_weights", nv.ptr(self.model.sigma_net.params.detach()), nv.ptr(self.model.color_net.params.detach()), nv.ptr(self.packed), nv.stream())
         self.graph = SegmentedCapture()
         if self.capture:
             self.graph.capture(self._whole_step)
         return self
-
-    def _snapshot(self):
-        state = {p: {k: (v.clone() if torch.is_tensor(v) else v) for k, v in self.optimizer.state[p].items()} for p in self.params if len(self.optimizer.state[p])}
-        return ([p.detach().clone() for p in self.params], state, self.step_dev.clone(), self.count_ring.clone(), self.loss_ring.clone(),
-                None if self.noises is None else self.noises.clone(), None if self.ema_shadow is None else [t.clone() for t in self.ema_shadow])
-
-    def _restore(self, snap):
-        values, state, step_dev, count_ring, loss_ring, noises, shadow = snap
-        if shadow is not None:
-            for t, v in zip(self.ema_shadow, shadow):
-                t.copy_(v)
-        for p, v in zip(self.params, values):
-            p.copy_(v)
-        for p in self.params:
-            for k, v in self.optimizer.state[p].items():
-                if torch.is_tensor(v):
-                    if p in state and k in state[p]:
-                        v.copy_(state[p][k].to(v.device))
-                    else:
-                        v.zero_()      # state created by the warm-up: back to its initial value, same storage (the graph holds its address)
-        self.step_dev.copy_(step_dev)
-        self.count_ring.copy_(count_ring)
-        self.loss_ring.copy_(loss_ring)
-        if noises is not None:
-            self.noises.copy_(noises)
-        nv.call("mlp_pack_weights", nv.ptr(self.model.sigma_net.params.detach()), nv.ptr(self.model.color_net.params.detach()), nv.ptr(self.packed), nv.stream())
 
     # ---- the loop
     @torch.no_grad()

@@ -16,6 +16,7 @@ import torch.nn.functional as F
 from . import _native as nv
 from . import fieldops as fo
 from . import dp
+from .capture import SegmentedCapture, warm_up
 from .dp import GradExchange, exchange_active, world_size
 from .distortion import DistortionLayer, host_uniform, scaled_width
 from .hidden_models import normalize_img, set_grad_arena, set_weights_stream
@@ -470,28 +471,26 @@ class GraphedWatermarkLoop:
     adds `headroom`; `overflowed()` reports (one host read) whether any replay since the last check produced more
     points than that -- such a step dropped the rays that did not fit, like the reference's bounded mode."""
 
-    def __init__(self, model, optimizer, render_kwargs, data, lambda_w=1.0, lambda_i=1.0, lr_lambda=None, headroom=0.0, native_dense_adam=True,
-                 overlap_content=True, march_ahead=None, presum_in_adam=True, stage_in_graph=True, content_headroom=None,
-                 content_sampler=None, fixed_blocks=False, distortion="none", distortion_seed=0):
+    def __init__(self, model, optimizer, render_kwargs, data, lambda_w=1.0, lambda_i=1.0, lr_lambda=None, headroom=0.0, overlap_content=True,
+                 content_headroom=None, content_sampler=None, fixed_blocks=False, distortion="none", distortion_seed=0):
         """distortion: all five of the reference's kinds run inside the captured step -- noise | brightness | blurring as part of the decoder's first launch,
         rotation | scaling as one resampling launch in front of it.  Their random parameters are re-drawn on the device every replay (wm_distort_draw, keyed
         by distortion_seed and the replay count), except the scaling factor: it sets the decoder's input WIDTH, so prepare() captures the step once per
         possible width and step() draws the factor on the host (distortion.host_uniform, same key) and replays the capture of that width.
-        presum_in_adam: the captured optimiser kernel also writes the pre-summed codebook of the NEXT step's message
+        Next message: the captured optimiser kernel also writes the pre-summed codebook of the NEXT step's message
         (opt_codebook_adam_sel_next: +9 % traffic inside an HBM-streaming kernel instead of a 128 MiB pass at the head of every step).
         The next message is handed over one step early -- `step(message_k, next_message=message_k1)`, a one-element look-ahead over
-        the random draws of utils_wtmk_disen.py:1165; a step whose message was not announced runs the stand-alone pre-sum before
-        its replay, so `step(message)` alone stays correct.
-        march_ahead (default: with overlap_content): the block render's samples are marched at the end of the previous
+        the random draws of utils_wtmk_disen.py:1165; a step whose message was not announced (`step(message)` alone) runs the
+        stand-alone pre-sum before its replay.
+        March-ahead (with overlap_content): the block render's samples are marched at the end of the previous
         replay, beside the optimiser (the march needs rays and occupancy grid only -- nothing a step updates -- and the
         codebook Adam is an HBM stream that leaves the ALUs idle: 166 us together against 224 us one after the other,
         tools/overlap_probe.py).  The block rays of the NEXT step therefore have to be in the static buffers when a replay
         starts: pass the next step's data as `step(..., next_data=...)` (its content part is applied at that step);
-        `step(..., data=...)` still works -- it re-marches before the replay, un-overlapped.  The content render's march stays
+        `step(..., data=...)` re-marches before the replay, un-overlapped.  The content render's march stays
         at the head of its own step on the side stream: next to the optimiser as well, the two marches took longer than the
         optimiser and the pre-sum lost its cover."""
         self.distortion = None if distortion in (None, "none") else (distortion if isinstance(distortion, DistortionLayer) else DistortionLayer(distortion, distortion_seed))
-        self.march_ahead = overlap_content if march_ahead is None else bool(march_ahead)
         # fixed_blocks (off by default): the watermark-block rays are one pair of tensors per dataset
         # (nerf/provider_wtmk.py:442-494) and everything their field pass reads except the codebook is frozen in this stage, so the
         # loop marches them ONCE, keeps the base-level feature planes and the scatter plan (NeRFNetwork.fix_rays / fieldops.FixedPoints)
@@ -504,14 +503,9 @@ class GraphedWatermarkLoop:
         # content_sampler (rays.DeviceRaySampler): the step draws its own content batch -- pose, pixels, rays, ground truth -- on the
         # device, inside the captured graph, from the replay count; `data` / `next_data` then carry no content part
         self.content_sampler = content_sampler
-        self.presum_in_adam = bool(presum_in_adam)
-        # stage_in_graph: the captured step opens with loop_step_begin, which zero-fills G and fetches the step's message words from the
-        # pinned ring itself (slot = replays so far, counted on the device) -- no host-to-device copy command between two replays
-        self.stage_in_graph = bool(stage_in_graph)
         self._s_for = None            # host copy of the message the pre-sum buffer currently belongs to (None: unknown / stale)
         self.marched = None
         self._pending_content = None
-        self.native_dense_adam = native_dense_adam
         self.side_stream = torch.cuda.Stream() if overlap_content else None
         self.plan_stream = self.side_stream   # scatter plans queue behind the content render
         # The decoder's parameter-gradient kernels (~85 us, needed only by the optimiser) leave the main stream, so that the block render's backward waits for
@@ -539,7 +533,7 @@ class GraphedWatermarkLoop:
         # G and (behind it) room for the decoder's flat gradient block in one allocation: one all-reduce per step (dp.GradExchange)
         self.sink = fo.GradSink(dev, tail=sum(p.numel() for p in model.msg_decoder.parameters()))
         model.grad_sink = self.sink
-        self.exchange = GradExchange(list(model.msg_decoder.parameters()), average=not native_dense_adam)
+        self.exchange = GradExchange(list(model.msg_decoder.parameters()), average=False)
         self.data = {"watermark": {k: v.clone() for k, v in data["watermark"].items()},
                      "content": {k: v.clone() for k, v in data["content"].items()}}
         # this step's message, then the next step's, then this step's learning rate: what the host hands a step, staged together -- with an lr schedule the
@@ -553,17 +547,19 @@ class GraphedWatermarkLoop:
         self.msg_ring = torch.zeros(16, self.stage_width, dtype=torch.float32).pin_memory()      # one row per in-flight step
         self.msg_events = [None] * len(self.msg_ring)
         self.stage_counter = torch.zeros(1, dtype=torch.int32, device=dev)           # replays so far (advanced by loop_step_begin)
-        self.ring_dev = nv.fn("nsig_host_device_pointer")(ctypes.c_void_p(self.msg_ring.data_ptr())) if self.stage_in_graph else None
-        if self.stage_in_graph and not self.ring_dev:
-            self.stage_in_graph = False         # the ring is not device-mapped on this platform: keep the per-step copy
+        # the captured step opens with loop_step_begin, which zero-fills G and fetches the step's message words from the pinned ring itself
+        # (slot = replays so far, counted on the device) -- no host-to-device copy command between two replays.  Where the ring is not
+        # device-mapped (0) the host keeps the per-step copy.
+        self.ring_dev = nv.fn("nsig_host_device_pointer")(ctypes.c_void_p(self.msg_ring.data_ptr()))
+        self.stage_in_graph = bool(self.ring_dev)
         self.base_lr = float(optimizer.param_groups[0]["lr"])
         self.lr_dev = self.msg_all[2 * D]        # (a 0-dim view: the optimiser's tensor lr)
         self.lr_dev.fill_(self.base_lr)
         for g in optimizer.param_groups:
             g["lr"] = self.lr_dev          # tensor lr: the captured optimiser reads it on the device
         self.tables = model.msg_encoder.tables()
-        self.graphs = None
-        self.segments, self.between = [], []
+        self.selected = None          # the SegmentedCapture step() replays (one of self.variants)
+        self._capture_stream = None   # one stream for every capture of this loop (autograd's accumulation nodes remember the stream they were made on)
         self.sharded = False
         self.opt_shard = None
         self.out = None
@@ -577,7 +573,7 @@ class GraphedWatermarkLoop:
     def resume_at(self, step):
         """Continue a run at iteration `step` (before the first replay): the learning-rate schedule, the device-side loader's batch
         sequence and the message ring's slot all count from there."""
-        if self.graphs is not None and self._replays:
+        if self.selected is not None and self._replays:
             raise RuntimeError("resume_at: the loop has already replayed steps")
         self.steps_done = int(step)
         self._replays = int(step)
@@ -589,7 +585,7 @@ class GraphedWatermarkLoop:
         here, in the buffer the graph reads (the captured step never re-packs)."""
         self._s_for = None
         self.model._packed()
-        if self.fixed_blocks and self.graphs is not None:
+        if self.fixed_blocks and self.selected is not None:
             self._fix_blocks()       # the base tables may have been overwritten: the kept feature planes, in place
 
     @torch.no_grad()
@@ -645,8 +641,7 @@ class GraphedWatermarkLoop:
         prev = fo.set_plan_stream(self.plan_stream)    # the scatter plans need the sample positions only: beside the forward pass
         try:
             out = train_step(self.model, self.data, self.msg_dev, self.render_kwargs, self.lambda_w, self.lambda_i, side_stream=self.side_stream,
-                             presum_first=self.marched is not None,
-                             presum_adopt=self.presum_in_adam and torch.cuda.is_current_stream_capturing(),
+                             presum_first=self.marched is not None, presum_adopt=torch.cuda.is_current_stream_capturing(),
                              blocks_first=self.side_stream is not None and self._blocks_issued_first(),
                              content_backward_now=(self.lambda_i * dp.content_grad_scale(self.sharded)) if (self.content_backward_first and self.side_stream is not None) else None,
                              distortion=self.distortion)
@@ -668,30 +663,25 @@ class GraphedWatermarkLoop:
     def _optimise(self, defer_collective=False):
         """The optimiser step.  defer_collective: return the sharded optimiser's closing all-reduce as a callable instead of running it
         (the caller runs it once every forked stream has joined: a collective may end a captured segment)."""
-        post = None
-        scale = 1.0 / world_size() if self.native_dense_adam else 1.0    # the exchange leaves sums: the mean is taken here
+        scale = 1.0 / world_size()      # the exchange leaves sums: the mean is taken here
         # sharded blocks: G is already sum_r G_block_r + mean_r G_content_r (the content seeds carried 1/world): no factor
-        scale_cb = 1.0 if (self.sharded and self.native_dense_adam) else scale
+        scale_cb = 1.0 if self.sharded else scale
         tables, msg, msg_next = self.tables, self.msg_dev, self.msg_next_dev
         if self.opt_shard is not None:      # ZeRO-style: this rank updates the tables of its own bits only (dp.optimizer_shard)
             b0, b1 = self.opt_shard
             tables, msg, msg_next = self.tables[2 * b0:2 * b1], self.msg_dev[b0:b1], self.msg_next_dev[b0:b1]
-        if self.presum_in_adam:     # ... and the next step's pre-sum, in place (both renders of this step are done with the buffer)
-            S = self.model._presum_cache[1]
-            self.optimizer.step_shared_sel(tables, msg, self.sink.G, self.lr_dev, scale_cb, next_message_dev=msg_next, S_next=S)
-            if self.opt_shard is not None:  # the ranks' partial pre-sums of the next message add up to the whole one
-                import torch.distributed as dist
-                post = lambda: dp.collective(lambda: dist.all_reduce(S, op=dist.ReduceOp.SUM), last=True, name="all_reduce_presum")
-        else:
-            self.optimizer.step_shared_sel(tables, msg, self.sink.G, self.lr_dev, scale_cb)
-        if self.native_dense_adam:
-            self.optimizer.step_dense(self.lr_dev, scale)      # the decoder's parameters: opt_adam_dense
-        else:
-            self.optimizer.step()
-        if post is not None and not defer_collective:
-            post()
-            post = None
-        return post
+        # ... and the next step's pre-sum, in place (both renders of this step are done with the buffer)
+        S = self.model._presum_cache[1]
+        self.optimizer.step_shared_sel(tables, msg, self.sink.G, self.lr_dev, scale_cb, next_message_dev=msg_next, S_next=S)
+        self.optimizer.step_dense(self.lr_dev, scale)      # the decoder's parameters: opt_adam_dense
+        if self.opt_shard is None:
+            return None
+        import torch.distributed as dist      # the ranks' partial pre-sums of the next message add up to the whole one
+        post = lambda: dp.collective(lambda: dist.all_reduce(S, op=dist.ReduceOp.SUM), last=True, name="all_reduce_presum")
+        if defer_collective:
+            return post
+        post()
+        return None
 
     def _march_ahead(self):
         kw, wm = self.render_kwargs, self.data["watermark"]
@@ -719,17 +709,12 @@ class GraphedWatermarkLoop:
         if not self.march_ahead or self.fixed_blocks:
             return self._optimise()
         main = torch.cuda.current_stream()
-        if self.side_stream is not None:
-            self.side_stream.wait_stream(main)      # both backward passes of this step are done with the buffers
-            with torch.cuda.stream(self.side_stream):
-                self._march_ahead()
-                self._warm_tables()
-        post = self._optimise(defer_collective=True)
-        if self.side_stream is not None:
-            main.wait_stream(self.side_stream)
-        else:
+        self.side_stream.wait_stream(main)      # both backward passes of this step are done with the buffers
+        with torch.cuda.stream(self.side_stream):
             self._march_ahead()
             self._warm_tables()
+        post = self._optimise(defer_collective=True)
+        main.wait_stream(self.side_stream)
         if post is not None:
             post()                                  # (a collective: only after the streams have joined)
 
@@ -768,7 +753,7 @@ class GraphedWatermarkLoop:
         return m.grid_key() + tuple((t.data_ptr(), t._version) for t in m.encoder.tables())
 
     def _set_inputs(self, message, data, next_data=None, next_message=None, eager_copy=True):
-        if self.fixed_blocks and self.graphs is not None and not self._refix_pending and self._kept_key != self._kept_inputs_key():
+        if self.fixed_blocks and self.selected is not None and not self._refix_pending and self._kept_key != self._kept_inputs_key():
             self._refix_pending = True      # a base table or the occupancy grid was written since the blocks were fixed (17 attribute reads per step)
         if self._refix_pending:      # the previous call's next_data brought new block rays: they are this step's now
             self._fix_blocks()
@@ -794,39 +779,19 @@ class GraphedWatermarkLoop:
             for part in ("watermark", "content"):
                 for k, v in data.get(part, {}).items():
                     self.data[part][k].copy_(v, non_blocking=True)
-            if self.fixed_blocks and self.graphs is not None and "watermark" in data:
+            if self.fixed_blocks and self.selected is not None and "watermark" in data:
                 self._fix_blocks()              # new block rays: marched and their kept planes refreshed before the replay
-            if self.march_ahead and self.graphs is not None and "watermark" in data and not self.fixed_blocks:
+            if self.march_ahead and self.selected is not None and "watermark" in data and not self.fixed_blocks:
                 self._march_ahead()             # this step's rays arrived only now: march them before the replay
         if next_data is not None:
             if not self.march_ahead:
-                raise ValueError("next_data needs march_ahead=True")
+                raise ValueError("next_data needs overlap_content=True (the march-ahead)")
             for k, v in next_data.get("watermark", {}).items():     # nothing in the replay reads the block rays before its closing march
                 self.data["watermark"][k].copy_(v, non_blocking=True)
                 self._refix_pending = self.fixed_blocks             # (no closing march with fixed blocks: re-fixed ahead of the next replay)
             content = next_data.get("content")
             if content is not None:
                 self._pending_content = content              # marched (and compared with its images) inside its own step
-
-    @torch.no_grad()
-    def _snapshot(self):
-        params = [p for g in self.optimizer.param_groups for p in g["params"]]
-        state = {p: {k: (v.clone() if torch.is_tensor(v) else v) for k, v in self.optimizer.state[p].items()} for p in params if len(self.optimizer.state[p])}
-        return [(p, p.detach().clone()) for p in params if p.requires_grad], state
-
-    @torch.no_grad()
-    def _restore(self, snapshot):
-        saved_params, saved_state = snapshot
-        for p, v in saved_params:
-            p.copy_(v)
-        for p, st in self.optimizer.state.items():
-            for k, v in st.items():
-                if not torch.is_tensor(v):
-                    continue
-                if p in saved_state and k in saved_state[p]:
-                    v.copy_(saved_state[p][k].to(v.device))
-                else:
-                    v.zero_()      # state created by the warm-up: back to its initial value, same storage (the graph holds its address)
 
     def prepare(self, message):
         """One synchronising step to size the point buffers, warm-up on a side stream, then capture."""
@@ -866,24 +831,12 @@ class GraphedWatermarkLoop:
         model.device_select = True
         self._set_inputs(message, None)
 
-        # Warm-up on a side stream (library handles, lazily created optimiser state, MIOpen algorithm choice must all
-        # exist before capture).  The warm-up iterations must not train: parameters and optimiser state are restored.
-        snapshot = self._snapshot()
         if self.fixed_blocks:
             if not self.march_ahead:
-                raise ValueError("fixed_blocks needs march_ahead=True (the kept samples live in the march-ahead record)")
+                raise ValueError("fixed_blocks needs overlap_content=True (the kept samples live in the march-ahead record)")
             self._fix_blocks()       # before the warm-up, so that it runs -- and loads -- the kernels the captured step will use
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            for _ in range(3):
-                self.optimizer.zero_grad(set_to_none=True)
-                self._forward_backward()
-                self.exchange(self.sink.G)
-                self._optimise()
-        torch.cuda.current_stream().wait_stream(side)
-        torch.cuda.synchronize()
-        self._restore(snapshot)
+        # warm-up (library handles, lazily created optimiser state, MIOpen algorithm choice must all exist before capture); it must not train
+        warm_up(self._warm_up_step, 3, self.optimizer, [p for g in self.optimizer.param_groups for p in g["params"] if p.requires_grad])
 
         # One capture per shape the step can take: a single one, except under `distortion='scaling'`, whose factor sets the decoder's input width
         # (floor(W * sf), sf in [0.75, 1.25)): one capture per width, each in a memory pool of its own; step() draws the factor on the host
@@ -903,97 +856,86 @@ class GraphedWatermarkLoop:
     def _select(self, key):
         """Make the capture of this shape the one step() replays and overflowed() / point_counts() read."""
         v = self.variants[key]
-        self.segments, self.between, self.graphs, self.out = v["segments"], v["between"], v["graphs"], v["out"]
+        self.selected, self.out = v["capture"], v["out"]
         self.capacity_rows, self.capacities = v["capacity_rows"], v["capacities"]
+
+    @property
+    def segments(self):
+        return self.selected.segments if self.selected is not None else []
+
+    @property
+    def between(self):
+        return self.selected.between if self.selected is not None else []
+
+    @property
+    def graphs(self):
+        return tuple(self.selected.segments) if self.selected is not None else None
+
+    @property
+    def march_ahead(self):
+        """The block render's samples are marched at the end of the previous replay (see __init__): whenever there is a side stream."""
+        return self.side_stream is not None
+
+    def _warm_up_step(self):
+        self.optimizer.zero_grad(set_to_none=True)
+        self._forward_backward()
+        self.exchange(self.sink.G)
+        self._optimise()
+
+    def _captured_step(self):
+        out = self._forward_backward()
+        self.exchange(self.sink.G)
+        self._optimise_and_march()
+        return out
+
+    def _segment_ended(self):
+        fo.forget_plan_events()          # events recorded in a finished capture must not be waited on in the next one (or by whatever comes next)
+        self.model._presum_event = None
+
+    def _first_segment_replayed(self):
+        slot = self._replays % len(self.msg_ring)
+        self._replays += 1       # immediately: the device counter has advanced whatever happens to the rest of this step
+        if self.stage_in_graph:  # the ring row of this step may be rewritten once this replay's opening kernel has read it
+            ev = torch.cuda.Event()
+            ev.record()
+            self.msg_events[slot] = ev
 
     def _capture(self, cap_block, cap_content):
         model = self.model
         self.optimizer.zero_grad(set_to_none=True)
         if self.march_ahead and not self.fixed_blocks:
             self._march_ahead()      # the first replay's samples (buffers outside the graph's pool, re-marched in place by every replay)
-        # Segmented capture: one hipGraph per stretch between collectives.  A collective reached while capturing (dp.collective: the
-        # all-gather of the rendered blocks, the gradient all-reduce) ends the running capture, is remembered as the eager call that
-        # follows that segment in every replay, and the next segment begins in the same memory pool.  One rank: a single segment.
-        # thread_local: with more than one rank the process group's watchdog thread queries events while we capture; only this
-        # thread's calls belong to the capture.
-        self.segments, self.between = [torch.cuda.CUDAGraph()], []
-
-        open_capture = [True]
-
-        def boundary(fn, last=False):
-            self.segments[-1].capture_end()
-            fo.forget_plan_events()          # events recorded in the finished capture must not be waited on in the next one
-            self.model._presum_event = None
-            self.between.append(fn)
-            if last:                         # the step ends with this collective: no empty segment behind it
-                open_capture[0] = False
-                return
-            g = torch.cuda.CUDAGraph()
-            self.segments.append(g)
-            g.capture_begin(pool=self.segments[0].pool(), capture_error_mode="thread_local")
-
-        import gc
-        gc.collect()
-        torch.cuda.synchronize()
-        dp.drain_watchdog()       # nothing of the warm-up's collectives may be left with ProcessGroupNCCL's watchdog thread when the capture begins (dp.py)
-        if getattr(self, "_capture_stream", None) is None:      # one stream for every capture of this loop (autograd's accumulation nodes remember the stream they were made on)
+        if self._capture_stream is None:
             self._capture_stream = torch.cuda.Stream()
-        capture_stream = self._capture_stream
-        capture_stream.wait_stream(torch.cuda.current_stream())
-        prev = dp.set_boundary(boundary)
-        try:
-            with torch.cuda.stream(capture_stream):
-                self.segments[0].capture_begin(capture_error_mode="thread_local")
-                self.out = self._forward_backward()
-                self.exchange(self.sink.G)
-                self._optimise_and_march()
-                if open_capture[0]:
-                    self.segments[-1].capture_end()
-        finally:
-            dp.set_boundary(prev)
-        torch.cuda.current_stream().wait_stream(capture_stream)
-        fo.forget_plan_events()              # (events recorded in the finished capture: not to be waited on by whatever comes next)
-        self.model._presum_event = None
+        # one hipGraph per stretch between collectives (the all-gather of the rendered blocks, the gradient all-reduce); one rank: a single segment
+        capture = SegmentedCapture(self._capture_stream, on_boundary=self._segment_ended, after_first=self._first_segment_replayed)
+        out = capture.capture(self._captured_step)
         capacity_rows = [(model.local_step - 2) % 16, (model.local_step - 1) % 16]
         self.content_capacity = cap_content
         if self.marched is not None:        # only the content render used the ring during the capture
             capacity_rows = [(model.local_step - 1) % 16]
         # the counters are written in issue order: with a side stream train_step issues the content render first
-        return {"segments": self.segments, "between": self.between, "graphs": tuple(self.segments), "out": self.out, "capacity_rows": capacity_rows,
+        return {"capture": capture, "out": out, "capacity_rows": capacity_rows,
                 "capacities": [cap_block, cap_content] if self._blocks_issued_first() else [cap_content, cap_block]}
 
     def step(self, message, data=None, next_data=None, next_message=None):
         """message: CPU float tensor of 0./1.; data: optional new rays/images of THIS step, next_data: of the next one (same
         shapes; see march_ahead).  Returns the static output tuple of train_step (valid until the next step; values are ready
         when the stream reaches them)."""
-        if self.graphs is None:
+        if self.selected is None:
             if data is not None:
                 self._set_inputs(message, data)
                 data = None
             self.prepare(message)
-        unannounced = False
-        if self.presum_in_adam:
-            msg_cpu = message.detach().to("cpu", torch.float32)
-            unannounced = self._s_for is None or not torch.equal(self._s_for, msg_cpu)
+        unannounced = self._s_for is None or not torch.equal(self._s_for, message.detach().to("cpu", torch.float32))
         self._set_inputs(message, data, next_data, next_message, eager_copy=unannounced or not self.stage_in_graph)
-        if self.presum_in_adam:
-            if unannounced:
-                self.model.prepare_message(self.msg_dev)     # not announced one step early: the stand-alone pass, before the replay
-            self._s_for = None if next_message is None else next_message.detach().to("cpu", torch.float32).clone()
+        if unannounced:
+            self.model.prepare_message(self.msg_dev)     # not announced one step early: the stand-alone pass, before the replay
+        self._s_for = None if next_message is None else next_message.detach().to("cpu", torch.float32).clone()
         if self.distortion is not None and self.distortion.name == "scaling":      # this step's factor (host-side draw) and the capture of its width
             self.distortion.set_scaling(host_uniform(self.distortion.seed, self._replays, 0.75, 1.25))
             self._select(self.distortion.out_width(self.data["watermark"]["rays_o_block"].shape[2]))
-        for i, g in enumerate(self.segments):
-            g.replay()
-            if i == 0:
-                slot = self._replays % len(self.msg_ring)
-                self._replays += 1       # immediately: the device counter has advanced whatever happens to the rest of this step
-                if self.stage_in_graph:  # the ring row of this step may be rewritten once this replay's opening kernel has read it
-                    ev = torch.cuda.Event()
-                    ev.record()
-                    self.msg_events[slot] = ev
-            if i < len(self.between):
-                self.between[i]()        # the collective between two segments (RCCL; ordered after the segment on this stream)
+        self.selected.replay()
         self.steps_done += 1
         if self.opt_shard is not None:
             self.model._codebook_stale = True      # tables of the other ranks' bits: stale here until gather_codebook()
@@ -1003,7 +945,7 @@ class GraphedWatermarkLoop:
         """One host read: if the last replay produced more points than the buffers hold (its overflowing rays were dropped, like the
         reference's bounded mode), re-size from the current rays with `growth` times the headroom and capture again.  Returns True when
         it re-captured.  Callers that draw new rays every step call this now and then, outside their timed region."""
-        if self.graphs is None:
+        if self.selected is None:
             return False
         over = bool(self.overflowed())
         if exchange_active():       # re-capturing runs warm-up steps with collectives in them: every rank or none
@@ -1017,7 +959,7 @@ class GraphedWatermarkLoop:
         self.content_headroom = (1.0 + self.content_headroom) * growth - 1.0
         message = self.msg_dev.detach().to("cpu", torch.float32)
         torch.cuda.synchronize()
-        self.graphs, self.segments, self.between, self.marched = None, [], [], None
+        self.selected, self.marched = None, None
         self.model.drop_marched()
         self._s_for = None
         self.prepare(message)

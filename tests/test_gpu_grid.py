@@ -256,3 +256,32 @@ def test_device_side_refresh_restates_update_extra_state_step_by_step():
         finals.append((m2.density_grid.clone(), m2.density_bitfield.clone(), m2.mean_density))
     assert torch.equal(finals[0][0], finals[1][0]) and torch.equal(finals[0][1], finals[1][1]) and finals[0][2] == finals[1][2]
     assert not torch.equal(finals[0][0], finals[2][0])
+
+
+def test_captured_refresh_follows_a_reallocated_step_count():
+    """DeviceGridRefresh.run keys its captured graphs on the addresses the refresh reads: a step count handed over in a new tensor of the same value is not
+    read through the graph captured with the old one (whose memory now holds another value) -- the next run is a new key, eager and then captured, and grid,
+    bitfield and mean sample count stay those of an uncaptured twin."""
+    from nerf_signature_amd import fieldops as fo
+    from nerf_signature_amd.gridrefresh import DeviceGridRefresh
+    m, twin = _refresh_model(2.0), _refresh_model(2.0)
+    packed = fo.pack_weights(m.sigma_net.params, m.color_net.params)
+    ring = torch.zeros(16, 2, dtype=torch.int32, device="cuda")
+    ring[:, 0] = (torch.arange(16, dtype=torch.int32) * 1000 + 13).cuda()
+    r, r_twin = DeviceGridRefresh(m, seed=3, capture=True), DeviceGridRefresh(twin, seed=3, capture=False)
+    old = torch.tensor([21], dtype=torch.int32, device="cuda")
+    for _ in range(2):                                                                        # eager, captured
+        r.run(packed, ring, old, window=5)
+        r_twin.run(packed, ring, old, window=5)
+    assert len(r.graphs) == 1
+    new = old.clone()
+    assert new.data_ptr() != old.data_ptr()
+    old.fill_(3)                                                                              # (the caller let it go: its memory holds something else now)
+    seen = len(r.seen)
+    for k in range(2):
+        r.run(packed, ring, new, window=5)
+        r_twin.run(packed, ring, new, window=5)
+        assert len(r.seen) == seen + 1 and len(r.graphs) == 1 + k                             # not the old graph: a new key, eager, then captured
+    torch.cuda.synchronize()
+    assert torch.equal(m.density_grid, twin.density_grid) and torch.equal(m.density_bitfield, twin.density_bitfield)
+    assert m.mean_count == twin.mean_count and m.mean_density == twin.mean_density
