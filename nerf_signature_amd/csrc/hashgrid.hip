@@ -235,9 +235,9 @@ __global__ void __launch_bounds__(1024) k_scatter_level(const float *__restrict_
 // Two measurements shape this version (tools/micro/lds_atomic_rate.hip, tools/scatter_timing.py):
 //  * ds_add_f32 retires 0.33 lane-operations per clock per CU; ds_add_u64 4.4 (ds_add_u32 5.2).  The scatter's 20.6 M LDS float
 //    atomics alone are 100 us -- that, not the instruction count, bounded k_scatter_sliced.  So the owners accumulate in 64-bit
-//    FIXED POINT: contribution * 2^k rounded to an integer, k chosen from the largest |gradient| of the launch so that 2^11
-//    maximal contributions cannot overflow; everything up to 2^-51 of that maximum is represented, the integer sum is exact
-//    and independent of the order of the atomics, and the owner converts back once per row.
+//    FIXED POINT: contribution * 2^k rounded to an integer, k chosen from the largest |gradient| of the launch and the slice's
+//    entry count so that no row sum can overflow (fixed_scale); the integer sum is exact and independent of the order of the
+//    atomics, and the owner converts back once per row.
 //  * with 16 bytes per (row, feature pair) an LDS slice holds 8192 rows: 64 slices.  Letting every owner test every point would
 //    double the redundant work, so the (point, (dy,dz) pair) hits are first grouped by slice with an exact two-pass counting
 //    sort -- count, then write at atomically reserved positions -- and an owner streams only its own entries.  An entry is
@@ -777,6 +777,18 @@ NSIG_EXPORT int level_entries_phase_ticks(unsigned long long *out144, int reset)
 // also with the owners' loads really in flight: 369-375 us against 365-373 on the 16-level scatter; the f64 instructions are ~5 us of the owners, LABNOTES 17a)
 __device__ inline long long to_fixed(float c, int k) { return __double2ll_rn(ldexp((double)c, k)); }
 
+// The fixed-point scale k of a slice (contribution c -> round(c * 2^k)), shared by the owners and the merge so that the two cannot disagree.
+// Every |contribution| <= gmax < 2^E and a row receives at most one per entry of its slice, so a row's |sum| <= n * gmax < 2^(E + bits(n)):
+// k = 62 - E - bits(n) keeps it below 2^62 (rounding adds at most n / 2).  Up to 2^11 entries the scale stays at 51 - E, 2^-51 of the
+// maximum.  This holds for ANY distribution of the entries over the rows: one row may take all of them (every sample of a launch on one
+// vertex) -- the codebook's routes once assumed 2^11 hits per row at most and wrapped modulo 2^64 beyond.  n is the slice's total entry
+// count, not one replica's share: the merge adds the replicas' sums.  gmax_bits: a float bit pattern below +inf (a poisoned launch uses no scale).
+__device__ inline int fixed_scale(uint32_t gmax_bits, uint32_t n) {
+    int E;
+    frexpf(__uint_as_float(gmax_bits), &E);
+    return n > 2048u ? 62 - E - (32 - __builtin_clz(n)) : 51 - E;
+}
+
 // torch.optim.Adam's update of one element (the dense passes further down and the owners' fused form share it)
 __device__ inline void adam_update(float g, float &p, float &m, float &v, float beta1, float beta2, float eps, float step_size, float inv_bc2_sqrt) {
     m = m + (1.0f - beta1) * (g - m);                 // exp_avg.lerp_(grad, 1 - beta1)
@@ -805,11 +817,11 @@ struct OwnerAdam {
 // inside this launch -- slabs, a ticket per slice, the last arriver sums -- needs an agent-scope release / acquire around the ticket, i.e. a write-back and an
 // invalidate of the XCD's whole L2 per workgroup: 29 -> 150 us, profiles/r06_exact_merge_ab.txt.  A launch boundary gives the same visibility for one
 // launch gap.)
-// scale_by_count: the fixed-point scale leaves room for as many maximal contributions as the slice has entries (the base levels of stage 1: at
-// level 0 a million samples share 4913 rows, far more than the 2^11 per row the codebook level's scale assumes).
+// The fixed-point scale leaves room for as many maximal contributions as the slice has entries (fixed_scale): at level 0 of stage 1 a million samples
+// share 4913 rows, and a codebook launch may put all of its points on one vertex.
 // set_max (optional): [sets][n_set_max] partial maxima of |contribution| (float bit patterns) whose maximum replaces the header's gmax_bits.
 __global__ void __launch_bounds__(1024) k_scatter_binned(const BinHeader *__restrict__ hd_all, const uint4 *__restrict__ queue_all, uint32_t M,
-                                                         ScatterTargets tg, uint32_t replicas, uint32_t scale_by_count = 0,
+                                                         ScatterTargets tg, uint32_t replicas,
                                                          const uint32_t *__restrict__ set_max = nullptr, uint32_t n_set_max = 0, OwnerAdam adam = OwnerAdam{},
                                                          unsigned long long *__restrict__ slabs = nullptr) {
     extern __shared__ unsigned long long acc64[];  // [kBinRows][2] fixed point
@@ -841,7 +853,7 @@ __global__ void __launch_bounds__(1024) k_scatter_binned(const BinHeader *__rest
 #pragma unroll
         for (int u = 0; u < kAhead; ++u) cur[u] = __builtin_nontemporal_load(q + min(beg + u * blockDim.x + threadIdx.x, end - 1));
     }
-    // |contribution| <= gmax < 2^E; 2^11 of them stay below 2^62 with k = 51 - E.  A non-finite gradient anywhere in the launch
+    // The scale: fixed_scale (from gmax and the slice's entry count n).  A non-finite gradient anywhere in the launch
     // (an overflowing scaled loss under torch's GradScaler) poisons every row of G with NaN, so that the scaler's inf check sees it
     // exactly as it sees the inf/NaN float sums of the reference's dense gradients and skips the step.
     uint32_t gb = hd->gmax_bits, mx = 0;
@@ -861,10 +873,7 @@ __global__ void __launch_bounds__(1024) k_scatter_binned(const BinHeader *__rest
         gb = smax;
     }
     const bool poisoned = gb >= 0x7f800000u;
-    int E;
-    frexpf(__uint_as_float(poisoned ? 0x3f800000u : gb), &E);
-    int k = poisoned ? 0 : 51 - E;
-    if (scale_by_count && !poisoned && n > 2048u) k = 62 - E - (32 - __builtin_clz(n));      // |sum| <= n * gmax < 2^(E + ceil(log2(n + 1))) stays below 2^62
+    const int k = poisoned ? 0 : fixed_scale(gb, n);
     float *out = G + 2 * (size_t)slice * kBinRows;
     if (beg >= end && !adam.on) {      // (uniform) nothing for this owner (two of level 0's 64 slices hold no cell pair at all; a replica beyond a short slice's end -- it leaves no slab, and the merge knows): its rows are zeros, no accumulators needed
         if (poisoned || replicas == 1) {
@@ -953,7 +962,8 @@ __global__ void __launch_bounds__(1024) k_scatter_binned(const BinHeader *__rest
 
 // The exact merge of a slice's replicas (see k_scatter_binned).  blockIdx.x = slice * kMergeParts + part: a quarter of the slice's words per workgroup, one 8-byte
 // fixed-point sum per thread and trip -- consecutive lanes on consecutive words, for the loads and for the atomics behind them (an atomic wave instruction leaves
-// the L2 as one request per 64 bytes it touches; a row pair per lane would double them).  The scale is the one the replicas used (the launch's gmax); a poisoned
+// the L2 as one request per 64 bytes it touches; a row pair per lane would double them).  The scale is the one the replicas used (fixed_scale of the launch's
+// gmax and the slice's entry count); a poisoned
 // launch has written its NaNs already.  One float atomic per non-zero element and launch.
 constexpr uint32_t kMergeParts = 4, kMergeThreads = 1024;
 __global__ void __launch_bounds__(kMergeThreads) k_scatter_merge(const BinHeader *__restrict__ hd_all, ScatterTargets tg, uint32_t replicas,
@@ -964,9 +974,7 @@ __global__ void __launch_bounds__(kMergeThreads) k_scatter_merge(const BinHeader
     const uint32_t slice = blockIdx.x / kMergeParts, part = blockIdx.x - slice * kMergeParts;
     const uint32_t n = hd->counts[slice], gb = hd->gmax_bits;
     if (n == 0 || gb >= 0x7f800000u) return;      // (uniform) an empty slice; a poisoned launch
-    int E;
-    frexpf(__uint_as_float(gb), &E);
-    const int k = 51 - E;
+    const int k = fixed_scale(gb, n);
     const uint32_t chunk = ceil_div(n, replicas);
     const unsigned long long *slice_slabs = slabs + ((size_t)blockIdx.y * kBinSlices + slice) * replicas * kSlab + (size_t)part * kPartWords;
     unsigned long long sum[kTrips];
@@ -1587,7 +1595,7 @@ static int launch_binned(const float *rec, uint32_t M, uint32_t sets, const Scat
     k_bin_scan<<<sets, 1024, 0, st>>>(hd, blocks);
     k_bin_write<<<dim3(blocks, sets), kBinThreads, 0, st>>>(rec, M, hd, queue);
     unsigned long long *slabs = replicas > 1 ? reinterpret_cast<unsigned long long *>(queue + (size_t)sets * 4 * M) : nullptr;      // (the merge scratch follows the queues)
-    k_scatter_binned<<<dim3(kBinSlices * replicas, sets), 1024, lds, st>>>(hd, queue, M, tg, replicas, 0u, nullptr, 0u, OwnerAdam{}, slabs);
+    k_scatter_binned<<<dim3(kBinSlices * replicas, sets), 1024, lds, st>>>(hd, queue, M, tg, replicas, nullptr, 0u, OwnerAdam{}, slabs);
     if (replicas > 1) k_scatter_merge<<<dim3(kBinSlices * kMergeParts, sets), kMergeThreads, 0, st>>>(hd, tg, replicas, slabs);
     return check_launch(who);
 }
@@ -1630,7 +1638,7 @@ NSIG_EXPORT int hg_scatter_planned(const void *plan, uint32_t M, float *G, nsig_
     // replicas: 1 -> 63 us, 2 -> 40, 4 -> 32, 8 -> 43 on 5.2 M entries (more owners stream less each, but merge with more float atomics)
     // (with the owners' pipelined queue walk, round 5: 2 -> 31.0, 3 -> 28.5, 4 -> 28.9, 6 -> 37.4, 8 -> 43.2 us; the step the same for 2..4)
     k_scatter_binned<<<dim3(kBinSlices * kBinReplicas, 1), 1024, (size_t)kBinRows * 2 * sizeof(unsigned long long), as_stream(stream)>>>(pl.hd, pl.queue, M, tg,
-                                                                                                                                           kBinReplicas, 0u, nullptr, 0u,
+                                                                                                                                           kBinReplicas, nullptr, 0u,
                                                                                                                                            OwnerAdam{}, pl.slabs);
     k_scatter_merge<<<dim3(kBinSlices * kMergeParts, 1), kMergeThreads, 0, as_stream(stream)>>>(pl.hd, tg, kBinReplicas, pl.slabs);
     return check_launch("hg_scatter_planned");
@@ -1715,10 +1723,10 @@ static int levels_scatter_launch(const char *who, const float *xyzs, uint32_t M,
         ScatterTargets one{};
         one.g[0] = tg.g[l];
         k_scatter_binned<<<dim3(kBinSlices, 1), 1024, (size_t)kBinRows * 2 * sizeof(unsigned long long), st>>>(pl.hd + l, pl.queue + (size_t)l * kLevelQueueStride * M,
-                                                                                                               M_stride, one, 1u, 1u, pl.chunk_max + (size_t)l * pl.n_chunks, pl.n_chunks);
+                                                                                                               M_stride, one, 1u, pl.chunk_max + (size_t)l * pl.n_chunks, pl.n_chunks);
     }
 #else
-    k_scatter_binned<<<dim3(kBinSlices, NSIG_BASE_LEVELS), 1024, (size_t)kBinRows * 2 * sizeof(unsigned long long), st>>>(pl.hd, pl.queue, M_stride, tg, 1u, 1u,
+    k_scatter_binned<<<dim3(kBinSlices, NSIG_BASE_LEVELS), 1024, (size_t)kBinRows * 2 * sizeof(unsigned long long), st>>>(pl.hd, pl.queue, M_stride, tg, 1u,
                                                                                                                           pl.chunk_max, pl.n_chunks, adam);
 #endif
     return check_launch(who);

@@ -72,6 +72,65 @@ def trilerp(e, w):
     return c0 * (1 - wz) + c1 * wz
 
 
+def scatter_ref(x01, dfeat, resolution):
+    """The table gradient of one level in float64: G[row_k] += w_k * dfeat for the 8 corners of every point, i.e. autograd of
+    trilerp(table[rows], w) (hash_encoding.py:73-94).  Rows and the fp32 weights w as voxel_lookup computes them; the corner
+    weights and the sums in float64.  x01 [M,3] fp32, dfeat [M,2] fp32 -> G [2^19, 2] float64.  A non-finite gradient
+    propagates into the rows it reaches."""
+    rows, w, _ = voxel_lookup(x01, resolution)
+    w = w.double()
+    f = torch.stack([1.0 - w, w], dim=1)                            # [M, side, axis]
+    cw = f[:, _CORNERS[:, 0], 0] * f[:, _CORNERS[:, 1], 1] * f[:, _CORNERS[:, 2], 2]   # [M,8]
+    G = torch.zeros(1 << LOG2_T, 2, dtype=torch.float64)
+    G.index_add_(0, rows.reshape(-1), (cw.unsqueeze(-1) * dfeat.double().unsqueeze(1)).reshape(-1, 2))
+    return G
+
+
+U32 = 2.0 ** -24                    # unit roundoff of fp32
+
+
+def fixed_quantum(gmax, n_slice_max):
+    """Upper bound of 2^-k, the fixed-point routes' grid: k = 62 - E - max(11, bit length of the slice's entry count) with gmax < 2^E
+    (nerf_signature_amd/csrc/hashgrid.hip fixed_scale).  A slice holds at most n_slice_max entries."""
+    E = math.frexp(gmax)[1] if gmax > 0 else 0
+    return 2.0 ** (E - 62 + max(11, int(n_slice_max).bit_length()))
+
+
+def scatter_row_stats(x01, dfeat, res):
+    """(contributions per row [T,1], float64 sum of |contribution| per row [T,2]) of the lookup at `res`: what scatter_tolerance scales with."""
+    rows, _, _ = voxel_lookup(x01, res)
+    return torch.bincount(rows.reshape(-1), minlength=1 << LOG2_T).double().unsqueeze(1), scatter_ref(x01, dfeat.abs(), res)
+
+
+def scatter_tolerance(want, stats, fixed, prefill=0.0, quantum=None, run_sums=0):
+    """Per-element bound [T,2] of |G - want| for a GPU scatter route, want = prefill + the float64 sum, stats = scatter_row_stats() of the launch:
+      every route: the fp32 corner weights ((g * fz) * fy) * fx -- each factor 1 - w and each product rounded: 8 u of the row's sum of |contribution|;
+      float routes (fp32 atomics, global or LDS): one rounding per add, n_row adds plus <= 16 partial sums of the replicas into G, each within u of
+                    (|prefill| + sum |c|); a float atomic may flush a subnormal sum: 2^-126 per add;
+      fixed-point routes: each contribution rounded to the grid `quantum` = 2^-k (half a quantum each), the integer sum exact, then two fp32
+                    roundings (the conversion and the add into G); a subnormal contribution is rounded in the weight products: 2^-148 each;
+      run_sums: contributions pre-summed in fp32 over runs of up to `run_sums` samples (merged stage-1 levels): run_sums u of sum |c| more."""
+    n_row, mag = stats
+    pre = torch.as_tensor(prefill, dtype=torch.float64).abs()
+    if fixed:
+        return n_row * quantum / 2 + (8 + run_sums) * U32 * mag + 2 * U32 * (want.abs() + pre + mag) + n_row * 2.0 ** -148
+    return (8 + run_sums) * U32 * mag + (n_row + 16) * U32 * (mag + pre) + U32 * want.abs() + n_row * 2.0 ** -126
+
+
+def assert_scatter_close(G, want, stats, fixed, prefill=0.0, quantum=None, run_sums=0, what=""):
+    """G (a device table [T,2]) within scatter_tolerance() of want, element by element; a NaN where want is finite fails."""
+    tol = scatter_tolerance(want, stats, fixed, prefill, quantum, run_sums)
+    n_row = stats[0]
+    got = G.detach().double().cpu()
+    err = (got - want).abs()
+    bad = ~(err <= tol)
+    if bool(bad.any()):
+        r, c = (int(v) for v in torch.nonzero(bad)[0])
+        r2, c2 = divmod(int(torch.argmax((err - tol).nan_to_num(float("inf")).reshape(-1))), 2)
+        raise AssertionError(f"{what}: {int(bad.sum())} elements off; first row {r}[{c}]: got {float(got[r, c])!r} want {float(want[r, c])!r} "
+                             f"tol {float(tol[r, c]):.3g} ({int(n_row[r, 0])} contributions); worst row {r2}[{c2}]: got {float(got[r2, c2])!r} "
+                             f"want {float(want[r2, c2])!r} tol {float(tol[r2, c2]):.3g}")
+
 def base_encode(x01, tables):
     """HashEmbedder.forward, hash_encoding.py:96-111.  tables: 16 x [T,2] -> [M,32]."""
     outs = []

@@ -1,6 +1,7 @@
 """GPU parity of the hash-grid and field-network kernels against the golden vectors / the CPU oracle,
 through the C ABI.  Tolerances: hash rows bit-exact; encoder features to fp32 round-off; sigma/rgb and
 gradients within the path's stated 1e-3 (north_star), measured far tighter."""
+import math
 import os
 
 import numpy as np
@@ -341,6 +342,10 @@ def test_sliced_scatter_equals_pointwise_scatter(fo, tables):
     fo.codebook_scatter_sliced(same, Ga, binned=False)
     fo.codebook_scatter_sliced(same, Gb, binned=True)
     assert float((Ga - Gb).norm() / Ga.norm()) < 1e-5 and int((Gb != 0).sum()) <= 16
+    xs, ds = ((pts[:1] + 1.0) / 2.0).repeat(5000, 1).cpu(), same[:, 5:7].cpu()          # ... and both against the float64 sum
+    stats, ref = fr.scatter_row_stats(xs, ds, CB_RES), fr.scatter_ref(xs, ds, CB_RES)
+    fr.assert_scatter_close(Ga, ref, stats, False, what="5000 copies, sliced")
+    fr.assert_scatter_close(Gb, ref, stats, True, quantum=fr.fixed_quantum(float(ds.abs().max()), 4 * 5000), what="5000 copies, binned")
     # planned route: destinations from the positions alone (also on a side stream), gradients written straight into the queue
     for stream in (None, torch.cuda.Stream()):
         prev = fo.set_plan_stream(stream)
@@ -370,6 +375,184 @@ def test_sliced_scatter_equals_pointwise_scatter(fo, tables):
     e0 = queue[d0]
     assert torch.equal(e0[:, 0] & 0xFFFF, cell[:, 0]) and torch.equal((e0[:, 0] >> 16) & 0x1FFF, ((hy ^ hz) & 0x1FFF).int())
     assert torch.equal(e0[:, 1], words[:, 2])                 # the x weight, bit for bit
+
+
+# ---- every codebook scatter route against the float64 sum (oracle.field_ref.scatter_ref) -------------------------------------------------------------------
+T_ROWS = 1 << 19
+CB_RES = fr.level_resolutions(64, 2048, 2048)[0]
+
+
+def _records(x01, dfeat):
+    """[M,8] scatter records of points x01 [M,3] (device, fp32) with feature gradients dfeat [M,2]: the layout pinned in
+    test_sliced_scatter_equals_pointwise_scatter (integer cell, the three weights, the two gradients, one pad word)."""
+    M = x01.shape[0]
+    cell = torch.floor(x01.clamp(0, 1) * 2048.0).int()
+    rec = torch.zeros(M, 8, dtype=torch.float32, device=x01.device)
+    words = rec.view(torch.int32)
+    words[:, 0] = cell[:, 0] | (cell[:, 1] << 16)
+    words[:, 1] = cell[:, 2]
+    rec[:, 2:5] = (x01 - cell.float() * (1.0 / 2048.0)) * 2048.0
+    rec[:, 5:7] = dfeat
+    return rec
+
+
+def _cb_case(name, seed=0):
+    """(x01 [M,3], dfeat [M,2]) on the CPU for one hit distribution of the codebook scatter tests."""
+    rng = np.random.RandomState(seed)
+    if name.startswith(("vertex", "cell")):            # hot rows: N copies of one point, gradient 1.0 | 0.75 | random sign
+        kind, N, g = name.split("_")
+        N = int(N)
+        p = np.array([1000, 517, 1301], np.float32) / np.float32(2048) if kind == "vertex" else np.array([0.37, 0.61, 0.19], np.float32)
+        x = np.repeat(p[None], N, 0)
+        if g == "mixed":
+            d = rng.choice([-1.0, 1.0], (N, 2)).astype(np.float32)
+        else:
+            d = np.full((N, 2), float(g), np.float32)
+        return torch.from_numpy(x), torch.from_numpy(d)
+    M = 65536
+    x = rng.rand(M, 3).astype(np.float32)
+    x[:8] = [[0, 0, 0], [1, 1, 1], [0.5, 0.5, 0.5], [1, 0, 0.25], [np.float32(1) - np.float32(2 ** -24)] * 3, [0.3, 0.7, 0.9], [0.3, 0.7, 0.9], [2 / 2048, 4 / 2048, 8 / 2048]]
+    d = rng.randn(M, 2).astype(np.float32)
+    if name == "uniform":
+        d[100:200] = 0.0
+    elif name == "cancel":                             # equal and opposite pairs on the same rows: exactly 0 on the fixed-point routes
+        x[1::2] = x[0::2]
+        d[1::2] = -d[0::2]
+    elif name == "hotcancel":
+        x[:] = x[2]
+        d[:] = 1.0
+        d[1::2] = -1.0
+    elif name == "range":                              # one outlier 2^30 x the rest: rows with small contributions only
+        d *= np.float32(2.0 ** -30)
+        d[5] = (1.0, -1.0)
+    elif name.startswith("gmax"):                      # the largest |gradient| a power of two | the float below one | subnormal | all zero
+        v = {"gmax_pow2": 4.0, "gmax_below": float(np.nextafter(np.float32(4), np.float32(0))), "gmax_subnormal": 2.0 ** -130, "gmax_zero": 0.0}[name]
+        d = (np.sign(d) * np.float32(v)).astype(np.float32)
+        if name == "gmax_subnormal":
+            x[:] = x[7]                                # a vertex: weights 0 and 1, the products exact
+    return torch.from_numpy(x), torch.from_numpy(d)
+
+
+CB_CASES = ["uniform", "cancel", "hotcancel", "range", "gmax_pow2", "gmax_below", "gmax_subnormal", "gmax_zero"] + \
+    [f"{k}_{n}_{g}" for k in ("vertex", "cell") for n in (4095, 8193, 65536) for g in ("1.0", "0.75", "mixed")]
+CB_ROUTES = ["pointwise", "sliced", "binned"]
+
+
+def _cb_route(fo, route, x01, dfeat, G):
+    if route == "pointwise":
+        fo.codebook_scatter(x01, dfeat, G)
+    elif route == "auto":
+        fo.codebook_scatter_sliced(_records(x01, dfeat), G)
+    else:
+        fo.codebook_scatter_sliced(_records(x01, dfeat), G, binned=(route == "binned"))
+    return G
+
+
+@pytest.mark.parametrize("case", CB_CASES)
+def test_codebook_scatter_routes_vs_float64(fo, case):
+    """The point-wise (fp32 global atomics), sliced (fp32 LDS atomics) and binned (fixed point, four replicas + the exact merge) codebook
+    scatters against the float64 sum, on a pre-filled G they must accumulate into; the fixed-point route twice: the same bits.  Hot rows
+    (up to 65536 hits on one row) are where a fixed-point scale that ignores the hit count wraps."""
+    x, d = _cb_case(case)
+    ref = fr.scatter_ref(x, d, CB_RES)
+    xd, dd = x.cuda(), d.cuda()
+    assert torch.equal(_records(xd, dd)[:, 5:7], dd)
+    prefill = torch.from_numpy(np.random.RandomState(1).randn(T_ROWS, 2).astype(np.float32))
+    want = prefill.double() + ref
+    M, stats = x.shape[0], fr.scatter_row_stats(x, d, CB_RES)
+    for route in CB_ROUTES:
+        G = _cb_route(fo, route, xd, dd, prefill.cuda())
+        fixed = route == "binned"
+        fr.assert_scatter_close(G, want, stats, fixed, prefill=prefill, quantum=fr.fixed_quantum(float(d.abs().max()), 4 * M), what=f"{case} {route}")
+        if fixed:
+            assert torch.equal(G, _cb_route(fo, route, xd, dd, prefill.cuda())), "fixed point: two runs, the same bits"
+            if case in ("cancel", "hotcancel"):
+                Gz = _cb_route(fo, route, xd, dd, torch.zeros(T_ROWS, 2, device="cuda"))
+                assert int((Gz != 0).sum()) == 0, "equal and opposite contributions cancel exactly in fixed point"
+    if case == "gmax_zero":
+        for route in CB_ROUTES:
+            assert torch.equal(_cb_route(fo, route, xd, dd, prefill.cuda()).cpu(), prefill), route
+
+
+def test_codebook_scatter_auto_route_and_tiny_binned_launches(fo, monkeypatch):
+    """codebook_scatter_sliced(binned=None) on both sides of fieldops.BINNED_MIN_POINTS with every point on one vertex (the binned route is
+    taken from 65536 points; NERFSIG_DETERMINISTIC=1 takes it at every size), and the binned route at M = 1, 2, 3, 5: fewer entries than
+    replicas, empty replicas at the merge."""
+    assert fo.BINNED_MIN_POINTS == 65536
+    p = torch.tensor([[1000 / 2048, 517 / 2048, 1301 / 2048]], dtype=torch.float32)
+    for M in (65535, 65536, 65537):
+        x, d = p.repeat(M, 1), torch.ones(M, 2)
+        d[::3] = 0.75
+        want = fr.scatter_ref(x, d, CB_RES)
+        G = _cb_route(fo, "auto", x.cuda(), d.cuda(), torch.zeros(T_ROWS, 2, device="cuda"))
+        fixed = M >= fo.BINNED_MIN_POINTS
+        fr.assert_scatter_close(G, want, fr.scatter_row_stats(x, d, CB_RES), fixed, quantum=fr.fixed_quantum(1.0, 4 * M), what=f"auto M={M}")
+    monkeypatch.setenv("NERFSIG_DETERMINISTIC", "1")
+    assert fo.binned_min_points() == 1
+    x, d = p.repeat(9000, 1), torch.full((9000, 2), -1.0)
+    G = _cb_route(fo, "auto", x.cuda(), d.cuda(), torch.zeros(T_ROWS, 2, device="cuda"))
+    fr.assert_scatter_close(G, fr.scatter_ref(x, d, CB_RES), fr.scatter_row_stats(x, d, CB_RES), True, quantum=fr.fixed_quantum(1.0, 4 * 9000), what="deterministic")
+    monkeypatch.delenv("NERFSIG_DETERMINISTIC")
+    rng = np.random.RandomState(4)
+    for M in (1, 2, 3, 5):
+        x = torch.from_numpy(rng.rand(M, 3).astype(np.float32))
+        d = torch.from_numpy(rng.randn(M, 2).astype(np.float32))
+        prefill = torch.full((T_ROWS, 2), 0.5)
+        G = _cb_route(fo, "binned", x.cuda(), d.cuda(), prefill.cuda())
+        fr.assert_scatter_close(G, 0.5 + fr.scatter_ref(x, d, CB_RES), fr.scatter_row_stats(x, d, CB_RES), True, prefill=prefill, quantum=fr.fixed_quantum(float(d.abs().max()), 4 * M),
+                             what=f"binned M={M}")
+        assert int((G != 0.5).sum()) <= 16 * M      # (8 corners x 2 features per point)
+
+
+@pytest.mark.parametrize("case", ["uniform", "vertex", "cell"])
+def test_planned_scatter_vs_float64(fo, tables, case):
+    """The headline's route (ScatterPlan + field_backward_planned: the MLP backward writes the queue, four replicas + the exact merge) against the
+    float64 sum of the feature gradients field_backward reports for the same points (the same kernel arithmetic), accumulated into a pre-filled G;
+    65536 points spread out, all on one vertex, or all in one cell.  Twice: the same bits.  (Exact cancellation in the owners and the merge:
+    test_codebook_scatter_routes_vs_float64's binned route, the same kernels.)"""
+    _, sp, cp = _params(tables)
+    packed = fo.pack_weights(sp, cp)
+    base_d, cb_d = tables[2], tables[3]
+    M = 65536
+    rng = np.random.RandomState(6)
+    if case == "uniform":
+        x01 = rng.rand(M, 3).astype(np.float32)
+    else:
+        p = np.array([0.37, 0.61, 0.19] if case == "cell" else [1000, 517, 1301], np.float32) / np.float32(1 if case == "cell" else 2048)
+        x01 = np.repeat(p[None], M, 0)
+    pts = torch.from_numpy(x01 * np.float32(2) - np.float32(1)).cuda()
+    dirs = torch.from_numpy(cf.unit_dirs(M, seed=8)).cuda()
+    gs, gc = torch.from_numpy(rng.randn(M).astype(np.float32)).cuda(), torch.from_numpy(rng.randn(M, 3).astype(np.float32)).cuda()
+    S = fo.codebook_presum(fo.select_tables(cb_d[:64], fo.message_bits(torch.from_numpy(cf.messages(32)[2]))))
+    s1, c1, _, masks = fo.field_forward(pts, dirs, 1.0, base_d, S, packed, want_masks=True)
+    dfeat = fo.field_backward(pts, 1.0, gs, gc, s1, c1, masks, packed, want_dfeat=True)
+    x, d = ((pts + 1.0) / 2.0).cpu(), dfeat.cpu()
+    prefill = torch.from_numpy(np.random.RandomState(1).randn(T_ROWS, 2).astype(np.float32))
+    got = []
+    for _ in range(2):
+        G = prefill.cuda()
+        fo.field_backward_planned(pts, 1.0, gs, gc, s1, c1, masks, packed, fo.ScatterPlan(pts, 1.0), G)
+        got.append(G)
+    assert torch.equal(got[0], got[1])
+    fr.assert_scatter_close(got[0], prefill.double() + fr.scatter_ref(x, d, CB_RES), fr.scatter_row_stats(x, d, CB_RES), True, prefill=prefill,
+                         quantum=fr.fixed_quantum(float(d.abs().max()), 4 * M), what=f"planned {case}")
+
+
+@pytest.mark.parametrize("bad", [float("nan"), float("inf"), -float("inf")])
+def test_codebook_scatter_routes_leave_a_non_finite_gradient_visible(fo, bad):
+    """One non-finite feature gradient among 65536: the float routes carry it into the rows it reaches; the fixed-point routes poison every
+    row with NaN (csrc/hashgrid.hip k_scatter_binned) -- either way GradScaler's inf check sees it."""
+    x, d = _cb_case("uniform")
+    d[1234, 1] = bad
+    xd, dd = x.cuda(), d.cuda()
+    rows, _, _ = fr.voxel_lookup(x[1234:1235], CB_RES)
+    for route in CB_ROUTES:
+        G = _cb_route(fo, route, xd, dd, torch.zeros(T_ROWS, 2, device="cuda"))
+        assert not bool(torch.isfinite(G).all()), route
+        if route == "binned":
+            assert bool(torch.isnan(G).all()), route
+        else:
+            assert not bool(torch.isfinite(G[rows[0].cuda(), 1]).any()), route
 
 
 def test_pipelined_training_launches_equal_the_plain_loops_bit_for_bit(fo, tables):

@@ -751,3 +751,133 @@ def test_parameter_ema_follows_torch_ema_inside_the_captured_step():
         torch_ema(want, [p.detach() for p in m.trainable()], k)
     for a, b in zip(eager.ema_shadow, want):
         assert torch.equal(a, b)
+
+
+# ---- the 16-level table-gradient scatters against the float64 sum (oracle.field_ref.scatter_ref) -------------------------------------------------------------
+T_ROWS = 1 << 19
+MERGE_LEVELS = 10              # csrc/hashgrid.hip kMergeLevels: levels whose runs of samples in one cell are pre-summed in fp32 (runs of <= 16 lanes)
+CHECK_LEVELS = (0, 9, 10, 15)  # float64 on a few levels: the coarsest, both sides of the merge boundary, the finest
+
+
+def _level_case(name, M=65536):
+    """(pts [M,3] in [-1,1], d_planes [16,M,2]) on the CPU: uniform points | one long ray of samples inside ONE level-0 cell (every lane row of the
+    merged levels a single run) | all samples on one vertex | all in one cell, gradients 1.0 / 0.75 / random sign."""
+    rng = np.random.RandomState(12)
+    if name == "uniform":
+        pts = rng.rand(M, 3).astype(np.float32) * 2 - 1
+        d = rng.randn(16, M, 2).astype(np.float32)
+    else:
+        if name == "ray":
+            t = (np.arange(M, dtype=np.float64) / M)[:, None]
+            pts = (np.array([-0.995, -0.99, -0.985]) + t * np.array([0.115, 0.1, 0.105])).astype(np.float32)    # x01 in [0.0025, 0.0625): level-0 cell 0
+        else:
+            p = np.array([0.0, 0.25, -0.5] if name == "vertex" else [0.123, -0.456, 0.789], np.float32)
+            pts = np.repeat(p[None], M, 0)
+        d = {"ray": np.ones((16, M, 2), np.float32), "vertex": np.full((16, M, 2), 0.75, np.float32),
+             "cell": rng.choice([-1.0, 1.0], (16, M, 2)).astype(np.float32)}[name]
+    return torch.from_numpy(np.ascontiguousarray(pts)), torch.from_numpy(d)
+
+
+def _levels_route(route, pts, dpl, G):
+    """pts, dpl on the device; G [16,T,2] (written: the level routes overwrite)."""
+    from nerf_signature_amd import _native as nv
+    M = pts.shape[0]
+    if route == "record":
+        scratch = torch.empty(int(nv.fn("hg_scatter_levels_scratch_bytes")(M)), dtype=torch.uint8, device="cuda")
+        nv.call("hg_scatter_levels", nv.ptr(pts), 1.0, nv.ptr(dpl), M, M, nv.ptr_array([G[l] for l in range(16)]), nv.ptr(scratch), nv.stream())
+    else:
+        plan = torch.empty(int(nv.fn("hg_levels_plan_bytes")(M)), dtype=torch.uint8, device="cuda")
+        nv.call("hg_levels_plan", nv.ptr(pts), M, None, 1.0, nv.ptr(plan), nv.stream())
+        nv.call("hg_levels_scatter", nv.ptr(pts), M, None, 1.0, nv.ptr(dpl), M, nv.ptr(plan), nv.ptr_array([G[l] for l in range(16)]), nv.stream())
+    return G
+
+
+def _level_bound_args(route, l, d, M):
+    """(quantum, run_sums) of level l: the record route's owners see each contribution (|c| <= |g|, 4 entries per point); the planned route's merged levels
+    see run sums of <= 16 samples (|c| <= 16 max|g|, <= 8 entries per point)."""
+    g = float(d[l].abs().max())
+    if route == "planned" and l < MERGE_LEVELS:
+        return fr.fixed_quantum(16 * g, 8 * M), 16
+    return fr.fixed_quantum(g, (8 if route == "planned" else 4) * M), 0
+
+
+@pytest.mark.parametrize("case", ["uniform", "ray", "vertex", "cell"])
+def test_level_scatters_vs_float64(case):
+    """hg_scatter_levels (the record route) and hg_levels_plan + hg_levels_scatter (the planned route, merged coarse runs) against the float64 sum on
+    levels 0, 9, 10, 15, into tables pre-filled with NaN: every row is overwritten (untouched rows with 0).  65536 samples: spread out, one long ray
+    inside a single level-0 cell (the merged-runs case: ~65536 hits on a row at level 0), or all on one point."""
+    pts, d = _level_case(case)
+    M = pts.shape[0]
+    x01 = (pts + 1.0) / 2.0
+    pd, dd = pts.cuda(), d.cuda()
+    want = {l: fr.scatter_ref(x01, d[l], fr.level_resolutions()[l]) for l in CHECK_LEVELS}
+    stats = {l: fr.scatter_row_stats(x01, d[l], fr.level_resolutions()[l]) for l in CHECK_LEVELS}
+    for route in ("record", "planned"):
+        G = _levels_route(route, pd, dd, torch.full((16, T_ROWS, 2), float("nan"), device="cuda"))
+        assert bool(torch.isfinite(G).all()), route
+        for l in CHECK_LEVELS:
+            quantum, run_sums = _level_bound_args(route, l, d, M)
+            fr.assert_scatter_close(G[l], want[l], stats[l], True, quantum=quantum, run_sums=run_sums, what=f"{case} {route} level {l}")
+        assert torch.equal(G, _levels_route(route, pd, dd, torch.empty_like(G))), f"{route}: two runs, the same bits"
+
+
+def test_level_scatters_poison_a_level_with_a_non_finite_gradient():
+    """One NaN / inf feature gradient at level 3: both level routes write NaN into every row of that level (GradScaler's inf check sees it) and leave the
+    other levels finite and exact."""
+    pts, d = _level_case("uniform", 4096)
+    x01 = (pts + 1.0) / 2.0
+    for bad in (float("nan"), float("inf")):
+        d[3, 77, 0] = bad
+        for route in ("record", "planned"):
+            G = _levels_route(route, pts.cuda(), d.cuda(), torch.zeros(16, T_ROWS, 2, device="cuda"))
+            assert bool(torch.isnan(G[3]).all()), (route, bad)
+            assert bool(torch.isfinite(G[torch.arange(16) != 3]).all()), (route, bad)
+            quantum, run_sums = _level_bound_args(route, 15, d, 4096)
+            res = fr.level_resolutions()[15]
+            fr.assert_scatter_close(G[15], fr.scatter_ref(x01, d[15], res), fr.scatter_row_stats(x01, d[15], res), True, quantum=quantum, run_sums=run_sums,
+                                    what=f"{route} level 15 beside a poisoned level")
+
+
+@pytest.mark.parametrize("case", ["uniform", "ray"])
+def test_level_scatter_adam_vs_float64_sum_then_torch_adam(case):
+    """hg_levels_scatter_adam (the owners end with Adam's update of their rows) against the float64 sum rounded to fp32 and one step of torch.optim.Adam
+    (eps = 1e-15) on the same state.  The bound on the gradient (scatter_tolerance) carries through the update: exp_avg = (1 - beta1) g,
+    exp_avg_sq = (1 - beta2) g^2; the parameter moves by lr g / (|g| + eps) -- insensitive to g wherever its sign is certain, and by at most 2 lr elsewhere."""
+    from nerf_signature_amd import _native as nv
+    pts, d = _level_case(case)
+    M = pts.shape[0]
+    x01 = (pts + 1.0) / 2.0
+    lr, betas, eps = 1e-2, (0.9, 0.99), 1e-15
+    p0 = torch.from_numpy(np.random.RandomState(3).randn(16, T_ROWS, 2).astype(np.float32))
+    p, m, v = p0.cuda(), torch.zeros(16, T_ROWS, 2, device="cuda"), torch.zeros(16, T_ROWS, 2, device="cuda")
+    steps = [torch.zeros((), device="cuda") for _ in range(16)]
+    lr_dev, scratch = torch.tensor(lr, device="cuda"), torch.empty(64, device="cuda")
+    pd, dd = pts.cuda(), d.cuda()
+    plan = torch.empty(int(nv.fn("hg_levels_plan_bytes")(M)), dtype=torch.uint8, device="cuda")
+    nv.call("hg_levels_plan", nv.ptr(pd), M, None, 1.0, nv.ptr(plan), nv.stream())
+    nv.call("hg_levels_scatter_adam", nv.ptr(pd), M, None, 1.0, nv.ptr(dd), M, nv.ptr(plan), nv.ptr_array([p[l] for l in range(16)]),
+            nv.ptr_array([m[l] for l in range(16)]), nv.ptr_array([v[l] for l in range(16)]), nv.ptr_array(steps), nv.ptr(lr_dev),
+            betas[0], betas[1], eps, 1.0, nv.ptr(scratch), nv.stream())
+    torch.cuda.synchronize()
+    assert all(float(s) == 1.0 for s in steps)
+    for l in (0, 15):
+        res = fr.level_resolutions()[l]
+        g64 = fr.scatter_ref(x01, d[l], res)
+        quantum, run_sums = _level_bound_args("planned", l, d, M)
+        a = g64.abs()      # (+ torch's grad is the float64 sum rounded to fp32: u |g| more)
+        tol_g = fr.scatter_tolerance(g64, fr.scatter_row_stats(x01, d[l], res), True, quantum=quantum, run_sums=run_sums) + fr.U32 * a
+        q = p0[l].clone().requires_grad_(True)
+        q.grad = g64.float()
+        opt = torch.optim.Adam([q], lr=lr, betas=betas, eps=eps)
+        opt.step()
+        st = opt.state[q]
+        tol_m = (1 - betas[0]) * tol_g + 2 * fr.U32 * st["exp_avg"].double().abs()
+        tol_v = (1 - betas[1]) * (2 * a + tol_g) * tol_g + 4 * fr.U32 * st["exp_avg_sq"].double().abs() + 2.0 ** -149
+        sure = a > tol_g
+        # (sign certain: both updates are lr * (+-1) through ~10 fp32 roundings each -- the moments, sqrt, the bias corrections, the quotient, the
+        # step size -- plus the rounding of p - update)
+        tol_p = torch.where(sure, fr.U32 * (24 * lr + 2 * q.detach().double().abs()), 2 * lr * (1 + 4 * fr.U32) * torch.ones_like(a))
+        for name, got, ref, tol in (("exp_avg", m[l], st["exp_avg"], tol_m), ("exp_avg_sq", v[l], st["exp_avg_sq"], tol_v), ("param", p[l], q.detach(), tol_p)):
+            err = (got.double().cpu() - ref.double()).abs()
+            assert bool((err <= tol).all()), (case, l, name, float((err - tol).max()))
+        assert float(sure.double().mean()) > 0 and bool(((p[l].cpu() == p0[l]) | (g64 != 0)).all())      # rows without a gradient keep their parameters

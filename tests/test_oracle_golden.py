@@ -29,6 +29,32 @@ def test_g1_base_encoder_rows_bit_exact_and_features():
     np.testing.assert_array_equal(feats.numpy(), g["features"])
 
 
+def test_scatter_ref_equals_float64_autograd_of_the_lookup():
+    """oracle.field_ref.scatter_ref (the float64 table gradient the GPU scatter routes are held to) against float64 autograd of
+    trilerp(table[rows], w) at the codebook resolution and at all 16 base-level resolutions, on cf.points()' edge points (exact 0 and 1,
+    cell boundaries and their neighbours) plus points repeated on one row; gradients of mixed sign and scale."""
+    x = torch.from_numpy(cf.points())
+    x = torch.cat([x, x[4:10].repeat(5, 1)])                    # the same cell corners hit again (rows that accumulate)
+    rng = np.random.RandomState(5)
+    g = torch.from_numpy((rng.randn(x.shape[0], 2) * np.exp2(rng.randint(-20, 20, (x.shape[0], 1)))).astype(np.float32))
+    cb_res = fr.level_resolutions(64, 2048, 2048)[0]
+    assert float(cb_res) == 2048.0
+    for res in [cb_res] + fr.level_resolutions():
+        rows, w, _ = fr.voxel_lookup(x, res)
+        table = torch.zeros(1 << 19, 2, dtype=torch.float64, requires_grad=True)
+        (fr.trilerp(table[rows], w.double()) * g.double()).sum().backward()
+        got = fr.scatter_ref(x, g, res)
+        assert got.dtype == torch.float64 and got.shape == (1 << 19, 2)
+        assert torch.equal(got != 0, table.grad != 0), float(res)
+        # two float64 evaluations of the same products and sums (another association order): a few ulp of the row's sum of magnitudes
+        np.testing.assert_allclose(got.numpy(), table.grad.numpy(), rtol=1e-13, atol=1e-13 * float(table.grad.abs().max()))
+    # a non-finite gradient reaches its rows and only them
+    g[0, 0] = float("nan")
+    got = fr.scatter_ref(x, g, cb_res)
+    rows, _, _ = fr.voxel_lookup(x[:1], cb_res)
+    assert torch.isnan(got[rows[0], 0]).all() and int(torch.isnan(got).sum()) == 8
+
+
 def test_g2_codebook_forward_and_shared_gradient():
     g = _load("g2_codebook.npz")
     x = torch.from_numpy(cf.points())
