@@ -669,6 +669,22 @@ int hg_levels_scatter_adam(const float *xyzs, uint32_t M, const uint32_t *rows_d
                            float *const *steps_host, const float *lr, float beta1, float beta2, float eps, float grad_scale, float *scratch,
                            nsig_stream_t stream);
 
+/* ------------------------------------------------------------------ mesh extraction */
+
+/*
+ * Marching cubes over a dense fp32 lattice u[nx, ny, nz] (z fastest; nx, ny, nz >= 2, at most 2^28 nodes): replaces the reference's
+ * mcubes.marching_cubes in extract_geometry (nerf/utils.py:192-204).  A node is inside when u > threshold (NaN: outside); the table is
+ * csrc/mc_tables.h, generated by nerf_signature_amd/mc_table.py.  mc_count classifies every cell and writes the output sizes to
+ * totals (device, 2 words: vertices V, triangles T); the host reads them, sizes the outputs and calls mc_emit with the same lattice,
+ * threshold and scratch (mc_scratch_bytes, 16-byte aligned, need not be initialised; 0 = dimensions out of range).  mc_emit writes
+ * vertices [V, 3] (lattice space) and triangles [T, 3] (vertex ids) in a fixed order: vertices by owning node in C order, then by axis
+ * x, y, z (a node owns its +x, +y, +z edges); triangles by cell in C order, then in table order.  V = 0 (T = 0) launches nothing.
+ */
+size_t mc_scratch_bytes(uint32_t nx, uint32_t ny, uint32_t nz);
+int mc_count(const float *u, uint32_t nx, uint32_t ny, uint32_t nz, float threshold, void *scratch, uint32_t *totals, nsig_stream_t stream);
+int mc_emit(const float *u, uint32_t nx, uint32_t ny, uint32_t nz, float threshold, void *scratch, uint32_t n_vertices, uint32_t n_triangles,
+            float *vertices, int32_t *triangles, nsig_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
