@@ -685,6 +685,30 @@ int mc_count(const float *u, uint32_t nx, uint32_t ny, uint32_t nz, float thresh
 int mc_emit(const float *u, uint32_t nx, uint32_t ny, uint32_t nz, float threshold, void *scratch, uint32_t n_vertices, uint32_t n_triangles,
             float *vertices, int32_t *triangles, nsig_stream_t stream);
 
+/* ------------------------------------------------------------------ image metrics */
+
+/*
+ * PSNR and SSIM of rendered views without leaving the device (for this project's own evaluation: the reference's PSNRMeter / SSIMMeter,
+ * nerf/utils_wtmk_disen.py:211-282).  pred, truth: contiguous fp32 images, channel last.  Nothing is allocated, read back or synchronised;
+ * no atomics: the same inputs give the same bits.
+ *
+ * im_range_sse: B images of n values each.  extrema (device, 4 floats): min and max of pred, min and max of truth over the whole batch;
+ * sse (device, B doubles): per image sum (double)(float(p - t))^2, partial sums added in a fixed order.  Two launches.  scratch:
+ * im_range_scratch_bytes(B, n), 16-byte aligned, need not be initialised (0 = out of range: B in 1 .. 65535, n >= 1).
+ *
+ * im_ssim: torchmetrics' structural_similarity_index_measure with its defaults (11 x 11 Gaussian window, sigma 1.5, k1 0.01, k2 0.03) over
+ * [B, H, W, C], 1 <= C <= 4, 11 <= H, W <= 32768: ssim (device, B doubles) the per-image mean over the C (H-10) (W-10) windows that lie inside
+ * the image (what survives torchmetrics' crop; its reflect padding never reaches the result).  The data range is
+ * max(extrema[1] - extrema[0], extrema[3] - extrema[2]) read on the device when extrema (im_range_sse's) is given, else data_range (>= 0).
+ * map: NULL or [B, H-10, W-10, C] fp32, the per-window values.  A data range of 0 or non-finite pixels give non-finite results; the kernels
+ * finish normally.  Two launches.  scratch: im_ssim_scratch_bytes(B, H, W, C), 16-byte aligned (0 = out of range).
+ */
+size_t im_range_scratch_bytes(uint32_t B, uint64_t n);
+int im_range_sse(const float *pred, const float *truth, uint32_t B, uint64_t n, void *scratch, float *extrema, double *sse, nsig_stream_t stream);
+size_t im_ssim_scratch_bytes(uint32_t B, uint32_t H, uint32_t W, uint32_t C);
+int im_ssim(const float *pred, const float *truth, uint32_t B, uint32_t H, uint32_t W, uint32_t C, const float *extrema, float data_range,
+            void *scratch, double *ssim, float *map, nsig_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

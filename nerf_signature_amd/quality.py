@@ -9,7 +9,7 @@ block render -> decoder -> BIT_ACC) and `test_image` (:816-933: staged full view
                          the reference's Trainer shape gets ("eager"), with the block rays declared constant ("fixed"), or through a
                          world-size-1 RCCL group with every collective of the multi-rank step issued and the codebook optimiser in its
                          sharded form ("rccl1"); every mode draws the same content batches (rg_sample_rays) and the same messages
-  test_bitacc / test_image   the two evaluation loops
+  test_bitacc / test_image   the two evaluation loops; test_image_metrics: test_image with PSNR and SSIM taken on the device
 
 Used by tests/test_gpu_convergence.py, bench.py's `quality` block and tools/converge.py."""
 import time
@@ -19,6 +19,7 @@ import torch
 
 from . import blocks, rays, synthetic, trainer
 from .distortion import DistortionLayer
+from .metrics import ImageMetrics
 from .trainer import BIT_ACC, PSNRMeter
 
 README = dict(iters=1000, lambda_w=0.005, lambda_i=1.0, lr=1e-2)       # README.md:45 + main_nerf_wtmk.py:21
@@ -191,23 +192,41 @@ def test_bitacc(stage, n_messages=200, seed=4321, distortion="none"):
 test_bitacc.__test__ = False
 
 
-@torch.no_grad()
-def test_image(stage, seed=9876, max_ray_batch=4096):
-    """Trainer.test_image (:816-933): per test view a random message, eval_step(render_whole=True) -- the full view staged in
-    max_ray_batch chunks -- against the clean view; PSNRMeter over the views.  Returns the mean PSNR in dB."""
+def test_views(stage, seed=9876, max_ray_batch=4096):
+    """Trainer.test_image's loop (:816-933) as a generator of (pred, truth) [1, H, W, 3]: per test view a random message and
+    eval_step(render_whole=True) -- the full view staged in max_ray_batch chunks -- beside the clean view."""
     model, D, dev, H, W = stage["model"], stage["D"], stage["device"], stage["H"], stage["W"]
-    meter = PSNRMeter()
     gen = torch.Generator(device="cpu").manual_seed(seed)
     for b in range(stage["test_poses"].shape[0]):
-        message = torch.randint(0, 2, (D,), generator=gen).float().to(dev)
-        r = rays.get_rays(stage["test_poses"][b:b + 1], stage["intr"], H, W, -1)
-        data = {"rays_o": r["rays_o"], "rays_d": r["rays_d"], "images": stage["clean_test"][b:b + 1], "H": H, "W": W}
-        pred, _, gt, _, _, _, _ = trainer.eval_step(model, data, message, dict(stage["render_kwargs"], max_ray_batch=max_ray_batch), render_whole=True)
+        with torch.no_grad():
+            message = torch.randint(0, 2, (D,), generator=gen).float().to(dev)
+            r = rays.get_rays(stage["test_poses"][b:b + 1], stage["intr"], H, W, -1)
+            data = {"rays_o": r["rays_o"], "rays_d": r["rays_d"], "images": stage["clean_test"][b:b + 1], "H": H, "W": W}
+            pred, _, gt, _, _, _, _ = trainer.eval_step(model, data, message, dict(stage["render_kwargs"], max_ray_batch=max_ray_batch), render_whole=True)
+        yield pred, gt
+
+
+def test_image(stage, seed=9876, max_ray_batch=4096):
+    """Trainer.test_image (:816-933): the views of `test_views` against the clean views; PSNRMeter over the views.  Returns the mean PSNR in dB."""
+    meter = PSNRMeter()
+    for pred, gt in test_views(stage, seed, max_ray_batch):
         meter.update(pred, gt)
     return float(meter.measure())
 
 
-test_image.__test__ = False
+def test_image_metrics(stage, seed=9876, max_ray_batch=4096, views=None, psnr_meter=None):
+    """The same loop with PSNR and SSIM taken on the device (metrics.ImageMetrics) and one host read at the end -> {"psnr_db", "ssim"}, each the mean
+    over the views.  views: (pred, truth) pairs to measure instead of rendering `test_views`; psnr_meter: a PSNRMeter fed the same views (its host copies)."""
+    meter = ImageMetrics(stage["device"])
+    for pred, gt in (test_views(stage, seed, max_ray_batch) if views is None else views):
+        meter.update(pred, gt)
+        if psnr_meter is not None:
+            psnr_meter.update(pred, gt)
+    m = meter.measure()
+    return {"psnr_db": m["psnr_db"], "ssim": m["ssim"]}
+
+
+test_views.__test__ = test_image.__test__ = test_image_metrics.__test__ = False
 
 
 LAST_STAGE = None      # (tools/converge.py's two-rank run compares the ranks' final models)
@@ -224,10 +243,12 @@ def run(mode="graphed", steps=None, scene="hotdog", n_messages=200, **train_kw):
     distorted = None
     if train_kw.get("distortion", "none") != "none":      # the reference's eval_step distorts the evaluated blocks too (utils_wtmk_disen.py:666)
         distorted = test_bitacc(stage, n_messages, distortion=train_kw["distortion"])[0]
-    psnr = test_image(stage)
+    host_psnr = PSNRMeter()        # the record's PSNR stays the reference meter's; SSIM comes from the same renders
+    ssim = test_image_metrics(stage, psnr_meter=host_psnr)["ssim"]
+    psnr = float(host_psnr.measure())
     torch.cuda.synchronize()
     sel = [c for c in rec["adam_steps"]]
-    return {"mode": mode, "steps": rec["steps"], "bit_acc": acc, "wrong_bits_mean": wrong_mean, "wrong_bits_worst_message": wrong_max, "psnr_db": psnr,
+    return {"mode": mode, "steps": rec["steps"], "bit_acc": acc, "wrong_bits_mean": wrong_mean, "wrong_bits_worst_message": wrong_max, "psnr_db": psnr, "ssim": ssim,
             **({} if distorted is None else {"bit_acc_distorted_blocks": distorted}),
             "wall_s": rec["wall_s"], "capture_s": rec["prepare_s"], "train_ms_per_step": rec["ms_per_step"], "eval_wall_s": time.perf_counter() - t0, "bit_acc_before_training": before,
             "n_messages": n_messages, "n_test_views": int(stage["test_poses"].shape[0]), "overflowed": rec["overflowed"], "recaptures": rec["recaptures"],

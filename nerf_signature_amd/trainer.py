@@ -16,6 +16,7 @@ import torch.nn.functional as F
 from . import _native as nv
 from . import fieldops as fo
 from . import dp
+from . import metrics
 from .capture import SegmentedCapture, warm_up
 from .dp import GradExchange, exchange_active, world_size
 from .distortion import DistortionLayer, host_uniform, scaled_width
@@ -455,6 +456,34 @@ class PSNRMeter:
 
     def report(self):
         return f"PSNR = {self.measure():.6f}"
+
+
+class SSIMMeter:
+    """The reference's SSIMMeter (utils_wtmk_disen.py:248-282) on this project's kernel: per update torchmetrics' structural similarity of
+    [B, H, W, C] views (metrics.ssim, restated in DESIGN.md section 15), averaged over the updates.  The sum stays on the device; measure()
+    reads it.  Pass an instance in the Trainer's `metrics=` in place of the reference's meter."""
+
+    def __init__(self, device=None):
+        self.V, self.N = 0, 0
+        self.device = device          # None: the inputs' own (GPU) device
+
+    def clear(self):
+        self.V, self.N = 0, 0
+
+    def update(self, preds, truths):
+        if self.device is not None:
+            preds, truths = preds.to(self.device), truths.to(self.device)
+        self.V = self.V + metrics.ssim(preds, truths)
+        self.N += 1
+
+    def measure(self):
+        return float(self.V / self.N)
+
+    def write(self, writer, global_step, prefix=""):
+        writer.add_scalar(os.path.join(prefix, "SSIM"), self.measure(), global_step)
+
+    def report(self):
+        return f"SSIM = {self.measure():.6f}"
 
 
 class GraphedWatermarkLoop:
