@@ -77,21 +77,17 @@ class BlockDecodeGraph:
     # ------------------------------------------------------------------ what must hold for the captured launches to be the eager ones
 
     def _record(self, model, rays_o, rays_d):
-        marched = getattr(model, "_marched", None)
-        if not marched:
+        rec = model.get_marched(*model._flatten_rays(rays_o, rays_d)[1:])
+        if rec is None or rec.fixed is None or rec.grid_key != model.grid_key():
             return None
-        _, o, d = model._flatten_rays(rays_o, rays_d)
-        rec = marched.get(model._rays_key(o, d))
-        if rec is None or rec.get("fixed") is None or rec["grid_key"] != model.grid_key():
-            return None
-        if rec["fixed"].key != fo.FixedPoints._tables_key(model.encoder.tables()):
+        if rec.fixed.key != fo.FixedPoints._tables_key(model.encoder.tables()):
             return None                                     # a base table moved: the eager route refreshes the kept planes in place
         return rec
 
     def _key(self, model, rays_o, rays_d, rec, fused, kw, sink):
         sp, cp = model.sigma_net.params, model.color_net.params
-        return (id(model), id(rays_o), id(rays_d), rays_o._version, rays_d._version, tuple(rays_o.shape), id(rec), id(rec["fixed"]), rec["xyzs"].data_ptr(),
-                rec["capacity"], rec["fixed"].planes.data_ptr(), tuple(p.data_ptr() for p in fused[1]), tuple(tuple(p.shape) for p in fused[1]),
+        return (id(model), id(rays_o), id(rays_d), rays_o._version, rays_d._version, tuple(rays_o.shape), id(rec), id(rec.fixed), rec.xyzs.data_ptr(),
+                rec.capacity, rec.fixed.planes.data_ptr(), tuple(p.data_ptr() for p in fused[1]), tuple(tuple(p.shape) for p in fused[1]),
                 tuple(bool(p.requires_grad) for p in fused[1]), float(fused[0]), sp.data_ptr(), sp._version, cp.data_ptr(), cp._version,
                 model._packed().data_ptr(), id(sink), sink.G.data_ptr(),
                 None if model._presum_cache is None else model._presum_cache[1].data_ptr(),
@@ -111,7 +107,7 @@ class BlockDecodeGraph:
         if not (torch.is_tensor(message) and rays_o.is_cuda and rays_o.dim() == 4 and model.training and torch.is_grad_enabled() and model.cuda_ray
                 and not torch.cuda.is_current_stream_capturing() and model.normalization is normalize_img and model.grad_sink is None
                 and getattr(model, "shared_gradient_step", False) and not getattr(model, "device_select", False)
-                and getattr(model, "point_capacity", None) is None):
+                and model.point_capacity is None):
             return None
         from .network import _data_parallel
         if _data_parallel():          # (more than one rank: DistributedDataParallel-style loops reduce autograd's own gradients)
@@ -287,14 +283,14 @@ class StepGraph(BlockDecodeGraph):
             self.forward_graph = self.backward_graph = None
             self.key = None              # (the capacity is part of the key: the caller's key is stale now; it is rebuilt at the next step)
         rec = model.march_ahead(self.c_o, self.c_d, dt_gamma, max_steps, capacity=self.capacity)
-        n = raymarching.padded_point_count(int(rec["counter"][0]))
+        n = raymarching.padded_point_count(int(rec.counter[0]))
         if n > self.capacity or self.key is None:
             if n > self.capacity:
                 self.overflows += 1
                 self.capacity = raymarching.padded_point_count(int(n * self.HEADROOM))
                 self.forward_graph = self.backward_graph = None
                 self.key = None
-            model._marched = {k: r for k, r in model._marched.items() if r is not rec}      # the eager route marches for itself
+            model.forget_marched(rec)      # the eager route marches for itself
             return False
         return True
 

@@ -8,6 +8,7 @@ frozen (network_wtmk_tcnn.py:90-95) and `get_params` exposes only the codebook a
 import torch
 
 from . import fieldops as fo
+from . import raymarching
 from . import tcnn_compat as tcnn
 from .hash_encoding import HashEmbedder
 from .hash_encoding_wtmk_bit import HashEmbedder as HashEmbedder_msg
@@ -211,18 +212,10 @@ class NeRFNetwork(NeRFRenderer):
 
     def _count_points(self, o, d, dt_gamma, max_steps):
         """Padded sample total of these rays through the current grid (one counting march, one host read)."""
-        from . import _native as nv
-        from . import raymarching
-        N, dev = o.shape[0], o.device
         nears, fars = raymarching.near_far_from_aabb(o, d, self.aabb_train, self.min_near)
-        counts = torch.empty(N, dtype=torch.int32, device=dev)
-        t_rec = torch.empty(N * int(max_steps), dtype=torch.float32, device=dev)
-        rays = torch.empty(N, 3, dtype=torch.int32, device=dev)
-        counter = torch.zeros(2, dtype=torch.int32, device=dev)
-        nv.call("rm_march_train_count", nv.ptr(o), nv.ptr(d), nv.ptr(self.density_bitfield), float(self.bound), float(dt_gamma), int(max_steps), N,
-                int(self.cascade), int(self.grid_size), nv.ptr(nears), nv.ptr(fars), None, nv.ptr(counts), nv.ptr(t_rec), nv.stream())
-        nv.call("rm_march_train_scan", nv.ptr(counts), N, nv.ptr(rays), nv.ptr(counter), nv.stream())
-        return raymarching.padded_point_count(int(counter[0]))
+        counter = torch.zeros(2, dtype=torch.int32, device=o.device)
+        raymarching.march_rays_train_device(o, d, self.bound, self.density_bitfield, self.cascade, self.grid_size, nears, fars, counter, None, dt_gamma, int(max_steps))
+        return raymarching.padded_point_count(int(counter[0]))      # (walk and offsets enqueued; no samples written)
 
     def fix_rays(self, rays_o, rays_d, dt_gamma=0, max_steps=1024):
         """Declare these ray tensors constant from step to step -- the watermark-block rays, one pair of tensors per dataset
@@ -239,26 +232,22 @@ class NeRFNetwork(NeRFRenderer):
         For the reference's own Trainer driving this model: one call after the dataset exists,
         `model.fix_rays(dataset.rays_o_block, dataset.rays_d_block, opt.dt_gamma, opt.max_steps)`, and train_step's block render
         (utils_wtmk_disen.py:590) takes this route."""
-        from . import raymarching
         _, o, d = self._flatten_rays(rays_o, rays_d)
-        N = o.shape[0]
-        loop_capacity = (getattr(self, "point_capacity", None) or {}).get(N)
-        marched = getattr(self, "_marched", None) or {}
-        known = next((r for r in marched.values() if r["ptrs"] == (o.data_ptr(), d.data_ptr(), N) and r.get("fixed") is not None), None)
-        capacity = loop_capacity if loop_capacity is not None else (known["capacity"] if known is not None else None)
+        loop_capacity = self.capacity_for(o.shape[0])
+        known = self.find_marched(o, d, fixed=True)
+        capacity = loop_capacity if loop_capacity is not None else (known.capacity if known is not None else None)
         if capacity is None:
             capacity = self._count_points(o, d, dt_gamma, max_steps)
         rec = self.march_ahead(rays_o, rays_d, dt_gamma, max_steps, capacity=capacity)
-        if loop_capacity is None and int(rec["counter"][0]) > capacity:       # self-sized and outgrown: new buffers (nothing captured holds them)
-            capacity = raymarching.padded_point_count(int(rec["counter"][0]))
+        if loop_capacity is None and int(rec.counter[0]) > capacity:       # self-sized and outgrown: new buffers (nothing captured holds them)
+            capacity = raymarching.padded_point_count(int(rec.counter[0]))
             rec = self.march_ahead(rays_o, rays_d, dt_gamma, max_steps, capacity=capacity)
-        if rec.get("fixed") is None:
-            rec["fixed"] = fo.FixedPoints(rec["xyzs"], self.bound, self.encoder.tables())
+        if rec.fixed is None:
+            rec.fixed = fo.FixedPoints(rec.xyzs, self.bound, self.encoder.tables())
         else:
-            rec["fixed"].refresh(rec["xyzs"], self.encoder.tables())
-        rec["fixed_args"] = (dt_gamma, max_steps)
-        rec["rays_ref"] = (rays_o, rays_d)      # the cache is keyed by address + version: keep the tensors alive, or a later allocation could take the address
-        rec["grid_key"] = self.grid_key()
+            rec.fixed.refresh(rec.xyzs, self.encoder.tables())
+        rec.fixed_args, rec.grid_key = (dt_gamma, max_steps), self.grid_key()
+        rec.rays_ref = (rays_o, rays_d)      # the cache is keyed by address + version: keep the tensors alive, or a later allocation could take the address
         return rec
 
     def density(self, x, message=None):

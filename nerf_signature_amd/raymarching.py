@@ -10,7 +10,9 @@ nerf/renderer_wtmk.py work unchanged.  Differences that are part of the contract
     allocated at their final padded size;
   * kernels run on torch's current stream; arguments are validated (device, dtype, contiguity).
 """
+import functools
 import os
+import weakref
 
 import torch
 from torch.autograd import Function
@@ -129,20 +131,88 @@ packbits = _packbits.apply
 
 # ----------------------------------------------------------------------------------------- training
 
-_SCAN_WRITE_MAX = None
-
-
+@functools.lru_cache(maxsize=None)
 def scan_write_max_rays():
-    """Largest ray count rm_march_train_scan_write takes (its N + 1 offsets live in LDS)."""
-    global _SCAN_WRITE_MAX
-    if _SCAN_WRITE_MAX is None:      # NERFSIG_MARCH_FUSED=0 | nf: the stand-alone scan + write launches (A/B measurements)
-        _SCAN_WRITE_MAX = 0 if os.environ.get("NERFSIG_MARCH_FUSED", "1") in ("0", "nf") else int(nv.fn("rm_march_train_scan_write_max_rays")())
-    return _SCAN_WRITE_MAX
+    """Largest ray count rm_march_train_scan_write takes (its N + 1 offsets live in LDS).  NERFSIG_MARCH_FUSED=0 | nf: 0 -- stand-alone scan + write (A/B measurements)."""
+    return 0 if os.environ.get("NERFSIG_MARCH_FUSED", "1") in ("0", "nf") else int(nv.fn("rm_march_train_scan_write_max_rays")())
 
 
 def fused_limits():
     """True: the training march computes near / far itself (rm_march_train_count_nf).  NERFSIG_MARCH_FUSED=0 | sw: a launch of its own."""
     return os.environ.get("NERFSIG_MARCH_FUSED", "1") not in ("0", "sw")
+
+
+class MarchRecord:
+    """What one training march of the flattened rays o, d [N, 3] left on the device.  xyzs / dirs / deltas [capacity rows], rays [N, 3],
+    nears / fars [N]: what a render reads.  counter [2] (total points, N), counts, t_rec, noises, max_steps: the march's own buffers, re-used
+    when the same tensors are marched again (NeRFRenderer.march_ahead).  ptrs / key: the ray tensors by address, and by address + version.
+    fixed, fixed_args, rays_ref, grid_key: set by NeRFNetwork.fix_rays for rays declared constant -- the kept part of their field pass
+    (fieldops.FixedPoints), the (dt_gamma, max_steps) to re-march them with, the tensors themselves and the grid they were marched through."""
+
+    def __init__(self, o, d, xyzs, dirs, deltas, rays, nears, fars, counter=None, counts=None, t_rec=None, max_steps=None):
+        self.ptrs, self.capacity, self.key = (o.data_ptr(), d.data_ptr(), o.shape[0]), xyzs.shape[0], None
+        self.xyzs, self.dirs, self.deltas, self.rays, self.nears, self.fars = xyzs, dirs, deltas, rays, nears, fars
+        self.counter, self.counts, self.t_rec, self.max_steps, self.noises = counter, counts, t_rec, max_steps, None
+        self.fixed = self.fixed_args = self.rays_ref = self.grid_key = self._made_for = None
+
+    @classmethod
+    def allocate(cls, o, d, capacity, max_steps):
+        N, i32, f32 = o.shape[0], dict(dtype=torch.int32, device=o.device), dict(dtype=torch.float32, device=o.device)
+        return cls(o, d, torch.empty(capacity, 3, **f32), torch.empty(capacity, 3, **f32), torch.empty(capacity, 2, **f32), torch.empty(N, 3, **i32),
+                   torch.empty(N, **f32), torch.empty(N, **f32), counter=torch.zeros(2, **i32), counts=torch.empty(N, **i32),
+                   t_rec=torch.empty(N * int(max_steps), **f32), max_steps=int(max_steps))
+
+    def matches(self, o, d, capacity=None):
+        """Marched from these two (flattened) tensors, by address -- and, if given, into buffers of this capacity."""
+        return self.ptrs == (o.data_ptr(), d.data_ptr(), o.shape[0]) and (capacity is None or self.capacity == capacity)
+
+    def made_for(self, rays_o, rays_d, *args):
+        """Remember the two tensor OBJECTS (weakly: the allocator reuses addresses), their versions and `args` (of the march; the grid's key)."""
+        self._made_for = (weakref.ref(rays_o), weakref.ref(rays_d), (rays_o._version, rays_d._version, rays_o.data_ptr(), rays_d.data_ptr()) + args)
+        return self
+
+    def valid_for(self, rays_o, rays_d, *args):
+        """Still the march of exactly these objects, unmodified, with the same `args` (see made_for)."""
+        ref_o, ref_d, stamp = self._made_for
+        return ref_o() is rays_o and ref_d() is rays_d and stamp == (rays_o._version, rays_d._version, rays_o.data_ptr(), rays_d.data_ptr()) + args
+
+
+def enqueue_train_walk(rays_o, rays_d, density_bitfield, geom, noises, nears, fars, counts, t_rec, limits=None):
+    """First half of the training march: every ray walks the occupancy grid and leaves its sample count in `counts` [N] and the samples'
+    parameters in `t_rec` [N * max_steps].  geom = (bound, dt_gamma, max_steps, C, H).  limits = (aabb, min_near): `nears` / `fars` [N] are OUTPUTS,
+    filled by the walk itself (rm_march_train_count_nf) or, where NERFSIG_MARCH_FUSED says so, by a near/far launch in front of it; None: by the caller."""
+    (bound, dt_gamma, max_steps, C, H), N = geom, rays_o.shape[0]
+    if limits is not None and fused_limits():
+        return nv.call("rm_march_train_count_nf", nv.ptr(rays_o), nv.ptr(rays_d), nv.ptr(_f32c(limits[0])), float(limits[1]), nv.ptr(density_bitfield), float(bound),
+                       float(dt_gamma), int(max_steps), N, int(C), int(H), nv.ptr(noises), nv.ptr(nears), nv.ptr(fars), nv.ptr(counts), nv.ptr(t_rec), nv.stream())
+    if limits is not None:
+        near_far_into(rays_o, rays_d, limits[0], limits[1], nears, fars)
+    nv.call("rm_march_train_count", nv.ptr(rays_o), nv.ptr(rays_d), nv.ptr(density_bitfield), float(bound), float(dt_gamma),
+            int(max_steps), N, int(C), int(H), nv.ptr(nears), nv.ptr(fars), nv.ptr(noises), nv.ptr(counts), nv.ptr(t_rec), nv.stream())
+
+
+def enqueue_train_offsets(counts, rays, counter):
+    """Prefix sum of the counts -> `rays` [N, 3] = (ray id, offset, count), `counter` [2] = (total points, N): for a caller that reads the total to size `out`."""
+    N = counts.shape[0]
+    if N > 16384:      # many rays (a staged full-image render): the two-launch scan of 4096-ray workgroups
+        sums = torch.empty(int(nv.fn("rm_march_train_scan_blocks")(N)), dtype=torch.int32, device=counts.device)
+        nv.call("rm_march_train_scan_wide", nv.ptr(counts), N, nv.ptr(rays), nv.ptr(counter), nv.ptr(sums), nv.stream())
+    else:
+        nv.call("rm_march_train_scan", nv.ptr(counts), N, nv.ptr(rays), nv.ptr(counter), nv.stream())
+
+
+def enqueue_train_samples(rays_o, rays_d, geom, noises, nears, t_rec, counts, rays, counter, out, offsets_done=False):
+    """Second half of the training march: the offsets (enqueue_train_offsets, unless offsets_done) and the samples of all rays, written into
+    out = (xyzs [M, 3], dirs [M, 3], deltas [M, 2]); rows past the total are zero, a ray that does not fit in M rows is dropped.  For ray counts whose
+    offsets fit in LDS the prefix sum rides in the write launch (rm_march_train_scan_write) instead of a single-workgroup launch of its own."""
+    (bound, dt_gamma, max_steps, C, H), N = geom, rays_o.shape[0]
+    head = (nv.ptr(rays_o), nv.ptr(rays_d), float(bound), float(dt_gamma), int(max_steps), N, int(C), int(H), out[0].shape[0], nv.ptr(nears), nv.ptr(noises), nv.ptr(t_rec))
+    tail = (nv.ptr(rays), nv.ptr(counter), *(nv.ptr(t) for t in out))
+    if not offsets_done and 1 <= N <= scan_write_max_rays():
+        return nv.call("rm_march_train_scan_write", *head, nv.ptr(counts), *tail, nv.stream())
+    if not offsets_done:
+        enqueue_train_offsets(counts, rays, counter)
+    nv.call("rm_march_train_write", *head, *tail, nv.stream())
 
 
 def march_rays_train_device(rays_o, rays_d, bound, density_bitfield, C, H, nears, fars, counter, noises, dt_gamma,
@@ -151,46 +221,21 @@ def march_rays_train_device(rays_o, rays_d, bound, density_bitfield, C, H, nears
 
     Returns (counts, t_rec, rays, write) where `write(M)` fills xyzs/dirs/deltas of M rows -- freshly allocated, or the
     tensors of `out` = (xyzs, dirs, deltas, rays) when given.  `counter` (int32[2]) receives (total points, N) on the device.
-    capacity: the row count is known up front (no host read of the total in between), so for ray counts whose offsets fit in LDS the
-    prefix sum rides in the write launch (rm_march_train_scan_write) instead of a single-workgroup launch of its own.
-    limits = (aabb, min_near): `nears` / `fars` are OUTPUTS, filled by the walk itself (rm_march_train_count_nf) instead of a
-    near_far_from_aabb launch in front of it."""
-    N = rays_o.shape[0]
-    dev = rays_o.device
+    capacity: the row count is known up front (no host read of the total in between), so the offsets are left to `write` (enqueue_train_samples).
+    limits = (aabb, min_near): `nears` / `fars` are OUTPUTS (enqueue_train_walk)."""
+    N, dev, geom = rays_o.shape[0], rays_o.device, (bound, dt_gamma, max_steps, C, H)
     counts = torch.empty(N, dtype=torch.int32, device=dev)
     t_rec = torch.empty(N * max_steps, dtype=torch.float32, device=dev)
     rays = torch.empty(N, 3, dtype=torch.int32, device=dev) if out is None else out[3]
-    s = nv.stream()
-    if limits is not None:
-        nv.call("rm_march_train_count_nf", nv.ptr(rays_o), nv.ptr(rays_d), nv.ptr(_f32c(limits[0])), float(limits[1]), nv.ptr(density_bitfield), float(bound),
-                float(dt_gamma), int(max_steps), N, int(C), int(H), nv.ptr(noises), nv.ptr(nears), nv.ptr(fars), nv.ptr(counts), nv.ptr(t_rec), s)
-    else:
-        nv.call("rm_march_train_count", nv.ptr(rays_o), nv.ptr(rays_d), nv.ptr(density_bitfield), float(bound), float(dt_gamma),
-                int(max_steps), N, int(C), int(H), nv.ptr(nears), nv.ptr(fars), nv.ptr(noises), nv.ptr(counts), nv.ptr(t_rec), s)
-    fused = capacity is not None and 1 <= N <= scan_write_max_rays()
-    if not fused and N > 16384:      # many rays (a staged full-image render): the two-launch scan of 4096-ray workgroups
-        sums = torch.empty(int(nv.fn("rm_march_train_scan_blocks")(N)), dtype=torch.int32, device=dev)
-        nv.call("rm_march_train_scan_wide", nv.ptr(counts), N, nv.ptr(rays), nv.ptr(counter), nv.ptr(sums), s)
-    elif not fused:
-        nv.call("rm_march_train_scan", nv.ptr(counts), N, nv.ptr(rays), nv.ptr(counter), s)
+    enqueue_train_walk(rays_o, rays_d, density_bitfield, geom, noises, nears, fars, counts, t_rec, limits)
+    if capacity is None:
+        enqueue_train_offsets(counts, rays, counter)
 
     def write(M):
-        if out is not None:
-            xyzs, dirs, deltas = out[:3]
-            if xyzs.shape[0] != M or rays.shape[0] != N:
-                raise ValueError(f"march buffers hold {xyzs.shape[0]} points / {rays.shape[0]} rays, the march needs {M} / {N}")
-        else:
-            xyzs = torch.empty(M, 3, dtype=torch.float32, device=dev)
-            dirs = torch.empty(M, 3, dtype=torch.float32, device=dev)
-            deltas = torch.empty(M, 2, dtype=torch.float32, device=dev)
-        if fused:
-            nv.call("rm_march_train_scan_write", nv.ptr(rays_o), nv.ptr(rays_d), float(bound), float(dt_gamma), int(max_steps), N, int(C), int(H), M,
-                    nv.ptr(nears), nv.ptr(noises), nv.ptr(t_rec), nv.ptr(counts), nv.ptr(rays), nv.ptr(counter), nv.ptr(xyzs), nv.ptr(dirs),
-                    nv.ptr(deltas), nv.stream())
-        else:
-            nv.call("rm_march_train_write", nv.ptr(rays_o), nv.ptr(rays_d), float(bound), float(dt_gamma), int(max_steps), N, int(C),
-                    int(H), M, nv.ptr(nears), nv.ptr(noises), nv.ptr(t_rec), nv.ptr(rays), nv.ptr(counter), nv.ptr(xyzs),
-                    nv.ptr(dirs), nv.ptr(deltas), nv.stream())
+        xyzs, dirs, deltas = out[:3] if out is not None else (torch.empty(M, k, dtype=torch.float32, device=dev) for k in (3, 3, 2))
+        if xyzs.shape[0] != M or rays.shape[0] != N:
+            raise ValueError(f"march buffers hold {xyzs.shape[0]} points / {rays.shape[0]} rays, the march needs {M} / {N}")
+        enqueue_train_samples(rays_o, rays_d, geom, noises, nears, t_rec, counts, rays, counter, (xyzs, dirs, deltas), offsets_done=capacity is None)
         return xyzs, dirs, deltas
 
     return counts, t_rec, rays, write

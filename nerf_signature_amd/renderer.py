@@ -146,6 +146,11 @@ class NeRFRenderer(nn.Module):
             self.mean_count = 0
             self.local_step = 0
         self._grid_epoch = 0      # bumped by everything that rewrites the occupancy grid (see grid_key)
+        # the training march's host state (plain attributes: none of it belongs in a state_dict)
+        self.point_capacity = None      # {ray count: sample rows} set by a captured loop: the no-host-sync march (capacity_for)
+        self._marched = {}              # _rays_key -> raymarching.MarchRecord of samples marched ahead of their render (march_ahead, fix_rays)
+        self._premarched = None         # the MarchRecord of premarch(), for the next render only
+        self._keep_rays, self._last_rays = False, None      # _render_staged_fused: leave the last march's ray table in _last_rays
 
     # mean_density / mean_count (renderer_wtmk.py:523,536): plain host numbers, as in the reference -- except behind a device-side refresh
     # (gridrefresh.DeviceGridRefresh), which leaves them in device memory: they are then read back when somebody asks, not every 16 steps.
@@ -304,7 +309,11 @@ class NeRFRenderer(nn.Module):
     def _rays_key(o, d):
         return (o.data_ptr(), o._version, d.data_ptr(), d._version, o.shape[0])
 
-    def march_ahead(self, rays_o, rays_d, dt_gamma=0, max_steps=1024, perturb=False, phase="all", capacity=None, noises=None):
+    def capacity_for(self, n_rays):
+        """Sample rows a captured loop has reserved for renders of this many rays (`point_capacity`), or None."""
+        return self.point_capacity.get(n_rays) if self.point_capacity else None
+
+    def march_ahead(self, rays_o, rays_d, dt_gamma=0, max_steps=1024, perturb=False, capacity=None, noises=None):
         """March the training samples of these rays now, for a render issued later with the same (unmodified) ray tensors.
 
         The march needs the rays and the occupancy grid only -- nothing a training step updates -- so a loop that knows its next
@@ -312,55 +321,44 @@ class NeRFRenderer(nn.Module):
         the next one.  Needs `point_capacity` (the no-host-sync march); a repeated call for the same tensors re-marches into the
         same buffers.  run_cuda picks the samples up by the tensors' addresses and versions; any in-place change of the rays after
         the call makes it march again as usual.  noises: the per-ray start offsets [N] drawn by the caller (instead of torch.rand under perturb=True:
-        a captured loop that keeps its own counter-based draws, stage1.GraphedCleanLoop).
-
-        phase: "all", or the two halves separately -- "count" (near/far and the occupancy walk: writes only per-ray counts and the
-        sampled parameters, scratch nobody else reads) and "write" (prefix sum + the sample buffers, which overwrite what the current
-        step's backward still reads).  A loop may therefore run "count" while the current step is still in flight and "write" at its end."""
-        if not hasattr(self, "_marched"):
-            self._marched = {}
+        a captured loop that keeps its own counter-based draws, stage1.GraphedCleanLoop)."""
+        # (the walk while the current step is in flight and offsets + samples at its end, as two calls: measured, slower)
         prefix, o, d = self._flatten_rays(rays_o, rays_d)
         if capacity is None:      # (an explicit capacity: NeRFNetwork.fix_rays sizing its own buffers)
-            capacity = getattr(self, "point_capacity", None)
-            capacity = capacity.get(o.shape[0]) if capacity else None
+            capacity = self.capacity_for(o.shape[0])
         if capacity is None or not o.is_cuda:
             raise RuntimeError("march_ahead needs point_capacity for this ray count (see trainer.GraphedWatermarkLoop.prepare) and CUDA rays")
-        rec = next((r for r in self._marched.values() if r["ptrs"] == (o.data_ptr(), d.data_ptr(), o.shape[0]) and r["capacity"] == capacity), None)
-        if rec is None:
-            N, dev = o.shape[0], o.device
-            f32 = dict(dtype=torch.float32, device=dev)
-            rec = {"ptrs": (o.data_ptr(), d.data_ptr(), N), "capacity": capacity, "nears": torch.empty(N, **f32), "fars": torch.empty(N, **f32),
-                   "xyzs": torch.empty(capacity, 3, **f32), "dirs": torch.empty(capacity, 3, **f32), "deltas": torch.empty(capacity, 2, **f32),
-                   "rays": torch.empty(N, 3, dtype=torch.int32, device=dev), "counter": torch.zeros(2, dtype=torch.int32, device=dev), "key": None,
-                   "counts": torch.empty(N, dtype=torch.int32, device=dev), "t_rec": torch.empty(N * int(max_steps), **f32), "max_steps": int(max_steps),
-                   "noises": None}
-        if rec["max_steps"] != int(max_steps):
+        rec = self.find_marched(o, d, capacity) or raymarching.MarchRecord.allocate(o, d, capacity, max_steps)
+        if rec.max_steps != int(max_steps):
             raise ValueError("march_ahead: max_steps changed for rays that were marched before")
-        N = o.shape[0]
-        geom = (float(self.bound), float(dt_gamma), int(max_steps), N, int(self.cascade), int(self.grid_size))
-        if phase in ("all", "count") and not raymarching.fused_limits():
-            raymarching.near_far_into(o, d, self.aabb_train, self.min_near, rec["nears"], rec["fars"])
-            rec["noises"] = noises if noises is not None else (torch.rand(N, dtype=torch.float32, device=o.device) if perturb else None)
-            nv.call("rm_march_train_count", nv.ptr(o), nv.ptr(d), nv.ptr(self.density_bitfield), *geom, nv.ptr(rec["nears"]), nv.ptr(rec["fars"]),
-                    nv.ptr(rec["noises"]), nv.ptr(rec["counts"]), nv.ptr(rec["t_rec"]), nv.stream())
-        elif phase in ("all", "count"):       # the walk computes the rays' limits itself: no near/far launch in front of it
-            rec["noises"] = noises if noises is not None else (torch.rand(N, dtype=torch.float32, device=o.device) if perturb else None)
-            nv.call("rm_march_train_count_nf", nv.ptr(o), nv.ptr(d), nv.ptr(self.aabb_train), float(self.min_near), nv.ptr(self.density_bitfield), *geom,
-                    nv.ptr(rec["noises"]), nv.ptr(rec["nears"]), nv.ptr(rec["fars"]), nv.ptr(rec["counts"]), nv.ptr(rec["t_rec"]), nv.stream())
-        if phase in ("all", "write"):
-            if N <= raymarching.scan_write_max_rays():      # prefix sum inside the write launch (no single-workgroup launch between the two)
-                nv.call("rm_march_train_scan_write", nv.ptr(o), nv.ptr(d), geom[0], geom[1], geom[2], N, geom[4], geom[5], capacity, nv.ptr(rec["nears"]),
-                        nv.ptr(rec["noises"]), nv.ptr(rec["t_rec"]), nv.ptr(rec["counts"]), nv.ptr(rec["rays"]), nv.ptr(rec["counter"]), nv.ptr(rec["xyzs"]),
-                        nv.ptr(rec["dirs"]), nv.ptr(rec["deltas"]), nv.stream())
-            else:
-                nv.call("rm_march_train_scan", nv.ptr(rec["counts"]), N, nv.ptr(rec["rays"]), nv.ptr(rec["counter"]), nv.stream())
-                nv.call("rm_march_train_write", nv.ptr(o), nv.ptr(d), geom[0], geom[1], geom[2], N, geom[4], geom[5], capacity, nv.ptr(rec["nears"]),
-                        nv.ptr(rec["noises"]), nv.ptr(rec["t_rec"]), nv.ptr(rec["rays"]), nv.ptr(rec["counter"]), nv.ptr(rec["xyzs"]), nv.ptr(rec["dirs"]),
-                        nv.ptr(rec["deltas"]), nv.stream())
-        self._marched = {k: r for k, r in self._marched.items() if r is not rec}
-        rec["key"] = self._rays_key(o, d)
-        self._marched[rec["key"]] = rec
+        geom = (self.bound, dt_gamma, max_steps, self.cascade, self.grid_size)
+        rec.noises = noises if noises is not None else (torch.rand(o.shape[0], dtype=torch.float32, device=o.device) if perturb else None)
+        raymarching.enqueue_train_walk(o, d, self.density_bitfield, geom, rec.noises, rec.nears, rec.fars, rec.counts, rec.t_rec,
+                                       limits=(self.aabb_train, self.min_near))
+        raymarching.enqueue_train_samples(o, d, geom, rec.noises, rec.nears, rec.t_rec, rec.counts, rec.rays, rec.counter, (rec.xyzs, rec.dirs, rec.deltas))
+        self.keep_marched(rec, o, d)
         return rec
+
+    # the cache of marched samples: records keyed by their ray tensors' addresses and versions (_rays_key)
+    def find_marched(self, o, d, capacity=None, fixed=False):
+        """The record marched from these tensors whatever their versions (and of this capacity / with kept points, if asked), or None."""
+        return next((r for r in self._marched.values() if r.matches(o, d, capacity) and (r.fixed is not None or not fixed)), None)
+
+    def get_marched(self, o, d):
+        """The record of exactly these tensors, unmodified since their march, or None."""
+        return self._marched.get(self._rays_key(o, d)) if self._marched else None
+
+    def keep_marched(self, rec, o, d):
+        """(Re-)enter a record under the current versions of its tensors."""
+        self.forget_marched(rec)
+        rec.key = self._rays_key(o, d)
+        self._marched[rec.key] = rec
+
+    def forget_marched(self, rec):
+        self._marched = {k: r for k, r in self._marched.items() if r is not rec}
+
+    def marched_records(self):
+        return list(self._marched.values())
 
     def drop_marched(self):
         self._marched = {}
@@ -371,7 +369,6 @@ class NeRFRenderer(nn.Module):
         front of whatever the caller enqueues in between.  An eager step whose content rays are known before its block render (trainer.train_step)
         calls this first: the read-back then waits for the march alone instead of for the block render and the decoder queued in front of it.
         The samples are used once; anything that does not match (other tensors, an in-place change, another grid) marches again as usual."""
-        import weakref
         prefix, o, d = self._flatten_rays(rays_o, rays_d)
         nears, fars = raymarching.near_far_from_aabb(o, d, self.aabb_train, self.min_near)
         counter = self.step_counter[self.local_step % 16]
@@ -379,48 +376,34 @@ class NeRFRenderer(nn.Module):
         counter.zero_()
         xyzs, dirs, deltas, rays = raymarching.march_rays_train(o, d, self.bound, self.density_bitfield, self.cascade, self.grid_size, nears, fars, counter,
                                                                self.mean_count, False, 128, True, dt_gamma, max_steps)
-        self._premarched = (weakref.ref(rays_o), weakref.ref(rays_d), (rays_o._version, rays_d._version, rays_o.data_ptr(), rays_d.data_ptr()), float(dt_gamma),
-                            int(max_steps), self.grid_key(), {"xyzs": xyzs, "dirs": dirs, "deltas": deltas, "rays": rays, "nears": nears, "fars": fars})
-
-    def _take_premarched(self, rays_o, rays_d, dt_gamma, max_steps):
-        pre, self._premarched = getattr(self, "_premarched", None), None
-        if pre is None or pre[0]() is not rays_o or pre[1]() is not rays_d:
-            return None
-        if pre[2] != (rays_o._version, rays_d._version, rays_o.data_ptr(), rays_d.data_ptr()) or pre[3] != float(dt_gamma) or pre[4] != int(max_steps) or pre[5] != self.grid_key():
-            return None
-        return pre[6]
+        self._premarched = raymarching.MarchRecord(o, d, xyzs, dirs, deltas, rays, nears, fars).made_for(rays_o, rays_d, float(dt_gamma), int(max_steps), self.grid_key())
 
     def run_cuda(self, rays_o, rays_d, message, dt_gamma=0, bg_color=None, perturb=False, force_all_rays=False, max_steps=1024,
                  T_thresh=1e-4, **kwargs):
         bg_color = self._background(bg_color)
         prefix, o, d = self._flatten_rays(rays_o, rays_d)
-        marched = getattr(self, "_marched", None)
-        marched = marched.get(self._rays_key(o, d)) if marched and self.training and force_all_rays and not perturb else None
-        if marched is None and getattr(self, "_premarched", None) is not None:
-            pre = self._take_premarched(rays_o, rays_d, dt_gamma, max_steps)
-            if pre is not None and self.training and force_all_rays and not perturb and getattr(self, "point_capacity", None) is None:
+        plain = self.training and force_all_rays and not perturb      # (the render that march_ahead and premarch march for)
+        marched = self.get_marched(o, d) if plain else None
+        if marched is None and self._premarched is not None:
+            pre, self._premarched = self._premarched, None      # (for the next render only)
+            if plain and self.point_capacity is None and pre.valid_for(rays_o, rays_d, float(dt_gamma), int(max_steps), self.grid_key()):
                 marched = pre                                  # (marched a moment ago for exactly this call: premarch)
-        if marched is not None and marched.get("fixed") is not None and not torch.cuda.is_current_stream_capturing() and \
-                marched["grid_key"] != self.grid_key():
-            marched = self.fix_rays(o, d, *marched["fixed_args"])      # rays declared constant, but the grid they were marched through changed
-        capacity = getattr(self, "point_capacity", None)
-        capacity = capacity.get(o.shape[0]) if capacity else None
-        fused_limits = (marched is None and self.training and capacity is not None and force_all_rays and o.is_cuda and o.dtype == torch.float32
-                        and raymarching.fused_limits())
+        if marched is not None and marched.fixed is not None and not torch.cuda.is_current_stream_capturing() and marched.grid_key != self.grid_key():
+            marched = self.fix_rays(o, d, *marched.fixed_args)      # rays declared constant, but the grid they were marched through changed
+        march_limits = marched is None and self.training and self.capacity_for(o.shape[0]) is not None and force_all_rays and o.is_cuda and o.dtype == torch.float32
         if marched is not None:
-            nears, fars = marched["nears"], marched["fars"]
-        elif fused_limits:       # the capacity march (a captured step) fills them itself: rm_march_train_count_nf
+            nears, fars = marched.nears, marched.fars
+        elif march_limits:       # the capacity march (a captured step) fills them itself: raymarching.enqueue_train_walk
             nears, fars = torch.empty(o.shape[0], dtype=torch.float32, device=o.device), torch.empty(o.shape[0], dtype=torch.float32, device=o.device)
         else:
             nears, fars = raymarching.near_far_from_aabb(o, d, self.aabb_train if self.training else self.aabb_infer, self.min_near)
         if self.training:
             bg = _background_tensor(bg_color, o) if o.is_cuda else None
             out = self._march_and_composite_train(o, d, message, nears, fars, dt_gamma, perturb, force_all_rays, max_steps, T_thresh, finish=bg,
-                                                  marched=marched, limits=(self.aabb_train, self.min_near) if fused_limits else None)
-            if bg is not None:   # the tail was done by the compositing launch
-                weights_sum, depth, image = out
-                return {"depth": depth.view(*prefix), "image": image.view(*prefix, 3), "weights_sum": weights_sum}
+                                                  marched=marched, limits=(self.aabb_train, self.min_near) if march_limits else None)
             weights_sum, depth, image = out
+            if bg is not None:   # the tail was done by the compositing launch
+                return {"depth": depth.view(*prefix), "image": image.view(*prefix, 3), "weights_sum": weights_sum}
         else:
             weights_sum, depth, image = self._march_and_composite_eval(o, d, message, nears, fars, dt_gamma, perturb, max_steps, T_thresh)
         image, depth = self._finish(prefix, image, depth, weights_sum, bg_color, nears, fars)
@@ -433,32 +416,27 @@ class NeRFRenderer(nn.Module):
                                    marched=None, limits=None):
         """All samples of all rays at once, then one differentiable composite (renderer_wtmk.py:280-321)."""
         if marched is not None:      # the samples were marched ahead of this step (march_ahead)
-            fixed = marched.get("fixed")
-            if fixed is not None:    # rays declared constant (NeRFNetwork.fix_rays): base planes and scatter plan are kept beside the samples
-                sigmas, rgbs = self(marched["xyzs"], marched["dirs"], message, fixed=fixed)
-            else:
-                sigmas, rgbs = self(marched["xyzs"], marched["dirs"], message)
-            sigmas = sigmas if self.density_scale == 1 else self.density_scale * sigmas
-            if finish is not None:
-                return _CompositeFinish.apply(sigmas, rgbs, marched["deltas"], marched["rays"], nears, fars, finish, T_thresh)
-            return raymarching.composite_rays_train(sigmas, rgbs, marched["deltas"], marched["rays"], T_thresh)
+            return self._field_and_composite(marched.xyzs, marched.dirs, marched.deltas, marched.rays, message, nears, fars, finish, T_thresh, marched.fixed)
         counter = self.step_counter[self.local_step % 16]  # ring of the last 16 (points, rays) totals
         self.local_step += 1
-        capacity = getattr(self, "point_capacity", None)
-        capacity = capacity.get(o.shape[0]) if capacity else None
-        if not (capacity is not None and force_all_rays):
-            counter.zero_()   # (the capacity path's scan kernel writes both entries itself: one launch less in the captured step)
+        capacity = self.capacity_for(o.shape[0])
         if capacity is not None and force_all_rays:
-            # no host round trip: buffers sized by a known bound on the padded point count (see march_rays_train_capacity)
+            # no host round trip: buffers sized by a known bound on the padded point count (see march_rays_train_capacity); its scan kernel writes
+            # both entries of `counter` itself (no zero-fill: one launch less in the captured step)
             xyzs, dirs, deltas, rays = raymarching.march_rays_train_capacity(o, d, self.bound, self.density_bitfield, self.cascade,
                                                                             self.grid_size, nears, fars, counter, capacity, perturb,
                                                                             dt_gamma, max_steps, limits=limits)
         else:
+            counter.zero_()
             xyzs, dirs, deltas, rays = raymarching.march_rays_train(o, d, self.bound, self.density_bitfield, self.cascade, self.grid_size,
                                                                    nears, fars, counter, self.mean_count, perturb, 128, force_all_rays,
                                                                    dt_gamma, max_steps)
-        self._last_rays = rays if getattr(self, "_keep_rays", False) else None      # (render's fused staging reads the per-ray counts)
-        sigmas, rgbs = self(xyzs, dirs, message)
+        self._last_rays = rays if self._keep_rays else None      # (render's fused staging reads the per-ray counts)
+        return self._field_and_composite(xyzs, dirs, deltas, rays, message, nears, fars, finish, T_thresh)
+
+    def _field_and_composite(self, xyzs, dirs, deltas, rays, message, nears, fars, finish, T_thresh, fixed=None):
+        # fixed: rays declared constant (NeRFNetwork.fix_rays) -- base planes and scatter plan are kept beside the samples
+        sigmas, rgbs = self(xyzs, dirs, message) if fixed is None else self(xyzs, dirs, message, fixed=fixed)
         sigmas = sigmas if self.density_scale == 1 else self.density_scale * sigmas
         if finish is not None:
             return _CompositeFinish.apply(sigmas, rgbs, deltas, rays, nears, fars, finish, T_thresh)
@@ -698,7 +676,7 @@ class NeRFRenderer(nn.Module):
         B, N = rays_o.shape[:2]
         device = rays_o.device
         if (staged and self.cuda_ray and self.training and not torch.is_grad_enabled() and rays_o.is_cuda and N > max_ray_batch
-                and kwargs.get("force_all_rays", False) and not kwargs.get("perturb", False) and getattr(self, "point_capacity", None) is None
+                and kwargs.get("force_all_rays", False) and not kwargs.get("perturb", False) and self.point_capacity is None
                 and os.environ.get("NERFSIG_STAGED_FUSED", "1") != "0"):
             return self._render_staged_fused(rays_o, rays_d, message, max_ray_batch, **kwargs)
         if staged:
@@ -726,7 +704,7 @@ class NeRFRenderer(nn.Module):
         INTEGRATION.md section 5 otherwise asks the user to do with one call.  Identity is by object (weak references), never by address alone: the
         content rays are fresh tensors every step and the allocator reuses their addresses."""
         if not (self.cuda_ray and self.training and force_all_rays and not perturb and rays_o.is_cuda and torch.is_grad_enabled()
-                and getattr(self, "point_capacity", None) is None and hasattr(self, "fix_rays") and not torch.cuda.is_current_stream_capturing()):
+                and self.point_capacity is None and hasattr(self, "fix_rays") and not torch.cuda.is_current_stream_capturing()):
             return
         import weakref
         seen = self.__dict__.setdefault("_ray_sightings", {})

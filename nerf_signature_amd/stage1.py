@@ -412,8 +412,8 @@ class GraphedCleanLoop:
         if self.sampler is not None:
             self.sampler.sample_into(self.step_dev, self.rays_o, self.rays_d, self.gt)
         rec = self.rec = self._march()
-        rows = rec["counter"]                                     # [points, rays] int32: element 0 is the device row count
-        xyzs, dirs, M, N = rec["xyzs"], rec["dirs"], self.capacity, self.n_rays
+        rows = rec.counter                                     # [points, rays] int32: element 0 is the device row count
+        xyzs, dirs, M, N = rec.xyzs, rec.dirs, self.capacity, self.n_rays
         main = torch.cuda.current_stream()
         if self.plan_stream is not None:
             self.plan_stream.wait_stream(main)
@@ -432,17 +432,17 @@ class GraphedCleanLoop:
             # books (sample totals, loss ring, the next step's march offsets, the step count) remain clean_loss's, behind it on the same stream -- two launches in a
             # row instead of three (same box: dense -1.7 %, sparse grid -1.3 %; with clean_loss beside the MLP backward on the plan's stream the extra fork / join of
             # the graph cost more than the launch saved: +3 %)
-            nv.call("rm_composite_train_mse", nv.ptr(tr.sig), nv.ptr(tr.rgb), nv.ptr(rec["deltas"]), nv.ptr(rec["rays"]), M, N, self.T_thresh, nv.ptr(rec["nears"]),
-                    nv.ptr(rec["fars"]), nv.ptr(self.bg), 0, nv.ptr(self.gt), 3 * N, 1.0 / dp.world_size(), nv.ptr(self.ws), nv.ptr(self.depth), nv.ptr(self.image),
+            nv.call("rm_composite_train_mse", nv.ptr(tr.sig), nv.ptr(tr.rgb), nv.ptr(rec.deltas), nv.ptr(rec.rays), M, N, self.T_thresh, nv.ptr(rec.nears),
+                    nv.ptr(rec.fars), nv.ptr(self.bg), 0, nv.ptr(self.gt), 3 * N, 1.0 / dp.world_size(), nv.ptr(self.ws), nv.ptr(self.depth), nv.ptr(self.image),
                     nv.ptr(self.image_out), nv.ptr(self.depth_out), nv.ptr(self.g_image), nv.ptr(self.g_sig), nv.ptr(self.g_rgb), s)
             nv.call("clean_loss", nv.ptr(self.image_out), nv.ptr(self.gt), 3 * N, 1.0 / dp.world_size(), nv.ptr(self.loss), nv.ptr(self._g_image_books), *books, s)
         else:
-            nv.call("rm_composite_train_finish_fwd", nv.ptr(tr.sig), nv.ptr(tr.rgb), nv.ptr(rec["deltas"]), nv.ptr(rec["rays"]), M, N, self.T_thresh,
-                    nv.ptr(rec["nears"]), nv.ptr(rec["fars"]), nv.ptr(self.bg), 0, nv.ptr(self.ws), nv.ptr(self.depth), nv.ptr(self.image),
+            nv.call("rm_composite_train_finish_fwd", nv.ptr(tr.sig), nv.ptr(tr.rgb), nv.ptr(rec.deltas), nv.ptr(rec.rays), M, N, self.T_thresh,
+                    nv.ptr(rec.nears), nv.ptr(rec.fars), nv.ptr(self.bg), 0, nv.ptr(self.ws), nv.ptr(self.depth), nv.ptr(self.image),
                     nv.ptr(self.image_out), nv.ptr(self.depth_out), s)
             # the loss of the global batch is the mean over the ranks' losses: each rank seeds 1 / world, the exchange sums
             nv.call("clean_loss", nv.ptr(self.image_out), nv.ptr(self.gt), 3 * N, 1.0 / dp.world_size(), nv.ptr(self.loss), nv.ptr(self.g_image), *books, s)
-            nv.call("rm_composite_train_finish_bwd", None, nv.ptr(self.g_image), nv.ptr(tr.sig), nv.ptr(tr.rgb), nv.ptr(rec["deltas"]), nv.ptr(rec["rays"]),
+            nv.call("rm_composite_train_finish_bwd", None, nv.ptr(self.g_image), nv.ptr(tr.sig), nv.ptr(tr.rgb), nv.ptr(rec.deltas), nv.ptr(rec.rays),
                     nv.ptr(self.ws), nv.ptr(self.image), nv.ptr(self.bg), 0, M, N, self.T_thresh, 1, nv.ptr(self.g_sig), nv.ptr(self.g_rgb), s)
         # two-launch route: the weight gradients (a streaming reduction) run beside the table scatter (store- and LDS-bound) on the plan's stream,
         # which has long finished the plan by then (stream order: plan, then the weight gradients); fused: they are done when the backward is
@@ -572,8 +572,7 @@ class GraphedCleanLoop:
         m = self.model
         if self.sampler is not None:
             self.sampler.sample_into(self.step_dev, self.rays_o, self.rays_d, self.gt)
-        probe = m.march_ahead(self.rays_o, self.rays_d, self.dt_gamma, self.max_steps, perturb=False, capacity=128)
-        n = int(probe["counter"][0])
+        n = int(m.march_ahead(self.rays_o, self.rays_d, self.dt_gamma, self.max_steps, perturb=False, capacity=128).counter[0])
         m.drop_marched()
         return padded_point_count(int(max(n, 4096) * (1.0 + self.headroom)))
 

@@ -160,8 +160,8 @@ def train_step(model, data, message, render_kwargs, lambda_w=1.0, lambda_i=1.0, 
     graphed = None
     eager_caller = block_graph is not None and main is None and shard is None and not presum_adopt
     # the content render's march and its one host read, in front of the block render: the read then waits for the march alone (NeRFRenderer.premarch)
-    premarch = (eager_caller and content["rays_o"].is_cuda and model.training and torch.is_grad_enabled() and hasattr(model, "premarch") and getattr(model, "cuda_ray", False)
-                and getattr(model, "point_capacity", None) is None and not torch.cuda.is_current_stream_capturing())
+    premarch = (eager_caller and content["rays_o"].is_cuda and model.training and torch.is_grad_enabled() and hasattr(model, "premarch") and model.cuda_ray
+                and model.point_capacity is None and not torch.cuda.is_current_stream_capturing())
     if eager_caller and (distortion is None or isinstance(distortion, DistortionLayer)):
         whole = None
         if hasattr(block_graph, "usable_content") and content["images"].shape[-1] == 3:
@@ -533,7 +533,7 @@ class GraphedWatermarkLoop:
         # device, inside the captured graph, from the replay count; `data` / `next_data` then carry no content part
         self.content_sampler = content_sampler
         self._s_for = None            # host copy of the message the pre-sum buffer currently belongs to (None: unknown / stale)
-        self.marched = None
+        self.marched = None           # the block render's raymarching.MarchRecord (march-ahead, or the kept samples of fixed_blocks)
         self._pending_content = None
         self.side_stream = torch.cuda.Stream() if overlap_content else None
         self.plan_stream = self.side_stream   # scatter plans queue behind the content render
@@ -712,24 +712,19 @@ class GraphedWatermarkLoop:
         post()
         return None
 
-    def _march_ahead(self):
+    def _march_ahead(self):      # (never with fixed_blocks: those are marched once, outside the step -- _fix_blocks)
         kw, wm = self.render_kwargs, self.data["watermark"]
-        args = (kw.get("dt_gamma", 0), kw.get("max_steps", 1024))   # (march_ahead(..., phase="count" | "write") could split the walk from the writes: measured, slower)
         # the block render's march only: the content render's stays at the head of its step, on the side stream, where it
         # overlaps the pre-sum and the block encoder (both marches next to the optimiser took longer than the optimiser)
         block_o, block_d, _ = local_blocks(wm)       # (this rank's shard of the blocks when they are split over the ranks)
-        if self.fixed_blocks:                        # marched once, outside the step (_fix_blocks)
-            self.marched = self.marched[:1]
-        else:
-            self.marched = (self.model.march_ahead(block_o, block_d, *args),)
+        self.marched = self.model.march_ahead(block_o, block_d, kw.get("dt_gamma", 0), kw.get("max_steps", 1024))
 
     @torch.no_grad()
     def _fix_blocks(self):
         """(Re-)march this rank's block rays and (re-)compute what their field pass keeps across steps, in place (eager, between replays)."""
         kw = self.render_kwargs
         block_o, block_d, _ = local_blocks(self.data["watermark"])
-        rec = self.model.fix_rays(block_o, block_d, kw.get("dt_gamma", 0), kw.get("max_steps", 1024))
-        self.marched = (rec,) + tuple(self.marched[1:] if self.marched else ())
+        self.marched = self.model.fix_rays(block_o, block_d, kw.get("dt_gamma", 0), kw.get("max_steps", 1024))
         self._refix_pending = False
         self._kept_key = self._kept_inputs_key()
 
@@ -762,7 +757,7 @@ class GraphedWatermarkLoop:
     def point_counts(self):
         """(block, content) sample totals of the last step (one host read)."""
         if self.marched is not None:      # the block render has its own counter, the content render the ring's latest row
-            return int(self.marched[0]["counter"][0]), int(self.model.step_counter[self.capacity_rows[-1], 0])
+            return int(self.marched.counter[0]), int(self.model.step_counter[self.capacity_rows[-1], 0])
         a, b = self.model.step_counter[self.capacity_rows, 0].tolist()
         return (a, b) if self._blocks_issued_first() else (b, a)     # issue order: with a side stream the content render comes first
 
@@ -996,10 +991,7 @@ class GraphedWatermarkLoop:
 
     def overflowed(self):
         """True if the last replay produced more points than the buffers hold (one host read of two counters)."""
-        if self.marched is not None and len(self.marched) > 1:
-            return any(int(r["counter"][0]) > r["capacity"] for r in self.marched)
         if self.marched is not None:
-            return int(self.marched[0]["counter"][0]) > self.marched[0]["capacity"] or \
-                int(self.model.step_counter[self.capacity_rows[-1], 0]) > self.content_capacity
+            return int(self.marched.counter[0]) > self.marched.capacity or int(self.model.step_counter[self.capacity_rows[-1], 0]) > self.content_capacity
         totals = self.model.step_counter[self.capacity_rows, 0].tolist()
         return any(t > c for t, c in zip(totals, self.capacities))

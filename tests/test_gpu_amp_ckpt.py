@@ -300,7 +300,7 @@ def test_shared_gradient_step_under_a_foreign_loop_matches_plain_autograd_and_ad
     assert float((d0 - d1).norm() / d0.norm()) < 0.05
     assert all(e.weight.grad is None for e in m1.msg_encoder.embeddings)    # consumed by the fused pass
     # the block rays were seen twice: the kept-planes route is in use from the second step on (same renders bit for bit: tests/test_gpu_fixed.py)
-    assert any(r.get("fixed") is not None for r in getattr(m1, "_marched", {}).values()) and not getattr(m0, "_marched", None)
+    assert any(r.fixed is not None for r in m1.marched_records()) and not m0.marched_records()
     # an optimiser the fused pass does not implement (weight decay): the shared gradient dissolves into ordinary dense gradients, the step is torch's
     opt_w = torch.optim.Adam(m1.get_params(1e-2), betas=(0.9, 0.99), eps=1e-15, weight_decay=1e-4)
     opt_w.zero_grad()

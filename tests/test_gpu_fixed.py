@@ -35,8 +35,8 @@ def test_fixed_rays_render_is_bit_identical_and_follows_its_inputs():
     from nerf_signature_amd.raymarching import padded_point_count
     n_points = int(m.step_counter[(m.local_step - 1) % 16, 0])
     rec = m.fix_rays(bo, bd, dt_gamma=0, max_steps=1024)              # no point_capacity: sized by one counting march
-    assert int(rec["counter"][0]) == n_points and rec["capacity"] == padded_point_count(n_points) and rec["fixed"].refreshes == 1
-    assert getattr(m, "point_capacity", None) is None                  # other renders with as many rays are not capped by it
+    assert int(rec.counter[0]) == n_points and rec.capacity == padded_point_count(n_points) and rec.fixed.refreshes == 1
+    assert m.point_capacity is None                  # other renders with as many rays are not capped by it
     for msg, (img, depth, grad) in zip(msgs, want):
         got = render(msg)
         assert torch.equal(got[0], img) and torch.allclose(got[1], depth, rtol=0, atol=0, equal_nan=True)
@@ -45,15 +45,15 @@ def test_fixed_rays_render_is_bit_identical_and_follows_its_inputs():
         assert float((got[2] - grad).norm() / grad.norm()) < 1e-5
     with torch.no_grad():
         assert torch.equal(m.render(bo, bd, None, **KW)["image"], clean)           # no message: base planes only
-    assert rec["fixed"].refreshes == 1                                              # nothing was recomputed for any of this
+    assert rec.fixed.refreshes == 1                                              # nothing was recomputed for any of this
 
     # a base table changes (stage-1 weights loaded): noticed at the next render, planes refreshed in place
-    planes_ptr = rec["fixed"].planes.data_ptr()
+    planes_ptr = rec.fixed.planes.data_ptr()
     with torch.no_grad():
         m.encoder.embeddings[15].weight.mul_(0.5)
         want2 = m.render(bo.clone(), bd.clone(), msgs[0], **KW)["image"].clone()    # (fresh tensors: the ordinary path)
         got2 = m.render(bo, bd, msgs[0], **KW)["image"]
-    assert rec["fixed"].refreshes == 2 and rec["fixed"].planes.data_ptr() == planes_ptr
+    assert rec.fixed.refreshes == 2 and rec.fixed.planes.data_ptr() == planes_ptr
     assert torch.equal(got2, want2) and not torch.equal(got2, want[0][0])
 
     # the occupancy grid changes: re-marched and refreshed in place
@@ -65,16 +65,16 @@ def test_fixed_rays_render_is_bit_identical_and_follows_its_inputs():
         m.density_bitfield.copy_(raymarching.packbits(m.density_grid, 10.0))
         want3 = m.render(bo.clone(), bd.clone(), msgs[0], **KW)["image"].clone()
         got3 = m.render(bo, bd, msgs[0], **KW)["image"]
-    assert rec["fixed"].refreshes == 3 and torch.equal(got3, want3) and not torch.equal(got3, got2)
+    assert rec.fixed.refreshes == 3 and torch.equal(got3, want3) and not torch.equal(got3, got2)
     # ... and a grid with MORE occupied cells than the buffers were sized for: sized again (new buffers), nothing dropped
     with torch.no_grad():
         m.density_grid.fill_(100.0)
         m.density_bitfield.copy_(raymarching.packbits(m.density_grid, 10.0))
         want3b = m.render(bo.clone(), bd.clone(), msgs[0], **KW)["image"].clone()
         got3b = m.render(bo, bd, msgs[0], **KW)["image"]
-        rec = next(r for r in m._marched.values() if r.get("fixed") is not None)
-    assert rec["capacity"] > padded_point_count(n_points) and int(rec["counter"][0]) <= rec["capacity"] and torch.equal(got3b, want3b)
-    refreshes = rec["fixed"].refreshes
+        rec = next(r for r in m.marched_records() if r.fixed is not None)
+    assert rec.capacity > padded_point_count(n_points) and int(rec.counter[0]) <= rec.capacity and torch.equal(got3b, want3b)
+    refreshes = rec.fixed.refreshes
 
     # the model re-packs its own grid (update_extra_state -> packbits writes the bitfield IN PLACE through its raw pointer: neither the
     # address nor -- without mark_dirty -- the version would move): the explicit grid epoch and the dirty mark make the kept samples notice
@@ -87,22 +87,22 @@ def test_fixed_rays_render_is_bit_identical_and_follows_its_inputs():
         assert m.density_bitfield.data_ptr() == ptr_before and m.grid_key() != key_before and m.density_bitfield._version > version_before
         want3c = m.render(bo.clone(), bd.clone(), msgs[0], **KW)["image"].clone()
         got3c = m.render(bo, bd, msgs[0], **KW)["image"]
-        rec = next(r for r in m._marched.values() if r.get("fixed") is not None)
-    assert rec["fixed"].refreshes > refreshes and torch.equal(got3c, want3c) and not torch.equal(got3c, got3b)
-    refreshes = rec["fixed"].refreshes
+        rec = next(r for r in m.marched_records() if r.fixed is not None)
+    assert rec.fixed.refreshes > refreshes and torch.equal(got3c, want3c) and not torch.equal(got3c, got3b)
+    refreshes = rec.fixed.refreshes
 
     # the rays change in place: they drop out of the cache by themselves (matched by address AND version)
     with torch.no_grad():
         bd.copy_(torch.nn.functional.normalize(bd + 0.01, dim=-1))
         want4 = m.render(bo.clone(), bd.clone(), msgs[0], **KW)["image"].clone()
         got4 = m.render(bo, bd, msgs[0], **KW)["image"]
-    assert rec["fixed"].refreshes == refreshes and torch.equal(got4, want4)
+    assert rec.fixed.refreshes == refreshes and torch.equal(got4, want4)
 
 
 def test_fixed_block_cache_trains_like_the_loop_that_recomputes():
     """GraphedWatermarkLoop(fixed_blocks=True) against fixed_blocks=False: same messages, block rays replaced twice on the way
     (`data` at the step itself, `next_data` one step early), a checkpoint-style invalidate in between."""
-    from nerf_signature_amd import trainer
+    from nerf_signature_amd import raymarching, trainer
     from nerf_signature_amd.optim import CodebookAdam
 
     def make(seed):
@@ -138,9 +138,9 @@ def test_fixed_block_cache_trains_like_the_loop_that_recomputes():
         runs[fixed] = ([[float(v) for v in row] for row in held], torch.cat([e.weight.detach().reshape(-1) for e in m.msg_encoder.embeddings]),
                        loop.point_counts())
         if fixed:
-            rec = loop.marched[0]
-            assert rec["fixed"].refreshes == 4          # prepare, step 2 (data), step 4 (next_data of step 3), invalidate
-            assert len(loop.marched) == 1
+            rec = loop.marched
+            assert rec.fixed.refreshes == 4          # prepare, step 2 (data), step 4 (next_data of step 3), invalidate
+            assert isinstance(rec, raymarching.MarchRecord)          # one record (the block render's), not a tuple of them
     (l0, t0, n0), (l1, t1, n1) = runs[False], runs[True]
     assert n0 == n1
     np.testing.assert_allclose(l1, l0, rtol=1e-4, atol=1e-6)
@@ -189,7 +189,7 @@ def test_fixed_rays_under_autocast_and_a_scaled_loss():
     want_big, want_one = run(bo.clone(), bd.clone(), 65536.0), run(bo.clone(), bd.clone(), 1.0)
     rec = m.fix_rays(bo, bd, dt_gamma=0, max_steps=1024)
     got_big, got_one = run(bo, bd, 65536.0), run(bo, bd, 1.0)          # the large step first: its scale must not leak into the next
-    assert rec["fixed"].refreshes == 1
+    assert rec.fixed.refreshes == 1
     for got, want in ((got_big, want_big), (got_one, want_one)):
         assert got[0].dtype == want[0].dtype and torch.equal(got[0], want[0])
         assert bool(torch.isfinite(got[1]).all()) and float((got[1] - want[1]).norm() / want[1].norm()) < 1e-5
@@ -220,6 +220,6 @@ def test_fixed_blocks_loop_notices_a_base_table_written_between_replays():
         torch.cuda.synchronize()
         runs[fixed] = [[float(v) for v in row] for row in held]
         if fixed:
-            assert loop.marched[0]["fixed"].refreshes == 2
+            assert loop.marched.fixed.refreshes == 2
     np.testing.assert_allclose(runs[True], runs[False], rtol=1e-4, atol=1e-6)
     assert abs(runs[False][2][1] - runs[False][1][1]) > 1e-6

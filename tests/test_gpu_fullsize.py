@@ -191,12 +191,12 @@ def test_full_workload_block_render_with_kept_planes_is_bit_identical(workload):
     want = [render(bo.clone(), bd.clone(), msg) for msg in msgs]
     rec = m.fix_rays(bo, bd, dt_gamma=m.scene_cfg["dt_gamma"], max_steps=1024)
     try:
-        assert int(rec["counter"][0]) > 1_250_000
+        assert int(rec.counter[0]) > 1_250_000
         for msg, w in zip(msgs, want):
             got = render(bo, bd, msg)
             assert torch.equal(got[0], w[0]) and torch.equal(got[1], w[1]) and torch.allclose(got[2], w[2], rtol=0, atol=0, equal_nan=True)
             assert float((got[3] - w[3]).norm() / w[3].norm()) < 1e-6
-        assert rec["fixed"].refreshes == 1
+        assert rec.fixed.refreshes == 1
     finally:
         m.drop_marched()
 

@@ -274,12 +274,12 @@ def test_bench_size_step_properties():
         if full_grid:
             m.density_bitfield.fill_(255)
         rec = m.march_ahead(o, d, 0, 1024, perturb=False, capacity=128)       # a counting march first: the exact point total
-        n = int(rec["counter"][0])
+        n = int(rec.counter[0])
         m.drop_marched()
         from nerf_signature_amd.raymarching import padded_point_count
         rec = m.march_ahead(o, d, 0, 1024, perturb=False, capacity=padded_point_count(n))
-        assert int(rec["counter"][0]) == n and (n > 500_000 if full_grid else 100_000 < n < 200_000), n
-        pts, dirs = rec["xyzs"][:n].contiguous(), rec["dirs"][:n].contiguous()
+        assert int(rec.counter[0]) == n and (n > 500_000 if full_grid else 100_000 < n < 200_000), n
+        pts, dirs = rec.xyzs[:n].contiguous(), rec.dirs[:n].contiguous()
         rng = np.random.RandomState(3)
         gs = torch.from_numpy((rng.randn(n) * 1e-4).astype(np.float32)).cuda()
         gc = torch.from_numpy((rng.randn(n, 3) * 1e-4).astype(np.float32)).cuda()

@@ -36,5 +36,5 @@ for k in range(steps):
     loop._forward_backward()
     loop._optimise_and_march()
 torch.cuda.synchronize()
-n_block = int(loop.marched[0]["counter"][0])
-print(f"PMC_STEP_END points: block render {n_block} (rows per launch {loop.marched[0]['capacity']}), content render capacity {loop.content_capacity}", flush=True)
+n_block = int(loop.marched.counter[0])
+print(f"PMC_STEP_END points: block render {n_block} (rows per launch {loop.marched.capacity}), content render capacity {loop.content_capacity}", flush=True)
