@@ -196,6 +196,25 @@ int rg_sample_rays(const float *poses, uint32_t P, const float *images, float fx
                    uint32_t N, const int32_t *step_counter, uint32_t stride, uint32_t offset, uint64_t seed, float *rays_o, float *rays_d,
                    float *gt, int64_t *inds_out, int32_t *pose_out, nsig_stream_t stream);
 
+/* rg_sample_rays drawing from an error map (the reference's --error_map loader, nerf/utils.py:105-114 + nerf/provider.py:300-321): error_map [P, grid*grid]
+ * float32 holds one weight per cell of a grid x grid partition of every image (1 <= grid <= 128; the reference fixes 128); N cells (1 <= N <= grid*grid) of row
+ * p are drawn WITHOUT replacement with probability proportional to their weight, as torch.multinomial(replacement=False) draws them: the exponential race
+ * key(c) = w / -ln(u), u = (24 hash bits of (seed, step, c) + 1) / 2^24 in (0, 1], take the N largest keys.  A weight that is not finite or not > 0 has key 0.
+ * Equal keys go to the lower cell index; with fewer than N valid cells the lowest-index invalid ones fill the draw (torch raises; nothing inside a captured
+ * step may fault).  The drawn cells are written in ASCENDING cell order to inds_coarse_out (int64 [N]); ray n is a uniformly drawn pixel of cell n
+ * (row = min(H-1, (int)(cell / grid * H/grid + u1 * H/grid)), the column alike with W), with rays_o / rays_d / gt / inds_out / pose_out as rg_sample_rays writes
+ * them.  keys_out (float [grid*grid], or NULL): every cell's key.  One workgroup, no global atomics, bit-reproducible, no host value: capturable. */
+int rg_sample_rays_weighted(const float *poses, uint32_t P, const float *images, float fx, float fy, float cx, float cy, uint32_t H, uint32_t W,
+                            uint32_t N, const int32_t *step_counter, uint32_t stride, uint32_t offset, uint64_t seed, const float *error_map, uint32_t grid,
+                            float *rays_o, float *rays_d, float *gt, int64_t *inds_out, int32_t *pose_out, int64_t *inds_coarse_out, float *keys_out,
+                            nsig_stream_t stream);
+
+/* The map's update behind a step's loss (nerf/utils.py:534-556): error_map[*pose_dev][inds_coarse[n]] = 0.1 * old + 0.9 * e_n with
+ * e_n = mean over the 3 channels of (pred[n] - gt[n])^2; pred, gt [N,3]; pose_dev: the DEVICE word rg_sample_rays_weighted wrote.  The cells of one draw
+ * are distinct (plain stores); a non-finite e_n leaves its cell unchanged. */
+int rg_error_map_update(float *error_map, uint32_t P, uint32_t grid, const int32_t *pose_dev, const int64_t *inds_coarse, const float *pred, const float *gt,
+                        uint32_t N, nsig_stream_t stream);
+
 /* ------------------------------------------------------------------ hash grids */
 
 /* S[t] = sum_i tables[i][t] over the D selected codebook tables (the tables 2i+bit_i of

@@ -136,16 +136,18 @@ __device__ inline uint32_t mix32(uint32_t v) {   // a finaliser with full avalan
     return v;
 }
 
-__global__ void k_sample_rays(const float *__restrict__ poses, uint32_t P, const float *__restrict__ images, float fx, float fy, float cx, float cy,
-                              uint32_t H, uint32_t W, uint32_t N, const int32_t *__restrict__ step_counter, uint32_t stride, uint32_t offset,
-                              uint32_t seed_lo, uint32_t seed_hi, float *__restrict__ rays_o, float *__restrict__ rays_d, float *__restrict__ gt,
-                              int64_t *__restrict__ inds_out, int32_t *__restrict__ pose_out) {
-    const uint32_t n = blockIdx.x * blockDim.x + threadIdx.x;
-    if (n >= N) return;
-    const uint32_t step = step_counter ? (uint32_t)step_counter[0] : 0u;
-    const uint32_t p = (uint32_t)(((uint64_t)step * stride + offset) % P);
-    const uint32_t r = mix32(mix32(mix32(seed_lo ^ (step * 0x9e3779b9u)) + seed_hi) ^ (n * 0x85ebca6bu + 0x6b43a9b5u));
-    const uint32_t ind = (uint32_t)(((uint64_t)r * ((uint64_t)H * W)) >> 32);                  // uniform in [0, H*W)
+// The per-step prefix of every draw's counter hash: (seed, step) -> one word; a draw is mix32(word ^ f(index)).  `stream` separates the independent
+// sequences one step needs (0: the uniform sampler's pixel indices, as before; the weighted sampler's keys and sub-cell offsets take 1..3).
+__device__ inline uint32_t draw_base(uint32_t seed_lo, uint32_t seed_hi, uint32_t step, uint32_t stream) {
+    const uint32_t b = mix32(mix32(seed_lo ^ (step * 0x9e3779b9u)) + seed_hi);
+    return stream == 0u ? b : mix32(b + stream * 0x7f4a7c15u);
+}
+__device__ inline uint32_t draw_word(uint32_t base, uint32_t index) { return mix32(base ^ (index * 0x85ebca6bu + 0x6b43a9b5u)); }
+
+// Ray n of a drawn batch: pixel `ind` of pose p -- the ray arithmetic of k_get_rays, the stored pixel as ground truth.  Shared by both samplers.
+__device__ inline void write_sampled_ray(const float *__restrict__ poses, const float *__restrict__ images, float fx, float fy, float cx, float cy, uint32_t H,
+                                         uint32_t W, uint32_t p, uint32_t ind, uint32_t n, float *__restrict__ rays_o, float *__restrict__ rays_d,
+                                         float *__restrict__ gt, int64_t *__restrict__ inds_out) {
     const float i = (float)(ind % W) + 0.5f, j = (float)(ind / W) + 0.5f;                      // as k_get_rays
     const float x = (i - cx) / fx, y = (j - cy) / fy, z = 1.0f;
     const float nrm = sqrtf(x * x + y * y + z * z);
@@ -162,7 +164,170 @@ __global__ void k_sample_rays(const float *__restrict__ poses, uint32_t P, const
         gt[3 * (size_t)n] = px[0]; gt[3 * (size_t)n + 1] = px[1]; gt[3 * (size_t)n + 2] = px[2];
     }
     if (inds_out != nullptr) inds_out[n] = (int64_t)ind;
+}
+
+__global__ void k_sample_rays(const float *__restrict__ poses, uint32_t P, const float *__restrict__ images, float fx, float fy, float cx, float cy,
+                              uint32_t H, uint32_t W, uint32_t N, const int32_t *__restrict__ step_counter, uint32_t stride, uint32_t offset,
+                              uint32_t seed_lo, uint32_t seed_hi, float *__restrict__ rays_o, float *__restrict__ rays_d, float *__restrict__ gt,
+                              int64_t *__restrict__ inds_out, int32_t *__restrict__ pose_out) {
+    const uint32_t n = blockIdx.x * blockDim.x + threadIdx.x;
+    if (n >= N) return;
+    const uint32_t step = step_counter ? (uint32_t)step_counter[0] : 0u;
+    const uint32_t p = (uint32_t)(((uint64_t)step * stride + offset) % P);
+    const uint32_t r = draw_word(draw_base(seed_lo, seed_hi, step, 0u), n);
+    const uint32_t ind = (uint32_t)(((uint64_t)r * ((uint64_t)H * W)) >> 32);                  // uniform in [0, H*W)
+    write_sampled_ray(poses, images, fx, fy, cx, cy, H, W, p, ind, n, rays_o, rays_d, gt, inds_out);
     if (pose_out != nullptr && n == 0) pose_out[0] = (int32_t)p;
+}
+
+// The same batch drawn from pose p's error map (the reference's --error_map loader: nerf/utils.py:105-114 draws N of the map's G x G cells with
+// torch.multinomial(replacement=False), then a uniform pixel inside each cell).  multinomial without replacement is an exponential race -- key = w / Exp(1),
+// take the N largest -- and so is this: key(c) = w_c / -ln(u_c), u_c in (0, 1] from the counter hash of (seed, step, c).  The same distribution from another
+// generator, which is the stance k_sample_rays takes.  A weight that is not finite or not positive has key 0 and is drawn only when fewer than N cells are
+// valid (torch raises there; a captured step must not fault: the lowest-index invalid cells fill up).
+//
+// ONE workgroup of 1024 threads owns the draw; every thread keeps its (up to 16) keys in registers for the whole launch.  Cell c sits with wave c / (64 R),
+// register (c / 64) % R, lane c % 64 (R = ceil(G*G / 1024) registers per lane), so ascending c is (wave, register, lane) order and a wave's ballots rank its cells.
+//   select : non-negative floats order as their bit patterns -- radix select over the 32 key bits, 8 bits a pass, most significant first: the keys that
+//            still match the threshold's known prefix are counted into an LDS histogram (kHistCopies copies, one per lane mod 32: an all-ones map puts
+//            every key of a pass into one or two bins), a wave scans the 256 bins from the top -> threshold key T and the number of keys above it;
+//   compact: every key > T is drawn, and the first N - above keys == T in cell order (equal keys go to the lower cell); ballots rank the cells inside a
+//            wave, the waves' totals are summed through LDS: the drawn cells leave in ASCENDING cell order -- no global atomics, bit-reproducible;
+//   rays   : ray n belongs to drawn cell n: a uniform pixel of the cell (utils.py:108-112: the row is "x"), then write_sampled_ray.
+constexpr uint32_t kWeightedThreads = 1024, kWeightedWaves = kWeightedThreads / 64, kMaxErrorGrid = 128, kMaxKeysPerLane = kMaxErrorGrid * kMaxErrorGrid / kWeightedThreads;
+constexpr uint32_t kHistCopies = 32;
+
+__global__ __launch_bounds__(kWeightedThreads) void k_sample_rays_weighted(
+    const float *__restrict__ poses, uint32_t P, const float *__restrict__ images, float fx, float fy, float cx, float cy, uint32_t H, uint32_t W, uint32_t N,
+    const int32_t *__restrict__ step_counter, uint32_t stride, uint32_t offset, uint32_t seed_lo, uint32_t seed_hi, const float *__restrict__ error_map, uint32_t G,
+    float *__restrict__ rays_o, float *__restrict__ rays_d, float *__restrict__ gt, int64_t *__restrict__ inds_out, int32_t *__restrict__ pose_out,
+    int64_t *__restrict__ inds_coarse_out, float *__restrict__ keys_out) {
+    __shared__ uint32_t hist[256 * kHistCopies];                  // 32 KiB
+    __shared__ uint32_t drawn[kMaxErrorGrid * kMaxErrorGrid];     // 64 KiB: the drawn cells in ascending order
+    __shared__ uint32_t bins[256];
+    __shared__ uint32_t wave_tot[kWeightedWaves];
+    __shared__ uint32_t found[2];                                 // the pass's digit, the keys above it
+
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    const uint32_t step = step_counter ? (uint32_t)step_counter[0] : 0u;
+    const uint32_t p = (uint32_t)(((uint64_t)step * stride + offset) % P);
+    const uint32_t cells = G * G, R = ceil_div(cells, kWeightedThreads);
+    const uint32_t first = wave * 64u * R + lane;                 // this lane's cells: first + 64 i, i < R
+
+    // ---- keys
+    const float *w_row = error_map + (size_t)p * cells;
+    const uint32_t key_base = draw_base(seed_lo, seed_hi, step, 1u);
+    uint32_t key[kMaxKeysPerLane];
+#pragma unroll
+    for (uint32_t i = 0; i < kMaxKeysPerLane; ++i) {
+        const uint32_t c = first + 64u * i;
+        key[i] = 0u;
+        if (i < R && c < cells) {
+            const float w = w_row[c];
+            const float u = (float)((draw_word(key_base, c) >> 8) + 1u) * (1.0f / 16777216.0f);      // (0, 1]
+            const float k = (w > 0.0f && w <= FLT_MAX) ? w / (0.0f - logf(u)) : 0.0f;                // u == 1: w / +0 = +inf
+            key[i] = __float_as_uint(k);
+            if (keys_out != nullptr) keys_out[c] = k;
+        }
+    }
+
+    // ---- radix select: `prefix` = the threshold's bits above `shift`, `need` = how many of the keys matching it are still to be taken
+    uint32_t prefix = 0u, need = N;
+    for (int shift = 24; shift >= 0; shift -= 8) {
+        for (uint32_t b = tid; b < 256u * kHistCopies; b += kWeightedThreads) hist[b] = 0u;
+        __syncthreads();
+#pragma unroll
+        for (uint32_t i = 0; i < kMaxKeysPerLane; ++i) {
+            const uint32_t c = first + 64u * i;
+            if (i < R && c < cells && (shift == 24 || (key[i] >> (shift + 8)) == prefix))
+                atomicAdd(&hist[((key[i] >> shift) & 255u) * kHistCopies + (lane & (kHistCopies - 1u))], 1u);
+        }
+        __syncthreads();
+        if (tid < 256u) {
+            uint32_t s = 0u;
+            for (uint32_t j = 0; j < kHistCopies; ++j) s += hist[tid * kHistCopies + ((j + tid) & (kHistCopies - 1u))];
+            bins[tid] = s;
+        }
+        __syncthreads();
+        if (wave == 0u) {       // lane l owns bins 255 - 4 l ... 252 - 4 l: a scan from the top bin down
+            uint32_t cnt[4], mine = 0u;
+#pragma unroll
+            for (uint32_t j = 0; j < 4u; ++j) { cnt[j] = bins[255u - (4u * lane + j)]; mine += cnt[j]; }
+            uint32_t run = mine;
+#pragma unroll
+            for (uint32_t d = 1; d < 64u; d <<= 1) {
+                const uint32_t v = __shfl_up(run, d);
+                if (lane >= d) run += v;
+            }
+            run -= mine;        // keys in the bins above this lane's
+#pragma unroll
+            for (uint32_t j = 0; j < 4u; ++j) {
+                if (run < need && run + cnt[j] >= need) { found[0] = 255u - (4u * lane + j); found[1] = run; }
+                run += cnt[j];
+            }
+        }
+        __syncthreads();
+        prefix = (prefix << 8) | found[0];
+        need -= found[1];
+    }
+    // prefix = the threshold key T; N - need keys exceed it, and need >= 1 of the keys equal to it are drawn
+
+    // ---- compaction in cell order
+    uint32_t n_gt = 0u, n_eq = 0u;
+#pragma unroll
+    for (uint32_t i = 0; i < kMaxKeysPerLane; ++i) {
+        const uint32_t c = first + 64u * i;
+        const bool live = i < R && c < cells;
+        n_gt += (uint32_t)__popcll(__ballot(live && key[i] > prefix));
+        n_eq += (uint32_t)__popcll(__ballot(live && key[i] == prefix));
+    }
+    if (lane == 0u) wave_tot[wave] = (n_eq << 16) | n_gt;         // (both <= 16384 / 16 = 1024 per wave)
+    __syncthreads();
+    uint32_t gt_before = 0u, eq_before = 0u;
+    for (uint32_t w = 0; w < wave; ++w) { gt_before += wave_tot[w] & 0xffffu; eq_before += wave_tot[w] >> 16; }
+    const unsigned long long below = (1ull << lane) - 1ull;
+#pragma unroll
+    for (uint32_t i = 0; i < kMaxKeysPerLane; ++i) {
+        const uint32_t c = first + 64u * i;
+        const bool live = i < R && c < cells;
+        const bool gt_ = live && key[i] > prefix, eq_ = live && key[i] == prefix;
+        const unsigned long long m_gt = __ballot(gt_), m_eq = __ballot(eq_);
+        const uint32_t g = gt_before + (uint32_t)__popcll(m_gt & below), e = eq_before + (uint32_t)__popcll(m_eq & below);
+        if (gt_ || (eq_ && e < need)) {
+            const uint32_t pos = g + min(e, need);
+            if (pos < N) { drawn[pos] = c; inds_coarse_out[pos] = (int64_t)c; }      // (always true: N cells are drawn; a bound on the store all the same)
+        }
+        gt_before += (uint32_t)__popcll(m_gt);
+        eq_before += (uint32_t)__popcll(m_eq);
+    }
+    __syncthreads();
+
+    // ---- rays: a uniform pixel inside each drawn cell
+    const uint32_t row_base = draw_base(seed_lo, seed_hi, step, 2u), col_base = draw_base(seed_lo, seed_hi, step, 3u);
+    const float sx = (float)H / (float)G, sy = (float)W / (float)G;
+    for (uint32_t n = tid; n < N; n += kWeightedThreads) {
+        const uint32_t c = drawn[n];
+        const float u1 = (float)(draw_word(row_base, n) >> 8) * (1.0f / 16777216.0f), u2 = (float)(draw_word(col_base, n) >> 8) * (1.0f / 16777216.0f);   // [0, 1)
+        const uint32_t row = min(H - 1u, (uint32_t)((float)(c / G) * sx + u1 * sx)), col = min(W - 1u, (uint32_t)((float)(c % G) * sy + u2 * sy));
+        write_sampled_ray(poses, images, fx, fy, cx, cy, H, W, p, row * W + col, n, rays_o, rays_d, gt, inds_out);
+    }
+    if (pose_out != nullptr && tid == 0u) pose_out[0] = (int32_t)p;
+}
+
+// The map's update behind the step's loss (nerf/utils.py:534-556): cell <- 0.1 old + 0.9 error with error = the ray's squared error averaged over the three
+// channels.  The cells of one draw are distinct: plain stores.  A non-finite error leaves its cell alone (one NaN pixel would otherwise retire the cell for good).
+__global__ void k_error_map_update(float *__restrict__ error_map, uint32_t P, uint32_t cells, const int32_t *__restrict__ pose, const int64_t *__restrict__ inds_coarse,
+                                   const float *__restrict__ pred, const float *__restrict__ gt, uint32_t N) {
+    const uint32_t n = blockIdx.x * blockDim.x + threadIdx.x;
+    if (n >= N) return;
+    const uint32_t p = (uint32_t)pose[0];
+    const uint64_t c = (uint64_t)inds_coarse[n];
+    if (p >= P || c >= cells) return;
+    const float d0 = pred[3 * (size_t)n] - gt[3 * (size_t)n], d1 = pred[3 * (size_t)n + 1] - gt[3 * (size_t)n + 1], d2 = pred[3 * (size_t)n + 2] - gt[3 * (size_t)n + 2];
+    const float e = (d0 * d0 + d1 * d1 + d2 * d2) / 3.0f;
+    if (!(fabsf(e) <= FLT_MAX)) return;
+    float *cell = error_map + (size_t)p * cells + c;
+    *cell = 0.1f * *cell + 0.9f * e;
 }
 
 // ----------------------------------------------------------------------------- the occupancy walk
@@ -1464,6 +1629,31 @@ NSIG_EXPORT int rg_sample_rays(const float *poses, uint32_t P, const float *imag
     k_sample_rays<<<ceil_div(N, 256u), 256, 0, as_stream(stream)>>>(poses, P, images, fx, fy, cx, cy, H, W, N, step_counter, stride, offset, (uint32_t)seed,
                                                                     (uint32_t)(seed >> 32), rays_o, rays_d, gt, inds_out, pose_out);
     return check_launch("rg_sample_rays");
+}
+
+NSIG_EXPORT int rg_sample_rays_weighted(const float *poses, uint32_t P, const float *images, float fx, float fy, float cx, float cy, uint32_t H, uint32_t W,
+                                        uint32_t N, const int32_t *step_counter, uint32_t stride, uint32_t offset, uint64_t seed, const float *error_map, uint32_t grid,
+                                        float *rays_o, float *rays_d, float *gt, int64_t *inds_out, int32_t *pose_out, int64_t *inds_coarse_out, float *keys_out,
+                                        nsig_stream_t stream) {
+    NSIG_REQUIRE(poses && rays_o && rays_d && error_map && inds_coarse_out, "rg_sample_rays_weighted: null pointer");
+    NSIG_REQUIRE(P > 0 && H > 0 && W > 0 && fx != 0.0f && fy != 0.0f, "rg_sample_rays_weighted: empty pose store, bad image size or focal length");
+    NSIG_REQUIRE(gt == nullptr || images != nullptr, "rg_sample_rays_weighted: ground truth requested without an image store");
+    NSIG_REQUIRE((uint64_t)H * W < (1ull << 32), "rg_sample_rays_weighted: image too large");
+    NSIG_REQUIRE(grid >= 1 && grid <= kMaxErrorGrid, "rg_sample_rays_weighted: grid %u out of range (1..%u)", grid, kMaxErrorGrid);
+    NSIG_REQUIRE(N >= 1 && N <= grid * grid, "rg_sample_rays_weighted: N %u out of range (1..grid * grid = %u: a draw without replacement)", N, grid * grid);
+    k_sample_rays_weighted<<<1, kWeightedThreads, 0, as_stream(stream)>>>(poses, P, images, fx, fy, cx, cy, H, W, N, step_counter, stride, offset, (uint32_t)seed,
+                                                                          (uint32_t)(seed >> 32), error_map, grid, rays_o, rays_d, gt, inds_out, pose_out,
+                                                                          inds_coarse_out, keys_out);
+    return check_launch("rg_sample_rays_weighted");
+}
+
+NSIG_EXPORT int rg_error_map_update(float *error_map, uint32_t P, uint32_t grid, const int32_t *pose_dev, const int64_t *inds_coarse, const float *pred,
+                                    const float *gt, uint32_t N, nsig_stream_t stream) {
+    if (N == 0) return NSIG_OK;
+    NSIG_REQUIRE(error_map && pose_dev && inds_coarse && pred && gt, "rg_error_map_update: null pointer");
+    NSIG_REQUIRE(P > 0 && grid >= 1 && grid <= kMaxErrorGrid, "rg_error_map_update: empty map or grid %u out of range (1..%u)", grid, kMaxErrorGrid);
+    k_error_map_update<<<ceil_div(N, 256u), 256, 0, as_stream(stream)>>>(error_map, P, grid * grid, pose_dev, inds_coarse, pred, gt, N);
+    return check_launch("rg_error_map_update");
 }
 
 NSIG_EXPORT int rg_get_rays(const float *poses, float fx, float fy, float cx, float cy, uint32_t H, uint32_t W, const int64_t *inds,

@@ -61,25 +61,70 @@ class DeviceRaySampler:
     [P,H*W,3] resident in HBM; every call writes one batch -- pose (step * stride + offset) mod P, N uniformly drawn pixels, their rays
     and ground-truth colours -- into caller-owned buffers, with `step` read from a device counter.  Nothing in the call depends on a
     host value, so trainer.GraphedWatermarkLoop captures it at the head of its step (`content_sampler=`): the per-step hand-over of
-    rays costs one 5 us launch inside the graph instead of a randint, a ray kernel, a gather and three copies between two replays."""
+    rays costs one 5 us launch inside the graph instead of a randint, a ray kernel, a gather and three copies between two replays.
+    error_map=: the pixels are drawn from a per-image map of recent errors instead (see __init__)."""
 
-    def __init__(self, poses, images, intrinsics, H, W, n_rays, stride=1, offset=0, seed=0):
+    def __init__(self, poses, images, intrinsics, H, W, n_rays, stride=1, offset=0, seed=0, error_map=False, error_grid=128):
+        """error_map: the reference's --error_map loader (nerf/provider.py:234-238,300-321; nerf/utils.py:105-114,534-556) on the device.  True allocates a
+        map of ones [P, error_grid^2]; a tensor of that shape is taken as given (and updated in place).  With a map, sample_into draws n_rays cells of the
+        pose's row without replacement in proportion to their weight and one pixel inside each (rg_sample_rays_weighted), and update_error_map(pred, gt)
+        writes 0.1 * old + 0.9 * error back into the drawn cells (rg_error_map_update).  torch.multinomial raises when fewer than n_rays cells have a positive
+        weight; here the lowest-index invalid cells fill the draw: nothing inside a captured step may fault."""
         if not poses.is_cuda:
             raise ValueError("DeviceRaySampler: poses must be on the GPU")
         self.poses = poses.contiguous().float()
         self.images = None if images is None else images.contiguous().float().view(self.poses.shape[0], H * W, 3)
         self.intr = tuple(float(v) for v in intrinsics)
         self.H, self.W, self.n_rays, self.stride, self.offset, self.seed = int(H), int(W), int(n_rays), int(stride), int(offset), int(seed)
+        self.error_map, self.error_grid = None, int(error_grid)
+        if error_map is not False and error_map is not None:
+            G, P = self.error_grid, self.poses.shape[0]
+            if not 1 <= G <= 128:
+                raise ValueError("DeviceRaySampler: error_grid must lie in 1..128")
+            if not 1 <= self.n_rays <= G * G:
+                raise ValueError(f"DeviceRaySampler: a draw without replacement takes at most error_grid^2 = {G * G} rays, not {self.n_rays}")
+            if error_map is True:
+                error_map = torch.ones(P, G * G, dtype=torch.float32, device=self.poses.device)      # provider.py:236
+            elif not (torch.is_tensor(error_map) and error_map.device == self.poses.device and error_map.dtype == torch.float32
+                      and tuple(error_map.shape) == (P, G * G) and error_map.is_contiguous()):
+                raise ValueError(f"DeviceRaySampler: error_map must be a contiguous float32 tensor [{P}, {G * G}] on {self.poses.device}")
+            self.error_map = error_map
+            self.inds_coarse = torch.zeros(self.n_rays, dtype=torch.int64, device=self.poses.device)      # the cells of the last draw, ascending
+            self.pose_word = torch.zeros(1, dtype=torch.int32, device=self.poses.device)                  # ... and its pose
 
     @torch.no_grad()
-    def sample_into(self, step_counter, rays_o, rays_d, gt=None, inds_out=None, pose_out=None):
-        """step_counter: int32 device tensor [1] (or None = step 0).  rays_o / rays_d / gt: float32 buffers of n_rays * 3 elements."""
+    def sample_into(self, step_counter, rays_o, rays_d, gt=None, inds_out=None, pose_out=None, keys_out=None):
+        """step_counter: int32 device tensor [1] (or None = step 0).  rays_o / rays_d / gt: float32 buffers of n_rays * 3 elements.
+        keys_out (map only): float32 [error_grid^2], every cell's key of the race."""
         for t in (rays_o, rays_d, gt):
             if t is not None and (t.numel() != self.n_rays * 3 or t.dtype != torch.float32):
                 raise ValueError(f"DeviceRaySampler: buffers must hold {self.n_rays} x 3 float32 values")
         if gt is not None and self.images is None:
             raise ValueError("DeviceRaySampler: no image store to take the ground truth from")
         fx, fy, cx, cy = self.intr
+        if self.error_map is not None:
+            if keys_out is not None and (keys_out.numel() != self.error_grid ** 2 or keys_out.dtype != torch.float32):
+                raise ValueError(f"DeviceRaySampler: keys_out must hold {self.error_grid ** 2} float32 values")
+            nv.call("rg_sample_rays_weighted", nv.ptr(self.poses), self.poses.shape[0], nv.ptr(self.images), fx, fy, cx, cy, self.H, self.W, self.n_rays,
+                    nv.ptr(step_counter), self.stride, self.offset, self.seed, nv.ptr(self.error_map), self.error_grid, nv.ptr(rays_o), nv.ptr(rays_d), nv.ptr(gt),
+                    nv.ptr(inds_out), nv.ptr(self.pose_word), nv.ptr(self.inds_coarse), nv.ptr(keys_out), nv.stream())
+            if pose_out is not None:
+                pose_out.copy_(self.pose_word)
+            return
+        if keys_out is not None:
+            raise ValueError("DeviceRaySampler: keys_out belongs to the error-map draw")
         nv.call("rg_sample_rays", nv.ptr(self.poses), self.poses.shape[0], nv.ptr(self.images), fx, fy, cx, cy, self.H, self.W, self.n_rays,
                 nv.ptr(step_counter), self.stride, self.offset, self.seed, nv.ptr(rays_o), nv.ptr(rays_d), nv.ptr(gt), nv.ptr(inds_out), nv.ptr(pose_out),
                 nv.stream())
+
+    @torch.no_grad()
+    def update_error_map(self, pred, gt):
+        """Behind the step's loss: the cells of the last draw take 0.1 * old + 0.9 * mean((pred - gt)^2 over the channels) (utils.py:549-553).  pred / gt:
+        float32 buffers of n_rays * 3 elements, in the order sample_into wrote the rays.  No host value: capturable."""
+        if self.error_map is None:
+            raise ValueError("DeviceRaySampler: this sampler draws uniformly (error_map=False)")
+        for t in (pred, gt):
+            if t.numel() != self.n_rays * 3 or t.dtype != torch.float32:
+                raise ValueError(f"DeviceRaySampler: buffers must hold {self.n_rays} x 3 float32 values")
+        nv.call("rg_error_map_update", nv.ptr(self.error_map), self.poses.shape[0], self.error_grid, nv.ptr(self.pose_word), nv.ptr(self.inds_coarse),
+                nv.ptr(pred), nv.ptr(gt), self.n_rays, nv.stream())

@@ -258,8 +258,11 @@ class CleanLoop:
     `update_extra_interval` steps refresh the density grid (utils.py:852-869).  With more than one rank the gradients are averaged
     (dp.allreduce_gradients) before the optimiser step."""
 
-    def __init__(self, model, optimizer, render_kwargs, update_extra_interval=16, lr_scheduler=None, ema_decay=None):
+    def __init__(self, model, optimizer, render_kwargs, update_extra_interval=16, lr_scheduler=None, ema_decay=None, error_map=None):
         self.model, self.optimizer, self.lr_scheduler = model, optimizer, lr_scheduler
+        # the trainer's error map [images, 128 * 128] (utils.py:393-394): updated behind every step whose `data` carries the loader's 'index' and 'inds_coarse'
+        # (rays.get_rays(..., error_map=)), with the reference's own operators -- the comparator of rg_error_map_update
+        self.error_map = error_map
         self.render_kwargs = dict(render_kwargs)
         self.update_extra_interval = update_extra_interval
         self.global_step = 0
@@ -277,12 +280,25 @@ class CleanLoop:
             tmp.mul_(1.0 - decay)
             s_.sub_(tmp)
 
+    @torch.no_grad()
+    def _update_error_map(self, data, image):
+        """utils.py:534-556."""
+        index, inds = data["index"], data["inds_coarse"]                                   # [B], [B, N]
+        index = torch.as_tensor(index, device=self.error_map.device).reshape(-1)
+        error_map = self.error_map[index]                                                  # [B, G * G]
+        error = ((image - data["images"]) ** 2).mean(-1).reshape(inds.shape).to(error_map.device)
+        ema_error = 0.1 * error_map.gather(1, inds) + 0.9 * error
+        error_map.scatter_(1, inds, ema_error)
+        self.error_map[index] = error_map
+
     def step(self, data):
         if self.model.cuda_ray and self.global_step % self.update_extra_interval == 0:
             self.model.update_extra_state()
         self.global_step += 1
         self.optimizer.zero_grad(set_to_none=True)
         image, loss = train_step(self.model, data, self.render_kwargs)
+        if self.error_map is not None and "inds_coarse" in data and "index" in data:
+            self._update_error_map(data, image)
         loss.backward()
         if dp.world_size() > 1:
             dp.allreduce_gradients([p for g in self.optimizer.param_groups for p in g["params"]])
@@ -307,7 +323,8 @@ class GraphedCleanLoop:
     costs memory, not time; a step that produced more points than fit dropped its overflowing rays, exactly like the reference's bounded
     march (raymarching.cu:416 with M = mean_count, the default of its stage-1 train_step: force_all_rays=False) -- `overflowed()` reports it,
     and the grid-refresh check grows the buffers and captures again when a step came within 10 % of them.
-    sampler (rays.DeviceRaySampler): draws pose, pixels, rays and ground truth inside the graph from the step count; otherwise call
+    sampler (rays.DeviceRaySampler): draws pose, pixels, rays and ground truth inside the graph from the step count (with error_map=: from its
+    map of recent errors, which the step updates behind its loss); otherwise call
     step(data) with 'rays_o', 'rays_d' [..,3] and 'images' [..,3] of `n_rays` rays (copied into the static buffers)."""
 
     LOSS_RING = 1024
@@ -436,12 +453,14 @@ class GraphedCleanLoop:
                     nv.ptr(rec.fars), nv.ptr(self.bg), 0, nv.ptr(self.gt), 3 * N, 1.0 / dp.world_size(), nv.ptr(self.ws), nv.ptr(self.depth), nv.ptr(self.image),
                     nv.ptr(self.image_out), nv.ptr(self.depth_out), nv.ptr(self.g_image), nv.ptr(self.g_sig), nv.ptr(self.g_rgb), s)
             nv.call("clean_loss", nv.ptr(self.image_out), nv.ptr(self.gt), 3 * N, 1.0 / dp.world_size(), nv.ptr(self.loss), nv.ptr(self._g_image_books), *books, s)
+            self._update_error_map()
         else:
             nv.call("rm_composite_train_finish_fwd", nv.ptr(tr.sig), nv.ptr(tr.rgb), nv.ptr(rec.deltas), nv.ptr(rec.rays), M, N, self.T_thresh,
                     nv.ptr(rec.nears), nv.ptr(rec.fars), nv.ptr(self.bg), 0, nv.ptr(self.ws), nv.ptr(self.depth), nv.ptr(self.image),
                     nv.ptr(self.image_out), nv.ptr(self.depth_out), s)
             # the loss of the global batch is the mean over the ranks' losses: each rank seeds 1 / world, the exchange sums
             nv.call("clean_loss", nv.ptr(self.image_out), nv.ptr(self.gt), 3 * N, 1.0 / dp.world_size(), nv.ptr(self.loss), nv.ptr(self.g_image), *books, s)
+            self._update_error_map()
             nv.call("rm_composite_train_finish_bwd", None, nv.ptr(self.g_image), nv.ptr(tr.sig), nv.ptr(tr.rgb), nv.ptr(rec.deltas), nv.ptr(rec.rays),
                     nv.ptr(self.ws), nv.ptr(self.image), nv.ptr(self.bg), 0, M, N, self.T_thresh, 1, nv.ptr(self.g_sig), nv.ptr(self.g_rgb), s)
         # two-launch route: the weight gradients (a streaming reduction) run beside the table scatter (store- and LDS-bound) on the plan's stream,
@@ -461,6 +480,13 @@ class GraphedCleanLoop:
         else:
             nv.call("hg_levels_scatter", nv.ptr(xyzs), M, nv.ptr(rows), float(m.bound), nv.ptr(tr.d_planes), tr.stride, nv.ptr(self.plan),
                     nv.ptr_array([self.g_tables[l] for l in range(16)]), s)
+
+    def _update_error_map(self):
+        """A sampler that draws from an error map (rays.DeviceRaySampler(error_map=)): the drawn cells take this step's per-ray error, right behind the loss
+        (utils.py:534-556), from the rendered image and the ground truth themselves -- the loss seed 1 / world is not in it; every rank keeps its own map, as
+        the reference's per-process loader does."""
+        if self.sampler is not None and getattr(self.sampler, "error_map", None) is not None:
+            self.sampler.update_error_map(self.image_out, self.gt)
 
     def _join_weight_gradients(self):
         """Once per step: a second wait in a LATER captured segment (the optimiser behind a collective that ended the segment in which the plan's stream was
@@ -601,7 +627,7 @@ class GraphedCleanLoop:
         nv.call("mlp_pack_weights", nv.ptr(self.model.sigma_net.params.detach()), nv.ptr(self.model.color_net.params.detach()), nv.ptr(self.packed), nv.stream())
         # warm-up (Adam state in its capturable format, module loading, RCCL's lazy set-up); it must not train
         warm_up(self._whole_step, 2, self.optimizer, self.params,
-                extra=(self.step_dev, self.count_ring, self.loss_ring, self.noises, *(self.ema_shadow or ())))
+                extra=(self.step_dev, self.count_ring, self.loss_ring, self.noises, getattr(self.sampler, "error_map", None), *(self.ema_shadow or ())))
         # the restored weights' operand image
         nv.call("mlp_pack_weights", nv.ptr(self.model.sigma_net.params.detach()), nv.ptr(self.model.color_net.params.detach()), nv.ptr(self.packed), nv.stream())
         self.graph = SegmentedCapture()

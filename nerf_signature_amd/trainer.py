@@ -531,6 +531,9 @@ class GraphedWatermarkLoop:
         self._kept_key = None
         # content_sampler (rays.DeviceRaySampler): the step draws its own content batch -- pose, pixels, rays, ground truth -- on the
         # device, inside the captured graph, from the replay count; `data` / `next_data` then carry no content part
+        if getattr(content_sampler, "error_map", None) is not None:
+            raise ValueError("GraphedWatermarkLoop: content_sampler draws from an error map, which only stage 1 updates (stage1.GraphedCleanLoop); the reference's "
+                             "watermark stage never writes its map (utils_wtmk_disen.py:763), so a map here would stay what it was: pass a uniform sampler")
         self.content_sampler = content_sampler
         self._s_for = None            # host copy of the message the pre-sum buffer currently belongs to (None: unknown / stale)
         self.marched = None           # the block render's raymarching.MarchRecord (march-ahead, or the kept samples of fixed_blocks)
