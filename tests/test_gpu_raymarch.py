@@ -330,3 +330,290 @@ def test_wide_scan_equals_the_single_workgroup_scan(n):
     r = out[1][0].cpu().numpy().astype(np.int64)
     assert np.array_equal(r[:, 0], np.arange(n)) and np.array_equal(r[:, 2], c) and np.array_equal(r[:, 1], np.concatenate([[0], np.cumsum(c)[:-1]]))
     assert out[1][1].tolist() == [int(c.sum()), n]
+
+
+# ---- compositing: every entry point against the float64 restatement (tests/composite_ref.py), through the C ABI with hand-built ray tables ----
+# The bound is composite_ref.composite_tolerance (derived there; tests/test_composite_cpu.py shows it is reachable and that it kills six mutants).
+# Every output buffer starts as NaN, so a row nobody wrote is seen.  Each test prints the largest |kernel - float64| / bound it met.
+
+import composite_ref as cr
+
+_CREF = {}
+
+
+def _cref(case):
+    """float64 forward of a case and the plain backward with its bound, computed once and shared"""
+    if case.name not in _CREF:
+        a = (case.sigmas, case.rgbs, case.deltas, case.rays, case.T_thresh)
+        fwd = cr.train_forward(*a)
+        gs, gc = cr.train_backward(case.grad_weights_sum, case.grad_image, *a, fwd=fwd)
+        _CREF[case.name] = cr.Bag(a=a, fwd=fwd, gs=gs, gc=gc, tol=cr.composite_tolerance(*a, fwd, case.grad_weights_sum, case.grad_image))
+    return _CREF[case.name]
+
+
+def _nan(*shape):
+    return torch.full(shape, float("nan"), device="cuda")
+
+
+def _dev(case):
+    return cr.Bag({k: _cuda(case[k]) for k in ("sigmas", "rgbs", "deltas", "rays", "nears", "fars", "bg", "bg_rays", "gt", "grad_weights_sum", "grad_image")})
+
+
+def _bits_equal(a, b):
+    return torch.equal(a.view(torch.int32), b.view(torch.int32))
+
+
+class _Worst(dict):
+    def check(self, case, what, got, want, tol, rows=None):
+        """got (device) within tol of want on `rows` (default: all)"""
+        got = got.cpu().numpy().astype(np.float64)
+        if rows is not None:
+            got, want, tol = got[rows], want[rows], tol[rows]
+        ratio = cr.max_ratio(got, want, tol)
+        self[what] = max(self.get(what, 0.0), ratio)
+        assert ratio <= 1.0, f"{case.name}: {what} is {ratio:.3g} x its bound"
+
+    def show(self, title):
+        print(f"\n{title}: largest |kernel - float64| / bound: " + ", ".join(f"{k} {v:.3f}" for k, v in self.items()))
+
+
+_SPARE = 2      # output rows behind the table's ids: nobody may write them
+
+
+def _owned(case):
+    """mask over the output rows: the table's ray ids"""
+    ids = np.zeros(case.N + _SPARE, bool)
+    ids[case.rays[:, 0]] = True
+    return ids
+
+
+def _train_fwd(nv, case, d):
+    n_all = case.N + _SPARE
+    ws, dep, img = _nan(n_all), _nan(n_all), _nan(n_all, 3)
+    nv.call("rm_composite_train_fwd", nv.ptr(d.sigmas), nv.ptr(d.rgbs), nv.ptr(d.deltas), nv.ptr(d.rays), case.M, case.N, float(case.T_thresh),
+            nv.ptr(ws), nv.ptr(dep), nv.ptr(img), nv.stream())
+    return ws, dep, img
+
+
+def _check_forward(worst, case, fwd, tol, ws, dep, img):
+    own = _owned(case)
+    worst.check(case, "weights_sum", ws, fwd.weights_sum, tol.weights_sum, np.flatnonzero(own))
+    worst.check(case, "depth", dep, fwd.depth, tol.depth, np.flatnonzero(own))
+    worst.check(case, "image", img, fwd.image, tol.image, np.flatnonzero(own))
+    for t in (ws, dep, img):
+        assert bool(torch.isnan(t[_cuda(~own)]).all()), f"{case.name}: an output of a ray outside the table was written"
+
+
+def _check_grads(worst, case, live, want_gs, want_gc, tol, gs, gc):
+    """live rows within the bound; every other one of the M rows exactly 0.0 (so none is left as the NaN it started as)"""
+    worst.check(case, "grad_sigmas", gs, want_gs, tol.grad_sigmas, live)
+    worst.check(case, "grad_rgbs", gc, want_gc, tol.grad_rgbs, live)
+    dead = _cuda(~live)
+    assert bool((gs[dead] == 0).all()) and bool((gc[dead] == 0).all()), f"{case.name}: a row that is not live is not exactly zero"
+
+
+def test_composite_train_fwd_bwd_against_float64():
+    """rm_composite_train_fwd / _bwd on every case: outputs and the gradients of live rows within the bound, every other row exactly 0.0."""
+    from nerf_signature_amd import _native as nv
+    worst = _Worst()
+    for case in cr.cases():
+        r, d = _cref(case), _dev(case)
+        ws, dep, img = _train_fwd(nv, case, d)
+        _check_forward(worst, case, r.fwd, r.tol, ws, dep, img)
+        if case.name.startswith("zero"):
+            own = _cuda(_owned(case))
+            assert bool((ws[own] == 0).all()) and bool((dep[own] == 0).all()) and bool((img[own] == 0).all())
+        gs, gc = _nan(case.M), _nan(case.M, 3)
+        nv.call("rm_composite_train_bwd", nv.ptr(d.grad_weights_sum), nv.ptr(d.grad_image), nv.ptr(d.sigmas), nv.ptr(d.rgbs), nv.ptr(d.deltas), nv.ptr(d.rays),
+                nv.ptr(ws), nv.ptr(img), case.M, case.N, float(case.T_thresh), nv.ptr(gs), nv.ptr(gc), nv.stream())
+        _check_grads(worst, case, r.fwd.live, r.gs, r.gc, r.tol, gs, gc)
+    worst.show("rm_composite_train_fwd/_bwd")
+
+
+@pytest.mark.parametrize("bg_stride", [0, 3])
+def test_composite_train_finish_fwd_against_float64(bg_stride):
+    """The forward with the render tail: the three raw outputs bit-equal to rm_composite_train_fwd's, image_out and depth_out within the bound."""
+    from nerf_signature_amd import _native as nv
+    worst = _Worst()
+    for case in cr.cases():
+        r, d = _cref(case), _dev(case)
+        n_all = case.N + _SPARE
+        bg = case.bg if bg_stride == 0 else case.bg_rays
+        ws0, dep0, img0 = _train_fwd(nv, case, d)
+        ws, dep, img, img_out, dep_out = _nan(n_all), _nan(n_all), _nan(n_all, 3), _nan(n_all, 3), _nan(n_all)
+        nv.call("rm_composite_train_finish_fwd", nv.ptr(d.sigmas), nv.ptr(d.rgbs), nv.ptr(d.deltas), nv.ptr(d.rays), case.M, case.N, float(case.T_thresh),
+                nv.ptr(d.nears), nv.ptr(d.fars), nv.ptr(d.bg if bg_stride == 0 else d.bg_rays), bg_stride, nv.ptr(ws), nv.ptr(dep), nv.ptr(img),
+                nv.ptr(img_out), nv.ptr(dep_out), nv.stream())
+        assert _bits_equal(ws, ws0) and _bits_equal(dep, dep0) and _bits_equal(img, img0), case.name
+        want_img, want_dep = cr.finish(r.fwd.weights_sum, r.fwd.image, r.fwd.depth, case.nears, case.fars, bg)
+        tol = cr.composite_tolerance(*r.a, r.fwd, bg=bg, nears=case.nears, fars=case.fars)
+        own = np.flatnonzero(_owned(case))
+        worst.check(case, "image_out", img_out, want_img, tol.image_out, own)
+        worst.check(case, "depth_out", dep_out, want_dep, tol.depth_out, own)
+        assert bool(torch.isnan(img_out[_cuda(~_owned(case))]).all()) and bool(torch.isnan(dep_out[_cuda(~_owned(case))]).all())
+        if case.name.startswith("zero"):       # nothing absorbed: exactly the background
+            assert torch.equal(img_out[_cuda(own)], _cuda(np.broadcast_to(bg, (case.N, 3))[own]))
+    worst.show(f"rm_composite_train_finish_fwd bg_stride={bg_stride}")
+
+
+@pytest.mark.parametrize("bg_stride", [0, 3])
+@pytest.mark.parametrize("with_gws", [True, False])
+@pytest.mark.parametrize("in_order", [0, 1])
+def test_composite_train_finish_bwd_against_float64(in_order, with_gws, bg_stride):
+    """The backward with the tail's adjoint.  rays_in_order = 1 (no memsets: the kernel zero-fills what it does not own) must leave every one of the M rows
+    finite, and the rows after termination, of dropped rays and of the padding exactly zero."""
+    from nerf_signature_amd import _native as nv
+    worst = _Worst()
+    for case in cr.cases():
+        if in_order and not case.in_order:
+            continue
+        r, d = _cref(case), _dev(case)
+        bg = case.bg if bg_stride == 0 else case.bg_rays
+        ws, dep, img = _train_fwd(nv, case, d)
+        gws_in = case.grad_weights_sum if with_gws else None
+        gws, gi = cr.finish_backward(case.grad_image, bg, gws_in)
+        want_gs, want_gc = cr.train_backward(gws, gi, *r.a, fwd=r.fwd)
+        tol = cr.composite_tolerance(*r.a, r.fwd, gws_in, case.grad_image, bg=bg)
+        gs, gc = _nan(case.M), _nan(case.M, 3)
+        nv.call("rm_composite_train_finish_bwd", nv.ptr(d.grad_weights_sum if with_gws else None), nv.ptr(d.grad_image), nv.ptr(d.sigmas), nv.ptr(d.rgbs),
+                nv.ptr(d.deltas), nv.ptr(d.rays), nv.ptr(ws), nv.ptr(img), nv.ptr(d.bg if bg_stride == 0 else d.bg_rays), bg_stride, case.M, case.N,
+                float(case.T_thresh), in_order, nv.ptr(gs), nv.ptr(gc), nv.stream())
+        _check_grads(worst, case, r.fwd.live, want_gs, want_gc, tol, gs, gc)
+        assert bool(torch.isfinite(gs).all()) and bool(torch.isfinite(gc).all()), case.name
+    worst.show(f"rm_composite_train_finish_bwd rays_in_order={in_order} grad_weights_sum={'given' if with_gws else 'null'} bg_stride={bg_stride}")
+
+
+def _mse(nv, case, d, bg_stride):
+    n_all = case.N + _SPARE
+    o = cr.Bag(weights_sum=_nan(n_all), depth=_nan(n_all), image=_nan(n_all, 3), image_out=_nan(n_all, 3), depth_out=_nan(n_all), grad_image=_nan(n_all, 3),
+               grad_sigmas=_nan(case.M), grad_rgbs=_nan(case.M, 3))
+    nv.call("rm_composite_train_mse", nv.ptr(d.sigmas), nv.ptr(d.rgbs), nv.ptr(d.deltas), nv.ptr(d.rays), case.M, case.N, float(case.T_thresh), nv.ptr(d.nears),
+            nv.ptr(d.fars), nv.ptr(d.bg if bg_stride == 0 else d.bg_rays), bg_stride, nv.ptr(d.gt), case.n_values, float(case.grad_scale), nv.ptr(o.weights_sum),
+            nv.ptr(o.depth), nv.ptr(o.image), nv.ptr(o.image_out), nv.ptr(o.depth_out), nv.ptr(o.grad_image), nv.ptr(o.grad_sigmas), nv.ptr(o.grad_rgbs), nv.stream())
+    return o
+
+
+def _mse_reference(case, fwd, a, bg):
+    """forward -> finish -> seed -> backward, and the bound of the whole chain"""
+    img_out, dep_out = cr.finish(fwd.weights_sum, fwd.image, fwd.depth, case.nears, case.fars, bg)
+    seed = cr.mse_seed(img_out, case.gt, case.grad_scale, case.n_values)
+    gws, gi = cr.finish_backward(seed, bg)
+    gs, gc = cr.train_backward(gws, gi, *a, fwd=fwd)
+    tol = cr.composite_tolerance(*a, fwd, bg=bg, nears=case.nears, fars=case.fars, gt=case.gt, grad_scale=case.grad_scale, n_values=case.n_values)
+    return cr.Bag(image_out=img_out, depth_out=dep_out, grad_image=seed, grad_sigmas=gs, grad_rgbs=gc), tol
+
+
+@pytest.mark.parametrize("bg_stride", [0, 3])
+def test_composite_train_mse_against_float64(bg_stride):
+    """The one-launch kernel of the captured stage-1 loop: every output against the reference chain, and the zero-fill of all rows it does not own."""
+    from nerf_signature_amd import _native as nv
+    worst = _Worst()
+    for case in cr.cases():
+        if not case.in_order:          # the entry point is defined for ascending gapless tables only
+            continue
+        r, d = _cref(case), _dev(case)
+        bg = case.bg if bg_stride == 0 else case.bg_rays
+        want, tol = _mse_reference(case, r.fwd, r.a, bg)
+        o = _mse(nv, case, d, bg_stride)
+        _check_forward(worst, case, r.fwd, tol, o.weights_sum, o.depth, o.image)
+        own = np.flatnonzero(_owned(case))
+        for k in ("image_out", "depth_out", "grad_image"):
+            worst.check(case, k, o[k], want[k], tol[k], own)
+            assert bool(torch.isnan(o[k][_cuda(~_owned(case))]).all())
+        _check_grads(worst, case, r.fwd.live, want.grad_sigmas, want.grad_rgbs, tol, o.grad_sigmas, o.grad_rgbs)
+        assert bool(torch.isfinite(o.grad_sigmas).all()) and bool(torch.isfinite(o.grad_rgbs).all()), case.name
+    worst.show(f"rm_composite_train_mse bg_stride={bg_stride}")
+
+
+def test_composite_non_finite_density_stays_in_its_ray():
+    """One -inf and one NaN density in one ray of a workgroup: that ray's sums and the gradients of its live rows are non-finite, its rows behind the
+    NaN (not live: a NaN transmittance passes no test) are zero, and the three neighbours are within the bound of the float64 reference."""
+    from nerf_signature_amd import _native as nv
+    case = cr.poisoned_case()
+    r, d = _cref(case), _dev(case)
+    bad = case.poison
+    off, cnt = int(case.rays[bad, 1]), int(case.rays[bad, 2])
+    mine = np.zeros(case.M, bool)
+    mine[off:off + cnt] = True
+    live_bad, good = r.fwd.live & mine, np.array([i for i in range(case.N) if i != bad])
+    assert live_bad.sum() == 6 and not np.isfinite(r.fwd.weights_sum[bad]) and not np.isfinite(r.fwd.image[bad]).any()
+    assert not np.isfinite(r.gs[live_bad]).any() and not np.isfinite(r.gc[live_bad]).any()        # the reference says so too
+    worst = _Worst()
+
+    def check(ws, img, gs, gc, want_gs, want_gc, tol):
+        assert not bool(torch.isfinite(ws[bad])) and not bool(torch.isfinite(img[bad]).any())
+        assert not bool(torch.isfinite(gs[_cuda(live_bad)]).any()) and not bool(torch.isfinite(gc[_cuda(live_bad)]).any())
+        worst.check(case, "weights_sum", ws, r.fwd.weights_sum, tol.weights_sum, good)
+        worst.check(case, "image", img, r.fwd.image, tol.image, good)
+        rest = ~mine
+        worst.check(case, "grad_sigmas", gs, want_gs, tol.grad_sigmas, r.fwd.live & rest)
+        worst.check(case, "grad_rgbs", gc, want_gc, tol.grad_rgbs, r.fwd.live & rest)
+        dead = _cuda(~r.fwd.live)
+        assert bool((gs[dead] == 0).all()) and bool((gc[dead] == 0).all())
+
+    ws, dep, img = _train_fwd(nv, case, d)
+    gs, gc = _nan(case.M), _nan(case.M, 3)
+    nv.call("rm_composite_train_bwd", nv.ptr(d.grad_weights_sum), nv.ptr(d.grad_image), nv.ptr(d.sigmas), nv.ptr(d.rgbs), nv.ptr(d.deltas), nv.ptr(d.rays),
+            nv.ptr(ws), nv.ptr(img), case.M, case.N, float(case.T_thresh), nv.ptr(gs), nv.ptr(gc), nv.stream())
+    check(ws, img, gs, gc, r.gs, r.gc, r.tol)
+    want, tol = _mse_reference(case, r.fwd, r.a, case.bg)
+    o = _mse(nv, case, d, 0)
+    check(o.weights_sum, o.image, o.grad_sigmas, o.grad_rgbs, want.grad_sigmas, want.grad_rgbs, tol)
+    worst.check(case, "grad_image", o.grad_image, want.grad_image, tol.grad_image, good)
+    assert not bool(torch.isfinite(o.grad_image[bad]).any())
+    worst.show("non-finite density, neighbours of the poisoned ray")
+
+
+def _burst_on_device(nv, n_alive0, first_step, density_scale, eval_form):
+    """A whole multi-round evaluation run on the device beside the float64 reference: rays_alive compared after every round (composite_ref.run_burst)."""
+    N = cr.BURST_RAYS
+    scene = cr.burst_scene()
+    t, ws, dep, img = _cuda(scene.rays_t0), _nan(N), _nan(N), _nan(N, 3)       # rays 0 .. n_alive0-1 take part; the others' state must stay NaN
+    for x in (ws, dep, img):
+        x[:n_alive0] = 0
+
+    def device_round(rd):
+        rows = N * rd.n_step                                     # room for every thread of the launch; rows past n_alive * n_step hold deltas = 0
+        pad = lambda a: _cuda(np.concatenate([a, np.zeros((rows - len(a),) + a.shape[1:], a.dtype)]))
+        alive = _cuda(np.concatenate([rd.rays_alive, np.zeros(N - rd.n_alive, np.int32)]))
+        sig, rgb, dl = pad(rd.sigmas), pad(rd.rgbs), pad(rd.deltas)      # held in names: a temporary's memory would be handed to the next one
+        if eval_form:
+            ctl = _cuda(np.array([rd.n_alive, rd.n_step, rd.n_alive * rd.n_step, 0], np.int32))
+            nv.call("rm_eval_composite", nv.ptr(ctl), N, 1e-2, float(density_scale), nv.ptr(alive), nv.ptr(t), nv.ptr(sig), nv.ptr(rgb),
+                    nv.ptr(dl), nv.ptr(ws), nv.ptr(dep), nv.ptr(img), nv.stream())
+        else:
+            nv.call("rm_composite", rd.n_alive, rd.n_step, 1e-2, nv.ptr(alive), nv.ptr(t), nv.ptr(sig), nv.ptr(rgb), nv.ptr(dl),
+                    nv.ptr(ws), nv.ptr(dep), nv.ptr(img), nv.stream())
+        got = alive.cpu().numpy()
+        assert (got[rd.n_alive:] == 0).all()
+        return got[:rd.n_alive]
+    st, log = cr.run_burst(n_alive0, first_step, 1e-2, density_scale if eval_form else None, fp32=device_round)
+    u = np.arange(N) < n_alive0
+    np.testing.assert_array_equal(t.cpu().numpy().astype(np.float64), np.where(u, st.t, scene.rays_t0))      # rays_t: exact
+    for x in (ws, dep, img):
+        assert bool(torch.isnan(x[n_alive0:]).all())
+    return [(cr.max_ratio(x.cpu().numpy().astype(np.float64)[u], want[u], tol[u]), k)
+            for k, x, want, tol in (("weights_sum", ws, st.ws, st.bound.weights_sum), ("depth", dep, st.d, st.bound.depth), ("image", img, st.im, st.bound.image))], log
+
+
+@pytest.mark.parametrize("n_alive0", cr.BURST_ALIVE)
+def test_composite_burst_against_float64(n_alive0):
+    """rm_composite over whole runs: n_step cycles through 1..8, rays end by deltas == 0 (at step 0 and in mid-burst) and by T < T_thresh (on the first and
+    on the last step of a burst); rays_alive and rays_t equal the reference's exactly, the accumulators are within the serial chain's bound."""
+    from nerf_signature_amd import _native as nv
+    ratios, log = _burst_on_device(nv, n_alive0, 1 + n_alive0 % 8, None, False)
+    print(f"\nrm_composite n_alive={n_alive0}: largest |kernel - float64| / bound: " + ", ".join(f"{k} {v:.3f}" for v, k in ratios))
+    assert all(v <= 1.0 for v, _ in ratios), ratios
+    assert log.rounds > 1 and (n_alive0 < 63 or (log.first and log.last and log.zero_first and log.zero_mid and log.steps == set(range(1, 9))))
+
+
+@pytest.mark.parametrize("density_scale", [1.0, 0.37])
+@pytest.mark.parametrize("n_alive0", cr.BURST_ALIVE)
+def test_eval_composite_against_float64(n_alive0, density_scale):
+    """rm_eval_composite: the same runs with the counts in `ctl` on the device (the launch covers all N threads, ctl[0] < N in every round but the first
+    of the full run) and the density scaled inside the kernel."""
+    from nerf_signature_amd import _native as nv
+    ratios, log = _burst_on_device(nv, n_alive0, 1 + n_alive0 % 8, density_scale, True)
+    print(f"\nrm_eval_composite n_alive={n_alive0} density_scale={density_scale}: largest |kernel - float64| / bound: " + ", ".join(f"{k} {v:.3f}" for v, k in ratios))
+    assert all(v <= 1.0 for v, _ in ratios), ratios
+    assert log.rounds > 1
