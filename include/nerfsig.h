@@ -209,6 +209,24 @@ int rg_sample_rays_weighted(const float *poses, uint32_t P, const float *images,
                             float *rays_o, float *rays_d, float *gt, int64_t *inds_out, int32_t *pose_out, int64_t *inds_coarse_out, float *keys_out,
                             nsig_stream_t stream);
 
+/* The stage-1 step on RGBA ground truth (nerf/utils.py:498-507): a fresh background colour per pixel and the target blended against it.  rgba [N,4] float32
+ * (16-byte aligned).  bg_out[n][c] = (draw_word(draw_base(seed, step, 4), 3 n + c) >> 8) * 2^-24: U[0,1) on torch.rand's 24-bit grid, sequence 4 of the counter
+ * hash the samplers draw from (0: pixel indices, 1: race keys, 2 / 3: sub-cell offsets), step = *step_counter (a DEVICE int32, NULL = 0).
+ * gt_out[n][c] = rgb * a + bg * (1 - a) in fp32, every product and sum rounded on its own in the reference's order: the bits of the torch expression on the
+ * same operands.  A pure function of (seed, step, ray): no atomics, no host value, capturable. */
+int rg_blend_random_background(const float *rgba, uint32_t N, const int32_t *step_counter, uint64_t seed, float *bg_out, float *gt_out, nsig_stream_t stream);
+
+/* rg_sample_rays / rg_sample_rays_weighted over an RGBA store: images [P,H*W,4] float32 (required, 16-byte aligned; one 16-byte load per drawn pixel).  Pixels,
+ * rays, inds_out, pose_out, inds_coarse_out and keys_out are the 3-channel entry points' bits for the same (seed, step); bg_out [N,3] (required) takes the rays'
+ * background colours and gt [N,3] (or NULL) the blended target, both exactly as rg_blend_random_background computes them from the drawn pixels. */
+int rg_sample_rays_rgba(const float *poses, uint32_t P, const float *images, float fx, float fy, float cx, float cy, uint32_t H, uint32_t W,
+                        uint32_t N, const int32_t *step_counter, uint32_t stride, uint32_t offset, uint64_t seed, float *rays_o, float *rays_d,
+                        float *gt, float *bg_out, int64_t *inds_out, int32_t *pose_out, nsig_stream_t stream);
+int rg_sample_rays_weighted_rgba(const float *poses, uint32_t P, const float *images, float fx, float fy, float cx, float cy, uint32_t H, uint32_t W,
+                                 uint32_t N, const int32_t *step_counter, uint32_t stride, uint32_t offset, uint64_t seed, const float *error_map, uint32_t grid,
+                                 float *rays_o, float *rays_d, float *gt, float *bg_out, int64_t *inds_out, int32_t *pose_out, int64_t *inds_coarse_out,
+                                 float *keys_out, nsig_stream_t stream);
+
 /* The map's update behind a step's loss (nerf/utils.py:534-556): error_map[*pose_dev][inds_coarse[n]] = 0.1 * old + 0.9 * e_n with
  * e_n = mean over the 3 channels of (pred[n] - gt[n])^2; pred, gt [N,3]; pose_dev: the DEVICE word rg_sample_rays_weighted wrote.  The cells of one draw
  * are distinct (plain stores); a non-finite e_n leaves its cell unchanged. */

@@ -21,6 +21,9 @@ SIGNATURES = {
     "nsig_host_device_pointer": [_vp],
     "rg_sample_rays": [_vp, _u32, _vp, _fl, _fl, _fl, _fl, _u32, _u32, _u32, _vp, _u32, _u32, _c.c_uint64, _vp, _vp, _vp, _vp, _vp, _vp],
     "rg_sample_rays_weighted": [_vp, _u32, _vp, _fl, _fl, _fl, _fl, _u32, _u32, _u32, _vp, _u32, _u32, _c.c_uint64, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "rg_blend_random_background": [_vp, _u32, _vp, _c.c_uint64, _vp, _vp, _vp],
+    "rg_sample_rays_rgba": [_vp, _u32, _vp, _fl, _fl, _fl, _fl, _u32, _u32, _u32, _vp, _u32, _u32, _c.c_uint64, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "rg_sample_rays_weighted_rgba": [_vp, _u32, _vp, _fl, _fl, _fl, _fl, _u32, _u32, _u32, _vp, _u32, _u32, _c.c_uint64, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "rg_error_map_update": [_vp, _u32, _u32, _vp, _vp, _vp, _vp, _u32, _vp],
     "rg_get_rays": [_vp, _fl, _fl, _fl, _fl, _u32, _u32, _vp, _u32, _u32, _vp, _vp, _vp],
     "rm_near_far_from_aabb": [_vp, _vp, _vp, _u32, _fl, _vp, _vp, _vp],

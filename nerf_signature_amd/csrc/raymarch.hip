@@ -137,17 +137,45 @@ __device__ inline uint32_t mix32(uint32_t v) {   // a finaliser with full avalan
 }
 
 // The per-step prefix of every draw's counter hash: (seed, step) -> one word; a draw is mix32(word ^ f(index)).  `stream` separates the independent
-// sequences one step needs (0: the uniform sampler's pixel indices, as before; the weighted sampler's keys and sub-cell offsets take 1..3).
+// sequences one step needs (0: the uniform sampler's pixel indices, as before; the weighted sampler's keys and sub-cell offsets take 1..3; 4: the RGBA
+// step's per-pixel background colours).
 __device__ inline uint32_t draw_base(uint32_t seed_lo, uint32_t seed_hi, uint32_t step, uint32_t stream) {
     const uint32_t b = mix32(mix32(seed_lo ^ (step * 0x9e3779b9u)) + seed_hi);
     return stream == 0u ? b : mix32(b + stream * 0x7f4a7c15u);
 }
 __device__ inline uint32_t draw_word(uint32_t base, uint32_t index) { return mix32(base ^ (index * 0x85ebca6bu + 0x6b43a9b5u)); }
 
+// The stage-1 step on RGBA ground truth (nerf/utils.py:498-507): a fresh background colour per pixel, bg = torch.rand_like(images[..., :3]), and the target
+// gt = rgb * a + bg * (1 - a).  bg[c] of ray n is word 3 n + c of sequence 4 of the step's counter hash, on torch.rand's grid (24 bits * 2^-24, exact in fp32);
+// the blend in the reference's operation order with every product and sum rounded on its own (the file is built without contraction; the intrinsics say so
+// where it matters), so that it equals the torch expression on the same operands bit for bit.  The one place the blend is written: the stand-alone kernel and
+// both RGBA samplers call it.
+constexpr uint32_t kBackgroundStream = 4u;
+__device__ inline void blend_random_background(float4 px, uint32_t bg_base, uint32_t n, float *__restrict__ bg_out, float *__restrict__ gt) {
+    const float rgb[3] = {px.x, px.y, px.z};
+    const float rest = __fsub_rn(1.0f, px.w);
+#pragma unroll
+    for (uint32_t c = 0; c < 3u; ++c) {
+        const float b = (float)(draw_word(bg_base, 3u * n + c) >> 8) * (1.0f / 16777216.0f);       // [0, 1)
+        bg_out[3 * (size_t)n + c] = b;
+        if (gt != nullptr) gt[3 * (size_t)n + c] = __fadd_rn(__fmul_rn(rgb[c], px.w), __fmul_rn(b, rest));
+    }
+}
+
+__global__ void k_blend_random_background(const float4 *__restrict__ rgba, uint32_t N, const int32_t *__restrict__ step_counter, uint32_t seed_lo, uint32_t seed_hi,
+                                          float *__restrict__ bg_out, float *__restrict__ gt_out) {
+    const uint32_t n = blockIdx.x * blockDim.x + threadIdx.x;
+    if (n >= N) return;
+    const uint32_t step = step_counter ? (uint32_t)step_counter[0] : 0u;
+    blend_random_background(rgba[n], draw_base(seed_lo, seed_hi, step, kBackgroundStream), n, bg_out, gt_out);
+}
+
 // Ray n of a drawn batch: pixel `ind` of pose p -- the ray arithmetic of k_get_rays, the stored pixel as ground truth.  Shared by both samplers.
+// RGBA: the store holds [P, H*W, 4] (one 16-byte load per pixel); the ray's background colour goes to bg_out and the ground truth is the blend against it.
+template <bool RGBA>
 __device__ inline void write_sampled_ray(const float *__restrict__ poses, const float *__restrict__ images, float fx, float fy, float cx, float cy, uint32_t H,
                                          uint32_t W, uint32_t p, uint32_t ind, uint32_t n, float *__restrict__ rays_o, float *__restrict__ rays_d,
-                                         float *__restrict__ gt, int64_t *__restrict__ inds_out) {
+                                         float *__restrict__ gt, int64_t *__restrict__ inds_out, uint32_t bg_base, float *__restrict__ bg_out) {
     const float i = (float)(ind % W) + 0.5f, j = (float)(ind / W) + 0.5f;                      // as k_get_rays
     const float x = (i - cx) / fx, y = (j - cy) / fy, z = 1.0f;
     const float nrm = sqrtf(x * x + y * y + z * z);
@@ -159,24 +187,30 @@ __device__ inline void write_sampled_ray(const float *__restrict__ poses, const 
         d[c] = dx * Pm[4 * c] + dy * Pm[4 * c + 1] + dz * Pm[4 * c + 2];
         o[c] = Pm[4 * c + 3];
     }
-    if (gt != nullptr) {
-        const float *px = images + 3 * ((size_t)p * H * W + ind);
-        gt[3 * (size_t)n] = px[0]; gt[3 * (size_t)n + 1] = px[1]; gt[3 * (size_t)n + 2] = px[2];
+    if constexpr (RGBA) {
+        blend_random_background(reinterpret_cast<const float4 *>(images)[(size_t)p * H * W + ind], bg_base, n, bg_out, gt);
+    } else {
+        if (gt != nullptr) {
+            const float *px = images + 3 * ((size_t)p * H * W + ind);
+            gt[3 * (size_t)n] = px[0]; gt[3 * (size_t)n + 1] = px[1]; gt[3 * (size_t)n + 2] = px[2];
+        }
     }
     if (inds_out != nullptr) inds_out[n] = (int64_t)ind;
 }
 
+template <bool RGBA>
 __global__ void k_sample_rays(const float *__restrict__ poses, uint32_t P, const float *__restrict__ images, float fx, float fy, float cx, float cy,
                               uint32_t H, uint32_t W, uint32_t N, const int32_t *__restrict__ step_counter, uint32_t stride, uint32_t offset,
                               uint32_t seed_lo, uint32_t seed_hi, float *__restrict__ rays_o, float *__restrict__ rays_d, float *__restrict__ gt,
-                              int64_t *__restrict__ inds_out, int32_t *__restrict__ pose_out) {
+                              int64_t *__restrict__ inds_out, int32_t *__restrict__ pose_out, float *__restrict__ bg_out) {
     const uint32_t n = blockIdx.x * blockDim.x + threadIdx.x;
     if (n >= N) return;
     const uint32_t step = step_counter ? (uint32_t)step_counter[0] : 0u;
     const uint32_t p = (uint32_t)(((uint64_t)step * stride + offset) % P);
     const uint32_t r = draw_word(draw_base(seed_lo, seed_hi, step, 0u), n);
     const uint32_t ind = (uint32_t)(((uint64_t)r * ((uint64_t)H * W)) >> 32);                  // uniform in [0, H*W)
-    write_sampled_ray(poses, images, fx, fy, cx, cy, H, W, p, ind, n, rays_o, rays_d, gt, inds_out);
+    write_sampled_ray<RGBA>(poses, images, fx, fy, cx, cy, H, W, p, ind, n, rays_o, rays_d, gt, inds_out,
+                            RGBA ? draw_base(seed_lo, seed_hi, step, kBackgroundStream) : 0u, bg_out);
     if (pose_out != nullptr && n == 0) pose_out[0] = (int32_t)p;
 }
 
@@ -193,15 +227,16 @@ __global__ void k_sample_rays(const float *__restrict__ poses, uint32_t P, const
 //            every key of a pass into one or two bins), a wave scans the 256 bins from the top -> threshold key T and the number of keys above it;
 //   compact: every key > T is drawn, and the first N - above keys == T in cell order (equal keys go to the lower cell); ballots rank the cells inside a
 //            wave, the waves' totals are summed through LDS: the drawn cells leave in ASCENDING cell order -- no global atomics, bit-reproducible;
-//   rays   : ray n belongs to drawn cell n: a uniform pixel of the cell (utils.py:108-112: the row is "x"), then write_sampled_ray.
+//   rays   : ray n belongs to drawn cell n: a uniform pixel of the cell (utils.py:108-112: the row is "x"), then write_sampled_ray (RGBA: with the blend).
 constexpr uint32_t kWeightedThreads = 1024, kWeightedWaves = kWeightedThreads / 64, kMaxErrorGrid = 128, kMaxKeysPerLane = kMaxErrorGrid * kMaxErrorGrid / kWeightedThreads;
 constexpr uint32_t kHistCopies = 32;
 
+template <bool RGBA>
 __global__ __launch_bounds__(kWeightedThreads) void k_sample_rays_weighted(
     const float *__restrict__ poses, uint32_t P, const float *__restrict__ images, float fx, float fy, float cx, float cy, uint32_t H, uint32_t W, uint32_t N,
     const int32_t *__restrict__ step_counter, uint32_t stride, uint32_t offset, uint32_t seed_lo, uint32_t seed_hi, const float *__restrict__ error_map, uint32_t G,
     float *__restrict__ rays_o, float *__restrict__ rays_d, float *__restrict__ gt, int64_t *__restrict__ inds_out, int32_t *__restrict__ pose_out,
-    int64_t *__restrict__ inds_coarse_out, float *__restrict__ keys_out) {
+    int64_t *__restrict__ inds_coarse_out, float *__restrict__ keys_out, float *__restrict__ bg_out) {
     __shared__ uint32_t hist[256 * kHistCopies];                  // 32 KiB
     __shared__ uint32_t drawn[kMaxErrorGrid * kMaxErrorGrid];     // 64 KiB: the drawn cells in ascending order
     __shared__ uint32_t bins[256];
@@ -304,12 +339,13 @@ __global__ __launch_bounds__(kWeightedThreads) void k_sample_rays_weighted(
 
     // ---- rays: a uniform pixel inside each drawn cell
     const uint32_t row_base = draw_base(seed_lo, seed_hi, step, 2u), col_base = draw_base(seed_lo, seed_hi, step, 3u);
+    const uint32_t bg_base = RGBA ? draw_base(seed_lo, seed_hi, step, kBackgroundStream) : 0u;
     const float sx = (float)H / (float)G, sy = (float)W / (float)G;
     for (uint32_t n = tid; n < N; n += kWeightedThreads) {
         const uint32_t c = drawn[n];
         const float u1 = (float)(draw_word(row_base, n) >> 8) * (1.0f / 16777216.0f), u2 = (float)(draw_word(col_base, n) >> 8) * (1.0f / 16777216.0f);   // [0, 1)
         const uint32_t row = min(H - 1u, (uint32_t)((float)(c / G) * sx + u1 * sx)), col = min(W - 1u, (uint32_t)((float)(c % G) * sy + u2 * sy));
-        write_sampled_ray(poses, images, fx, fy, cx, cy, H, W, p, row * W + col, n, rays_o, rays_d, gt, inds_out);
+        write_sampled_ray<RGBA>(poses, images, fx, fy, cx, cy, H, W, p, row * W + col, n, rays_o, rays_d, gt, inds_out, bg_base, bg_out);
     }
     if (pose_out != nullptr && tid == 0u) pose_out[0] = (int32_t)p;
 }
@@ -1618,33 +1654,78 @@ NSIG_EXPORT int rm_eval_compact(uint32_t *ctl, uint32_t N, uint32_t max_steps, c
     return check_launch("rm_eval_compact");
 }
 
+// rg_sample_rays / rg_sample_rays_rgba: one body, the store's channel count as the kernel's template argument
+template <bool RGBA>
+static int sample_rays(const char *name, const float *poses, uint32_t P, const float *images, float fx, float fy, float cx, float cy, uint32_t H, uint32_t W, uint32_t N,
+                       const int32_t *step_counter, uint32_t stride, uint32_t offset, uint64_t seed, float *rays_o, float *rays_d, float *gt, int64_t *inds_out,
+                       int32_t *pose_out, float *bg_out, nsig_stream_t stream) {
+    if (N == 0) return NSIG_OK;
+    NSIG_REQUIRE(poses && rays_o && rays_d && (!RGBA || (images && bg_out)), "%s: null pointer", name);
+    NSIG_REQUIRE(P > 0 && H > 0 && W > 0 && fx != 0.0f && fy != 0.0f, "%s: empty pose store, bad image size or focal length", name);
+    NSIG_REQUIRE(gt == nullptr || images != nullptr, "%s: ground truth requested without an image store", name);
+    NSIG_REQUIRE((uint64_t)H * W < (1ull << 32), "%s: image too large", name);
+    NSIG_REQUIRE(!RGBA || (reinterpret_cast<uintptr_t>(images) & 15u) == 0, "%s: the RGBA store must be 16-byte aligned", name);
+    k_sample_rays<RGBA><<<ceil_div(N, 256u), 256, 0, as_stream(stream)>>>(poses, P, images, fx, fy, cx, cy, H, W, N, step_counter, stride, offset, (uint32_t)seed,
+                                                                          (uint32_t)(seed >> 32), rays_o, rays_d, gt, inds_out, pose_out, bg_out);
+    return check_launch(name);
+}
+
 NSIG_EXPORT int rg_sample_rays(const float *poses, uint32_t P, const float *images, float fx, float fy, float cx, float cy, uint32_t H, uint32_t W,
                                uint32_t N, const int32_t *step_counter, uint32_t stride, uint32_t offset, uint64_t seed, float *rays_o, float *rays_d,
                                float *gt, int64_t *inds_out, int32_t *pose_out, nsig_stream_t stream) {
-    if (N == 0) return NSIG_OK;
-    NSIG_REQUIRE(poses && rays_o && rays_d, "rg_sample_rays: null pointer");
-    NSIG_REQUIRE(P > 0 && H > 0 && W > 0 && fx != 0.0f && fy != 0.0f, "rg_sample_rays: empty pose store, bad image size or focal length");
-    NSIG_REQUIRE(gt == nullptr || images != nullptr, "rg_sample_rays: ground truth requested without an image store");
-    NSIG_REQUIRE((uint64_t)H * W < (1ull << 32), "rg_sample_rays: image too large");
-    k_sample_rays<<<ceil_div(N, 256u), 256, 0, as_stream(stream)>>>(poses, P, images, fx, fy, cx, cy, H, W, N, step_counter, stride, offset, (uint32_t)seed,
-                                                                    (uint32_t)(seed >> 32), rays_o, rays_d, gt, inds_out, pose_out);
-    return check_launch("rg_sample_rays");
+    return sample_rays<false>("rg_sample_rays", poses, P, images, fx, fy, cx, cy, H, W, N, step_counter, stride, offset, seed, rays_o, rays_d, gt, inds_out, pose_out,
+                              nullptr, stream);
+}
+
+NSIG_EXPORT int rg_sample_rays_rgba(const float *poses, uint32_t P, const float *images, float fx, float fy, float cx, float cy, uint32_t H, uint32_t W,
+                                    uint32_t N, const int32_t *step_counter, uint32_t stride, uint32_t offset, uint64_t seed, float *rays_o, float *rays_d,
+                                    float *gt, float *bg_out, int64_t *inds_out, int32_t *pose_out, nsig_stream_t stream) {
+    return sample_rays<true>("rg_sample_rays_rgba", poses, P, images, fx, fy, cx, cy, H, W, N, step_counter, stride, offset, seed, rays_o, rays_d, gt, inds_out,
+                             pose_out, bg_out, stream);
+}
+
+template <bool RGBA>
+static int sample_rays_weighted(const char *name, const float *poses, uint32_t P, const float *images, float fx, float fy, float cx, float cy, uint32_t H, uint32_t W,
+                                uint32_t N, const int32_t *step_counter, uint32_t stride, uint32_t offset, uint64_t seed, const float *error_map, uint32_t grid,
+                                float *rays_o, float *rays_d, float *gt, int64_t *inds_out, int32_t *pose_out, int64_t *inds_coarse_out, float *keys_out,
+                                float *bg_out, nsig_stream_t stream) {
+    NSIG_REQUIRE(poses && rays_o && rays_d && error_map && inds_coarse_out && (!RGBA || (images && bg_out)), "%s: null pointer", name);
+    NSIG_REQUIRE(P > 0 && H > 0 && W > 0 && fx != 0.0f && fy != 0.0f, "%s: empty pose store, bad image size or focal length", name);
+    NSIG_REQUIRE(gt == nullptr || images != nullptr, "%s: ground truth requested without an image store", name);
+    NSIG_REQUIRE((uint64_t)H * W < (1ull << 32), "%s: image too large", name);
+    NSIG_REQUIRE(!RGBA || (reinterpret_cast<uintptr_t>(images) & 15u) == 0, "%s: the RGBA store must be 16-byte aligned", name);
+    NSIG_REQUIRE(grid >= 1 && grid <= kMaxErrorGrid, "%s: grid %u out of range (1..%u)", name, grid, kMaxErrorGrid);
+    NSIG_REQUIRE(N >= 1 && N <= grid * grid, "%s: N %u out of range (1..grid * grid = %u: a draw without replacement)", name, N, grid * grid);
+    k_sample_rays_weighted<RGBA><<<1, kWeightedThreads, 0, as_stream(stream)>>>(poses, P, images, fx, fy, cx, cy, H, W, N, step_counter, stride, offset, (uint32_t)seed,
+                                                                                (uint32_t)(seed >> 32), error_map, grid, rays_o, rays_d, gt, inds_out, pose_out,
+                                                                                inds_coarse_out, keys_out, bg_out);
+    return check_launch(name);
 }
 
 NSIG_EXPORT int rg_sample_rays_weighted(const float *poses, uint32_t P, const float *images, float fx, float fy, float cx, float cy, uint32_t H, uint32_t W,
                                         uint32_t N, const int32_t *step_counter, uint32_t stride, uint32_t offset, uint64_t seed, const float *error_map, uint32_t grid,
                                         float *rays_o, float *rays_d, float *gt, int64_t *inds_out, int32_t *pose_out, int64_t *inds_coarse_out, float *keys_out,
                                         nsig_stream_t stream) {
-    NSIG_REQUIRE(poses && rays_o && rays_d && error_map && inds_coarse_out, "rg_sample_rays_weighted: null pointer");
-    NSIG_REQUIRE(P > 0 && H > 0 && W > 0 && fx != 0.0f && fy != 0.0f, "rg_sample_rays_weighted: empty pose store, bad image size or focal length");
-    NSIG_REQUIRE(gt == nullptr || images != nullptr, "rg_sample_rays_weighted: ground truth requested without an image store");
-    NSIG_REQUIRE((uint64_t)H * W < (1ull << 32), "rg_sample_rays_weighted: image too large");
-    NSIG_REQUIRE(grid >= 1 && grid <= kMaxErrorGrid, "rg_sample_rays_weighted: grid %u out of range (1..%u)", grid, kMaxErrorGrid);
-    NSIG_REQUIRE(N >= 1 && N <= grid * grid, "rg_sample_rays_weighted: N %u out of range (1..grid * grid = %u: a draw without replacement)", N, grid * grid);
-    k_sample_rays_weighted<<<1, kWeightedThreads, 0, as_stream(stream)>>>(poses, P, images, fx, fy, cx, cy, H, W, N, step_counter, stride, offset, (uint32_t)seed,
-                                                                          (uint32_t)(seed >> 32), error_map, grid, rays_o, rays_d, gt, inds_out, pose_out,
-                                                                          inds_coarse_out, keys_out);
-    return check_launch("rg_sample_rays_weighted");
+    return sample_rays_weighted<false>("rg_sample_rays_weighted", poses, P, images, fx, fy, cx, cy, H, W, N, step_counter, stride, offset, seed, error_map, grid, rays_o,
+                                       rays_d, gt, inds_out, pose_out, inds_coarse_out, keys_out, nullptr, stream);
+}
+
+NSIG_EXPORT int rg_sample_rays_weighted_rgba(const float *poses, uint32_t P, const float *images, float fx, float fy, float cx, float cy, uint32_t H, uint32_t W,
+                                             uint32_t N, const int32_t *step_counter, uint32_t stride, uint32_t offset, uint64_t seed, const float *error_map,
+                                             uint32_t grid, float *rays_o, float *rays_d, float *gt, float *bg_out, int64_t *inds_out, int32_t *pose_out,
+                                             int64_t *inds_coarse_out, float *keys_out, nsig_stream_t stream) {
+    return sample_rays_weighted<true>("rg_sample_rays_weighted_rgba", poses, P, images, fx, fy, cx, cy, H, W, N, step_counter, stride, offset, seed, error_map, grid,
+                                      rays_o, rays_d, gt, inds_out, pose_out, inds_coarse_out, keys_out, bg_out, stream);
+}
+
+NSIG_EXPORT int rg_blend_random_background(const float *rgba, uint32_t N, const int32_t *step_counter, uint64_t seed, float *bg_out, float *gt_out,
+                                           nsig_stream_t stream) {
+    if (N == 0) return NSIG_OK;
+    NSIG_REQUIRE(rgba && bg_out && gt_out, "rg_blend_random_background: null pointer");
+    NSIG_REQUIRE((reinterpret_cast<uintptr_t>(rgba) & 15u) == 0, "rg_blend_random_background: rgba must be 16-byte aligned");
+    k_blend_random_background<<<ceil_div(N, 256u), 256, 0, as_stream(stream)>>>(reinterpret_cast<const float4 *>(rgba), N, step_counter, (uint32_t)seed,
+                                                                                (uint32_t)(seed >> 32), bg_out, gt_out);
+    return check_launch("rg_blend_random_background");
 }
 
 NSIG_EXPORT int rg_error_map_update(float *error_map, uint32_t P, uint32_t grid, const int32_t *pose_dev, const int64_t *inds_coarse, const float *pred,

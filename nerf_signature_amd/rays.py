@@ -62,7 +62,10 @@ class DeviceRaySampler:
     and ground-truth colours -- into caller-owned buffers, with `step` read from a device counter.  Nothing in the call depends on a
     host value, so trainer.GraphedWatermarkLoop captures it at the head of its step (`content_sampler=`): the per-step hand-over of
     rays costs one 5 us launch inside the graph instead of a randint, a ray kernel, a gather and three copies between two replays.
-    error_map=: the pixels are drawn from a per-image map of recent errors instead (see __init__)."""
+    error_map=: the pixels are drawn from a per-image map of recent errors instead (see __init__).
+    RGBA images [P,H*W,4] (the Blender scenes): `channels` is 4, and every draw also writes one random background colour per ray (`bg`) and hands out the
+    ground truth blended against it, gt = rgb * a + bg * (1 - a) (the reference's stage-1 train_step, nerf/utils.py:498-507) -- in the same launch
+    (rg_sample_rays_rgba / rg_sample_rays_weighted_rgba)."""
 
     def __init__(self, poses, images, intrinsics, H, W, n_rays, stride=1, offset=0, seed=0, error_map=False, error_grid=128):
         """error_map: the reference's --error_map loader (nerf/provider.py:234-238,300-321; nerf/utils.py:105-114,534-556) on the device.  True allocates a
@@ -73,7 +76,10 @@ class DeviceRaySampler:
         if not poses.is_cuda:
             raise ValueError("DeviceRaySampler: poses must be on the GPU")
         self.poses = poses.contiguous().float()
-        self.images = None if images is None else images.contiguous().float().view(self.poses.shape[0], H * W, 3)
+        if images is not None and images.shape[-1] not in (3, 4):
+            raise ValueError(f"DeviceRaySampler: images must be RGB or RGBA, not {images.shape[-1]} channels")
+        self.channels = 3 if images is None else int(images.shape[-1])
+        self.images = None if images is None else images.contiguous().float().view(self.poses.shape[0], H * W, self.channels)
         self.intr = tuple(float(v) for v in intrinsics)
         self.H, self.W, self.n_rays, self.stride, self.offset, self.seed = int(H), int(W), int(n_rays), int(stride), int(offset), int(seed)
         self.error_map, self.error_grid = None, int(error_grid)
@@ -93,10 +99,16 @@ class DeviceRaySampler:
             self.pose_word = torch.zeros(1, dtype=torch.int32, device=self.poses.device)                  # ... and its pose
 
     @torch.no_grad()
-    def sample_into(self, step_counter, rays_o, rays_d, gt=None, inds_out=None, pose_out=None, keys_out=None):
+    def sample_into(self, step_counter, rays_o, rays_d, gt=None, inds_out=None, pose_out=None, keys_out=None, bg=None):
         """step_counter: int32 device tensor [1] (or None = step 0).  rays_o / rays_d / gt: float32 buffers of n_rays * 3 elements.
-        keys_out (map only): float32 [error_grid^2], every cell's key of the race."""
-        for t in (rays_o, rays_d, gt):
+        keys_out (map only): float32 [error_grid^2], every cell's key of the race.  bg (an RGBA store only, and required there): float32 buffer of
+        n_rays * 3 elements for the rays' background colours; gt is then the blend against them."""
+        if self.channels == 4 and bg is None:
+            raise ValueError("DeviceRaySampler: an RGBA store draws a background colour per ray: pass bg=")
+        if self.channels != 4 and bg is not None:
+            raise ValueError("DeviceRaySampler: bg= belongs to an RGBA store (this one holds RGB)")
+        rgba = ("_rgba", (nv.ptr(bg),)) if self.channels == 4 else ("", ())
+        for t in (rays_o, rays_d, gt, bg):
             if t is not None and (t.numel() != self.n_rays * 3 or t.dtype != torch.float32):
                 raise ValueError(f"DeviceRaySampler: buffers must hold {self.n_rays} x 3 float32 values")
         if gt is not None and self.images is None:
@@ -105,16 +117,16 @@ class DeviceRaySampler:
         if self.error_map is not None:
             if keys_out is not None and (keys_out.numel() != self.error_grid ** 2 or keys_out.dtype != torch.float32):
                 raise ValueError(f"DeviceRaySampler: keys_out must hold {self.error_grid ** 2} float32 values")
-            nv.call("rg_sample_rays_weighted", nv.ptr(self.poses), self.poses.shape[0], nv.ptr(self.images), fx, fy, cx, cy, self.H, self.W, self.n_rays,
+            nv.call("rg_sample_rays_weighted" + rgba[0], nv.ptr(self.poses), self.poses.shape[0], nv.ptr(self.images), fx, fy, cx, cy, self.H, self.W, self.n_rays,
                     nv.ptr(step_counter), self.stride, self.offset, self.seed, nv.ptr(self.error_map), self.error_grid, nv.ptr(rays_o), nv.ptr(rays_d), nv.ptr(gt),
-                    nv.ptr(inds_out), nv.ptr(self.pose_word), nv.ptr(self.inds_coarse), nv.ptr(keys_out), nv.stream())
+                    *rgba[1], nv.ptr(inds_out), nv.ptr(self.pose_word), nv.ptr(self.inds_coarse), nv.ptr(keys_out), nv.stream())
             if pose_out is not None:
                 pose_out.copy_(self.pose_word)
             return
         if keys_out is not None:
             raise ValueError("DeviceRaySampler: keys_out belongs to the error-map draw")
-        nv.call("rg_sample_rays", nv.ptr(self.poses), self.poses.shape[0], nv.ptr(self.images), fx, fy, cx, cy, self.H, self.W, self.n_rays,
-                nv.ptr(step_counter), self.stride, self.offset, self.seed, nv.ptr(rays_o), nv.ptr(rays_d), nv.ptr(gt), nv.ptr(inds_out), nv.ptr(pose_out),
+        nv.call("rg_sample_rays" + rgba[0], nv.ptr(self.poses), self.poses.shape[0], nv.ptr(self.images), fx, fy, cx, cy, self.H, self.W, self.n_rays,
+                nv.ptr(step_counter), self.stride, self.offset, self.seed, nv.ptr(rays_o), nv.ptr(rays_d), nv.ptr(gt), *rgba[1], nv.ptr(inds_out), nv.ptr(pose_out),
                 nv.stream())
 
     @torch.no_grad()

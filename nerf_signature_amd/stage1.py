@@ -243,14 +243,38 @@ class CleanNeRFNetwork(NeRFRenderer):
 
 
 def train_step(model, data, render_kwargs):
-    """nerf/utils.py:469-517 for RGB ground truth: render with perturbed samples, MSE.  Returns (pred_rgb, loss)."""
+    """nerf/utils.py:469-517: render with perturbed samples, MSE.  Returns (pred_rgb, loss).
+    RGBA ground truth (:498-507): one random background colour per pixel -- data['bg_color'] [.., 3] where the caller fixes the draw, else torch.rand_like --
+    is blended under the ground truth and handed to the render; data['images'] is left as it was."""
     images = data["images"]
-    if images.shape[-1] != 3:
-        raise NotImplementedError("stage-1 train_step: RGB ground truth (the RGBA branch blends with a random background, utils.py:489-498)")
-    out = model.render(data["rays_o"], data["rays_d"], None, staged=False, bg_color=1, perturb=data.get("perturb", True),
+    C = images.shape[-1]
+    if C not in (3, 4):
+        raise ValueError(f"stage-1 train_step: ground truth with 3 or 4 channels, not {C}")
+    if C == 3 or model.bg_radius > 0:
+        bg_color = 1
+    else:
+        bg_color = data.get("bg_color")
+        if bg_color is None:
+            bg_color = torch.rand_like(images[..., :3])
+    gt_rgb = images if C == 3 else images[..., :3] * images[..., 3:] + bg_color * (1 - images[..., 3:])
+    out = model.render(data["rays_o"], data["rays_d"], None, staged=False, bg_color=bg_color, perturb=data.get("perturb", True),
                        force_all_rays=data.get("force_all_rays", False), **render_kwargs)
-    loss = ((out["image"] - images) ** 2).mean(-1).mean()
+    loss = ((out["image"] - gt_rgb) ** 2).mean(-1).mean()
     return out["image"], loss
+
+
+@torch.no_grad()
+def eval_step(model, data, render_kwargs):
+    """nerf/utils.py:567-591: a whole view against a white background (RGBA ground truth blended onto white), staged, unperturbed.  data['images'] [B,H,W,3|4].
+    Returns (pred_rgb [B,H,W,3], pred_depth [B,H,W], gt_rgb, loss) -- what metrics.py scores."""
+    images = data["images"]
+    B, H, W, C = images.shape
+    bg_color = 1
+    gt_rgb = images[..., :3] * images[..., 3:] + bg_color * (1 - images[..., 3:]) if C == 4 else images
+    out = model.render(data["rays_o"], data["rays_d"], None, staged=True, bg_color=bg_color, perturb=False, **render_kwargs)
+    pred_rgb, pred_depth = out["image"].reshape(B, H, W, 3), out["depth"].reshape(B, H, W)
+    loss = ((pred_rgb - gt_rgb) ** 2).mean()
+    return pred_rgb, pred_depth, gt_rgb, loss
 
 
 class CleanLoop:
@@ -325,14 +349,18 @@ class GraphedCleanLoop:
     and the grid-refresh check grows the buffers and captures again when a step came within 10 % of them.
     sampler (rays.DeviceRaySampler): draws pose, pixels, rays and ground truth inside the graph from the step count (with error_map=: from its
     map of recent errors, which the step updates behind its loss); otherwise call
-    step(data) with 'rays_o', 'rays_d' [..,3] and 'images' [..,3] of `n_rays` rays (copied into the static buffers)."""
+    step(data) with 'rays_o', 'rays_d' [..,3] and 'images' [..,3] of `n_rays` rays (copied into the static buffers).
+    rgba: RGBA ground truth, trained as the reference trains it (train_step): every ray is composited against a background colour of its own, drawn afresh every
+    step as a function of (seed, step, ray), and its target is the stored pixel blended against that colour.  None: what the sampler stores; without a sampler
+    the caller says rgba=True and step(data) takes 'images' [..,4].  An RGBA sampler blends inside its own launch -- the captured step has the launches of the
+    RGB step; the data path spends one more (rg_blend_random_background) at the head of the step."""
 
     LOSS_RING = 1024
     PLAN_OVERLAP_MIN_ROWS = 600_000      # overlap_plan="auto": buffer capacity (rows) from which the scatter plan runs on its own stream (~400 k points per step)
 
     def __init__(self, model, optimizer, render_kwargs, n_rays, sampler=None, update_extra_interval=16, lr_lambda=None, headroom=0.5, perturb=True,
                  capacity=None, overlap_plan="auto", capture=True, seed=0, fused_backward=True, fused_composite=True, fused_table_adam=None, sparse_exchange=True,
-                 device_refresh=True, trace_dtype="f32", ema_decay=None):
+                 device_refresh=True, trace_dtype="f32", ema_decay=None, rgba=None):
         if not model.cuda_ray:
             raise ValueError("GraphedCleanLoop drives the occupancy-grid path (cuda_ray=True)")
         if model.density_scale != 1:
@@ -351,7 +379,15 @@ class GraphedCleanLoop:
         f32 = dict(dtype=torch.float32, device=dev)
         N = self.n_rays
         self.rays_o, self.rays_d, self.gt = (torch.zeros(N, 3, **f32) for _ in range(3))
-        self.bg = torch.ones(3, **f32)
+        stored = None if sampler is None else getattr(sampler, "channels", 3) == 4
+        if rgba is not None and stored is not None and bool(rgba) != stored:
+            raise ValueError(f"GraphedCleanLoop: rgba={rgba} with a sampler that stores {'RGBA' if stored else 'RGB'} images")
+        self.rgba = bool(stored if rgba is None else rgba)
+        # RGB: one constant colour (bg_stride 0).  RGBA: a colour per ray (bg_stride 3), rewritten at the head of every step, and -- data path -- the static copy
+        # of the batch's pixels the blend reads
+        self.bg = torch.zeros(N, 3, **f32) if self.rgba else torch.ones(3, **f32)
+        self.bg_stride = 3 if self.rgba else 0
+        self.rgba_px = torch.zeros(N, 4, **f32) if self.rgba and sampler is None else None
         self.ws, self.depth, self.depth_out = (torch.empty(N, **f32) for _ in range(3))
         self.image, self.image_out, self.g_image, self._g_image_books = (torch.empty(N, 3, **f32) for _ in range(4))      # (_g_image_books: what clean_loss writes when
         # it only keeps the books -- the same values as g_image)
@@ -426,8 +462,7 @@ class GraphedCleanLoop:
     def _forward_backward(self):
         m, tr = self.model, self.tr
         self._wg_joined = False
-        if self.sampler is not None:
-            self.sampler.sample_into(self.step_dev, self.rays_o, self.rays_d, self.gt)
+        self._draw_batch()
         rec = self.rec = self._march()
         rows = rec.counter                                     # [points, rays] int32: element 0 is the device row count
         xyzs, dirs, M, N = rec.xyzs, rec.dirs, self.capacity, self.n_rays
@@ -450,19 +485,19 @@ class GraphedCleanLoop:
             # row instead of three (same box: dense -1.7 %, sparse grid -1.3 %; with clean_loss beside the MLP backward on the plan's stream the extra fork / join of
             # the graph cost more than the launch saved: +3 %)
             nv.call("rm_composite_train_mse", nv.ptr(tr.sig), nv.ptr(tr.rgb), nv.ptr(rec.deltas), nv.ptr(rec.rays), M, N, self.T_thresh, nv.ptr(rec.nears),
-                    nv.ptr(rec.fars), nv.ptr(self.bg), 0, nv.ptr(self.gt), 3 * N, 1.0 / dp.world_size(), nv.ptr(self.ws), nv.ptr(self.depth), nv.ptr(self.image),
+                    nv.ptr(rec.fars), nv.ptr(self.bg), self.bg_stride, nv.ptr(self.gt), 3 * N, 1.0 / dp.world_size(), nv.ptr(self.ws), nv.ptr(self.depth), nv.ptr(self.image),
                     nv.ptr(self.image_out), nv.ptr(self.depth_out), nv.ptr(self.g_image), nv.ptr(self.g_sig), nv.ptr(self.g_rgb), s)
             nv.call("clean_loss", nv.ptr(self.image_out), nv.ptr(self.gt), 3 * N, 1.0 / dp.world_size(), nv.ptr(self.loss), nv.ptr(self._g_image_books), *books, s)
             self._update_error_map()
         else:
             nv.call("rm_composite_train_finish_fwd", nv.ptr(tr.sig), nv.ptr(tr.rgb), nv.ptr(rec.deltas), nv.ptr(rec.rays), M, N, self.T_thresh,
-                    nv.ptr(rec.nears), nv.ptr(rec.fars), nv.ptr(self.bg), 0, nv.ptr(self.ws), nv.ptr(self.depth), nv.ptr(self.image),
+                    nv.ptr(rec.nears), nv.ptr(rec.fars), nv.ptr(self.bg), self.bg_stride, nv.ptr(self.ws), nv.ptr(self.depth), nv.ptr(self.image),
                     nv.ptr(self.image_out), nv.ptr(self.depth_out), s)
             # the loss of the global batch is the mean over the ranks' losses: each rank seeds 1 / world, the exchange sums
             nv.call("clean_loss", nv.ptr(self.image_out), nv.ptr(self.gt), 3 * N, 1.0 / dp.world_size(), nv.ptr(self.loss), nv.ptr(self.g_image), *books, s)
             self._update_error_map()
             nv.call("rm_composite_train_finish_bwd", None, nv.ptr(self.g_image), nv.ptr(tr.sig), nv.ptr(tr.rgb), nv.ptr(rec.deltas), nv.ptr(rec.rays),
-                    nv.ptr(self.ws), nv.ptr(self.image), nv.ptr(self.bg), 0, M, N, self.T_thresh, 1, nv.ptr(self.g_sig), nv.ptr(self.g_rgb), s)
+                    nv.ptr(self.ws), nv.ptr(self.image), nv.ptr(self.bg), self.bg_stride, M, N, self.T_thresh, 1, nv.ptr(self.g_sig), nv.ptr(self.g_rgb), s)
         # two-launch route: the weight gradients (a streaming reduction) run beside the table scatter (store- and LDS-bound) on the plan's stream,
         # which has long finished the plan by then (stream order: plan, then the weight gradients); fused: they are done when the backward is
         _backward_trace(tr, self.g_sig, self.g_rgb, self.packed, self.g_sigma, self.g_color, rows=rows, wgrad_stream=self.plan_stream)
@@ -480,6 +515,14 @@ class GraphedCleanLoop:
         else:
             nv.call("hg_levels_scatter", nv.ptr(xyzs), M, nv.ptr(rows), float(m.bound), nv.ptr(tr.d_planes), tr.stride, nv.ptr(self.plan),
                     nv.ptr_array([self.g_tables[l] for l in range(16)]), s)
+
+    def _draw_batch(self):
+        """The head of a step: the sampler's draw (RGBA: with the rays' backgrounds and the blended ground truth), or -- RGBA batches handed to step(data) -- the
+        background draw and the blend of the static pixels.  Both read the step count on the device."""
+        if self.sampler is not None:
+            self.sampler.sample_into(self.step_dev, self.rays_o, self.rays_d, self.gt, **({"bg": self.bg} if self.rgba else {}))
+        elif self.rgba:
+            nv.call("rg_blend_random_background", nv.ptr(self.rgba_px), self.n_rays, nv.ptr(self.step_dev), self.seed, nv.ptr(self.bg), nv.ptr(self.gt), nv.stream())
 
     def _update_error_map(self):
         """A sampler that draws from an error map (rays.DeviceRaySampler(error_map=)): the drawn cells take this step's per-ray error, right behind the loss
@@ -596,8 +639,7 @@ class GraphedCleanLoop:
     def _size(self):
         """One synchronising march of the current rays: the point count the buffers have to hold (+ headroom)."""
         m = self.model
-        if self.sampler is not None:
-            self.sampler.sample_into(self.step_dev, self.rays_o, self.rays_d, self.gt)
+        self._draw_batch()
         n = int(m.march_ahead(self.rays_o, self.rays_d, self.dt_gamma, self.max_steps, perturb=False, capacity=128).counter[0])
         m.drop_marched()
         return padded_point_count(int(max(n, 4096) * (1.0 + self.headroom)))
@@ -712,10 +754,10 @@ class GraphedCleanLoop:
     def _set_batch(self, data):
         if self.sampler is not None:
             raise ValueError("GraphedCleanLoop: this loop draws its own batches (sampler=)")
-        for dst, key in ((self.rays_o, "rays_o"), (self.rays_d, "rays_d"), (self.gt, "images")):
+        for dst, key in ((self.rays_o, "rays_o"), (self.rays_d, "rays_d"), (self.rgba_px if self.rgba else self.gt, "images")):
             src = data[key]
-            if src.numel() != dst.numel():
-                raise ValueError(f"GraphedCleanLoop: '{key}' must hold {self.n_rays} x 3 values")
+            if src.numel() != dst.numel() or (dst is self.rgba_px and src.shape[-1] != 4):
+                raise ValueError(f"GraphedCleanLoop: '{key}' must hold {self.n_rays} x {dst.shape[-1]} values")
             dst.copy_(src.reshape(dst.shape), non_blocking=True)
 
     def overflowed(self):
