@@ -9,21 +9,9 @@
 // elements 4*C bytes apart, so every load is its own cache line and a read-modify loop would be a chain of exposed
 // L2 latencies: the workgroup (1024 threads) instead issues all of its loads back to back into registers
 // (<= 8 per thread, N*P <= 8192), reduces twice from registers, and stores; larger batches take the looping kernels.
-#include "common.h"
+#include "wave.h"
 
 namespace nsig {
-
-__device__ inline float block_sum(float v, float *scratch) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    __syncthreads();  // scratch reuse
-    if (lane == 0) scratch[wid] = v;
-    __syncthreads();
-    float t = 0.0f;
-    for (int w = 0; w < (int)(blockDim.x >> 6); ++w) t += scratch[w];
-    return t;
-}
 
 __device__ inline float gelu(float z) { return 0.5f * z * (1.0f + erff(z * 0.70710678118654752f)); }
 __device__ inline float gelu_grad(float z) {

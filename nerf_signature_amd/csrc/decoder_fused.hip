@@ -26,7 +26,7 @@
 #include <algorithm>
 #include <cstring>
 
-#include "common.h"
+#include "wave.h"
 
 namespace nsig {
 
@@ -148,13 +148,8 @@ __device__ inline float half_sum(float v) {   // sum over the 32 lanes that shar
     for (int d = 16; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
     return v;
 }
-__device__ inline float wave_sum64(float v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
-    return v;
-}
 __device__ inline float block_sum256(float v, float *scratch) {   // scratch: 4 floats
-    v = wave_sum64(v);
+    v = wave_sum(v);
     __syncthreads();
     if ((threadIdx.x & 63) == 0) scratch[threadIdx.x >> 6] = v;
     __syncthreads();
@@ -907,8 +902,8 @@ __global__ void __launch_bounds__(256) k_dec_l8_fwd(DecParams prm, DecWs ws, Dec
     __syncthreads();
     if (t < 64) {   // one wave: the pair's (sum, M2)
         const uint32_t n = pair_count(pair, g.P);
-        const float v = t < n ? s_x[t] : 0.0f, s = wave_sum64(v);
-        const float d = t < n ? v - s / (float)n : 0.0f, m2 = wave_sum64(d * d);
+        const float v = t < n ? s_x[t] : 0.0f, s = wave_sum(v);
+        const float d = t < n ? v - s / (float)n : 0.0f, m2 = wave_sum(d * d);
         if (t == 0) {
             ws.stat[8][((size_t)pair * g.B + im) * 2] = s;
             ws.stat[8][((size_t)pair * g.B + im) * 2 + 1] = m2;
@@ -974,7 +969,7 @@ __global__ void __launch_bounds__(256) k_dec_head_bwd(const float *__restrict__ 
     for (uint32_t pair = t >> 6; pair < g.npair; pair += 4) {   // one wave per pair
         const uint32_t lane = t & 63, q = 64 * pair + lane;
         const float dz = q < g.P ? s_dz[q] : 0.0f, xh = q < g.P ? s_xh[q] : 0.0f;
-        const float s1 = wave_sum64(dz), s2 = wave_sum64(dz * xh);
+        const float s1 = wave_sum(dz), s2 = wave_sum(dz * xh);
         if (lane == 0) {
             ws.bsum[8][((size_t)pair * g.B + im) * 2] = s1;
             ws.bsum[8][((size_t)pair * g.B + im) * 2 + 1] = s2;

@@ -30,6 +30,7 @@
 #include <mutex>
 #include <unordered_set>
 #include "fieldmlp.h"
+#include "wave.h"
 
 #include <stdlib.h>
 
@@ -751,8 +752,7 @@ __global__ void __launch_bounds__(256) k_field_bwd(const float *__restrict__ xyz
         }
     }
     if (planned) {   // the owners' fixed-point scale comes from the launch's largest |gradient|
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) gbits = max(gbits, (uint32_t)__shfl_xor((int)gbits, d, 64));
+        gbits = wave_max(gbits);
         // 3072 waves finish together: atomics on one address serialise (~10 ns each), so only a wave that would raise the
         // maximum issues one -- after the first few, almost none does
         if (lane == 0 && gbits > __hip_atomic_load(&plan.hd->gmax_bits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(&plan.hd->gmax_bits, gbits);
@@ -895,8 +895,7 @@ __device__ inline void field_bwd_pipelined(const char *lds, int lane, const floa
     }
     if (have) store_prev();
     // the owners' fixed-point scale comes from the launch's largest |gradient|
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) gbits = max(gbits, (uint32_t)__shfl_xor((int)gbits, d, 64));
+    gbits = wave_max(gbits);
     if (lane == 0 && gbits > __hip_atomic_load(&plan.hd->gmax_bits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(&plan.hd->gmax_bits, gbits);
 }
 

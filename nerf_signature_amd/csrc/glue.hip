@@ -3,20 +3,9 @@
 // On this path a "tensor" is a few thousand rays, so every stock elementwise/reduction operator is a ~3 us launch and the
 // reference's op chains (renderer_wtmk.py:316-319: background mix and depth normalisation; utils_wtmk_disen.py:615-640:
 // MSE + BCE-with-logits + weighted sum, and their autograd backward) come to ~60 launches per step: 0.2 ms of a 1.8 ms step.
-#include "common.h"
+#include "wave.h"
 
 namespace nsig {
-
-__device__ inline float block_reduce_1024(float v, float *scratch) {   // scratch: 16 floats
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) scratch[threadIdx.x >> 6] = v;
-    __syncthreads();
-    float t = 0.0f;
-    for (int w = 0; w < (int)(blockDim.x >> 6); ++w) t += scratch[w];
-    return t;
-}
 
 // renderer_wtmk.py:316-319 / 369-372.
 __global__ void __launch_bounds__(256) k_finish_fwd(const float *__restrict__ image, const float *__restrict__ depth, const float *__restrict__ ws,
@@ -63,8 +52,8 @@ __global__ void __launch_bounds__(1024) k_wm_loss_fwd(const float *__restrict__ 
         sw += (1.0f - y) * x + fmaxf(-x, 0.0f) + log1pf(expf(-fabsf(x)));
         d_decoded[i] = kw * (1.0f / (1.0f + expf(-x)) - y);
     }
-    si = block_reduce_1024(si, scratch);
-    sw = block_reduce_1024(sw, scratch);
+    si = block_sum(si, scratch);
+    sw = block_sum(sw, scratch);
     if (threadIdx.x == 0) {
         const float li = si / (float)n_content, lw = sw / (float)D;
         losses[0] = li;

@@ -15,7 +15,7 @@
 //         -> rg_refresh_finish: k_grid_ema (per-workgroup partial sums in double, fixed order) -> k_grid_stats (one workgroup: the mean, the refresh
 //            count, the mean sample count of the window from the loop's ring) -> k_packbits_dev (threshold read from device memory).
 // Everything is a pure function of (grid, parameters, seed, refresh count): two runs leave the same bits (tests/test_gpu_stage1.py, test_gpu_grid.py).
-#include "common.h"
+#include "wave.h"
 
 namespace nsig {
 
@@ -37,20 +37,6 @@ __device__ inline float rg_u01(uint64_t bits) { return (float)(uint32_t)(bits >>
 // prefix inside each workgroup's cells, on top of its offset.  The first launch also clears the counting sort's row bins.
 constexpr uint32_t kOccThreads = 1024, kOccPerThread = 4, kOccCells = kOccThreads * kOccPerThread;
 
-__device__ inline int32_t occ_block_exclusive(int32_t mine, int32_t *wave_tot) {      // exclusive prefix of `mine` over the 1024 threads of a workgroup; wave_tot[16]
-    int32_t incl = mine;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int32_t up = __shfl_up(incl, d, 64);
-        if ((int)(threadIdx.x & 63u) >= d) incl += up;
-    }
-    if ((threadIdx.x & 63u) == 63u) wave_tot[threadIdx.x >> 6] = incl;
-    __syncthreads();
-    int32_t before = 0;
-    for (uint32_t w = 0; w < (threadIdx.x >> 6); ++w) before += wave_tot[w];
-    return before + incl - mine;
-}
-
 __global__ void __launch_bounds__(kOccThreads) k_occ_count(const float *__restrict__ grid, uint32_t cells, int32_t *__restrict__ block_sums, int32_t *__restrict__ bins,
                                                           uint32_t n_bins) {
     __shared__ int32_t wave_tot[16];
@@ -63,7 +49,7 @@ __global__ void __launch_bounds__(kOccThreads) k_occ_count(const float *__restri
     } else {
         for (uint32_t u = 0; u < kOccPerThread; ++u) c += (first + u < cells && grid[first + u] > 0.0f);
     }
-    const int32_t before = occ_block_exclusive(c, wave_tot);
+    const int32_t before = block_exclusive_sum<16>(c, wave_tot);
     if (threadIdx.x == kOccThreads - 1u) block_sums[blockIdx.x] = before + c;
 }
 
@@ -74,7 +60,7 @@ __global__ void __launch_bounds__(kOccThreads) k_occ_prefix(const float *__restr
     int32_t f[kOccPerThread];
 #pragma unroll
     for (uint32_t u = 0; u < kOccPerThread; ++u) f[u] = (first + u < cells && grid[first + u] > 0.0f) ? 1 : 0;
-    int32_t run = occ_block_exclusive(f[0] + f[1] + f[2] + f[3], wave_tot) + block_offsets[blockIdx.x];
+    int32_t run = block_exclusive_sum<16>(f[0] + f[1] + f[2] + f[3], wave_tot) + block_offsets[blockIdx.x];
 #pragma unroll
     for (uint32_t u = 0; u < kOccPerThread; ++u) {
         run += f[u];
@@ -197,19 +183,10 @@ __global__ void __launch_bounds__(1024) k_refresh_bins(int32_t *__restrict__ bin
     for (uint32_t base = 0; base < n_bins; base += 1024u) {      // (uniform trip count)
         const uint32_t i = base + threadIdx.x;
         const int32_t v = i < n_bins ? bins[i] : 0;
-        int32_t incl = v;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const int32_t up = __shfl_up(incl, d, 64);
-            if ((int)(threadIdx.x & 63u) >= d) incl += up;
-        }
-        if ((threadIdx.x & 63u) == 63u) wave_tot[threadIdx.x >> 6] = incl;
+        const int32_t before = carry + block_exclusive_sum<16>(v, wave_tot);
+        if (i < n_bins) bins[i] = before;
         __syncthreads();
-        int32_t before = carry;
-        for (uint32_t w = 0; w < (threadIdx.x >> 6); ++w) before += wave_tot[w];
-        if (i < n_bins) bins[i] = before + incl - v;
-        __syncthreads();
-        if (threadIdx.x == 1023u) carry = before + incl;
+        if (threadIdx.x == 1023u) carry = before + v;
         __syncthreads();
     }
 }
@@ -278,8 +255,7 @@ __global__ void __launch_bounds__(kEmaThreads) k_grid_ema(float *__restrict__ gr
             s += (double)fmaxf(g, 0.0f);
         }
     }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) s += __shfl_xor(s, d, 64);
+    s = wave_sum(s);
     if ((threadIdx.x & 63u) == 0) part[threadIdx.x >> 6] = s;
     __syncthreads();
     if (threadIdx.x == 0) {

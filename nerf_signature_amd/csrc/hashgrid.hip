@@ -13,6 +13,7 @@
 //       scatters once into G and a fan-out pass copies G into the D gradient tensors autograd expects.
 #include <cstdlib>
 #include "hashgrid.h"
+#include "wave.h"
 
 namespace nsig {
 
@@ -275,8 +276,7 @@ __global__ void __launch_bounds__(kBinThreads) k_bin_count(const float *__restri
             gb = max(gb, __float_as_uint(gabs));   // non-negative floats (and +inf, NaN) order like their bit patterns
         }
     }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) gb = max(gb, (uint32_t)__shfl_xor((int)gb, d, 64));
+    gb = wave_max(gb);
     if ((threadIdx.x & 63) == 0 && gb) atomicMax(&gm, gb);
     __syncthreads();
     if (threadIdx.x < kBinSlices) hd->wg[blockIdx.x][threadIdx.x] = h[threadIdx.x];
@@ -411,12 +411,7 @@ __global__ void __launch_bounds__(kBinThreads) k_plan_dest(const float *__restri
             uint32_t t = 0, b = 0;
 #pragma unroll
             for (int k = 0; k < 16; ++k) { t += seg_tot[k][threadIdx.x]; b += seg_before[k][threadIdx.x]; }
-            uint32_t incl = t;
-#pragma unroll
-            for (int d = 1; d < 64; d <<= 1) {
-                const uint32_t v = (uint32_t)__shfl_up((int)incl, d, 64);
-                if ((int)threadIdx.x >= d) incl += v;
-            }
+            const uint32_t incl = wave_prefix_sum(t, (int)threadIdx.x);
             running[threadIdx.x] = incl - t + b;
             if (blockIdx.x == 0) hd->counts[threadIdx.x] = t;
         }
@@ -538,12 +533,7 @@ __global__ void __launch_bounds__(kBinThreads) k_levels_scan(uint32_t M, const u
         uint32_t t = 0;
 #pragma unroll
         for (int k = 0; k < 16; ++k) t += seg[k][threadIdx.x];
-        uint32_t incl = t;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const uint32_t v = (uint32_t)__shfl_up((int)incl, d, 64);
-            if ((int)threadIdx.x >= d) incl += v;
-        }
+        const uint32_t incl = wave_prefix_sum(t, (int)threadIdx.x);
         start[threadIdx.x] = incl - t;
         pl.hd[level].counts[threadIdx.x] = t;
     }
@@ -675,12 +665,7 @@ __global__ void __launch_bounds__(kBinThreads) k_level_entries(const float *__re
     ENT_STAMP(3);      // barrier
     if (threadIdx.x < kBinSlices) {      // one wave: where each slice's run starts in the staging area
         const uint32_t t = h[threadIdx.x];
-        uint32_t incl = t;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const uint32_t v = (uint32_t)__shfl_up((int)incl, d, 64);
-            if ((int)threadIdx.x >= d) incl += v;
-        }
+        const uint32_t incl = wave_prefix_sum(t, (int)threadIdx.x);
         base[threadIdx.x] = incl - t;
         if (threadIdx.x == kBinSlices - 1) base[kBinSlices] = incl;
     }
@@ -834,9 +819,7 @@ __global__ void __launch_bounds__(1024) k_scatter_binned(const BinHeader *__rest
     // and the chunk maxima REQUESTED, then the accumulators cleared and the maximum reduced while those are on their way.
     static_assert(kBinSlices == 64, "one slice count per lane");
     const uint32_t lane = threadIdx.x & 63u, cnt = hd->counts[lane];
-    uint32_t before = lane < slice ? cnt : 0u;
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) before += (uint32_t)__shfl_xor((int)before, d, 64);
+    const uint32_t before = wave_sum(lane < slice ? cnt : 0u);
     const uint32_t start = (uint32_t)__builtin_amdgcn_readfirstlane((int)before);
     const uint32_t n = (uint32_t)__builtin_amdgcn_readfirstlane(__shfl((int)cnt, (int)slice, 64)), chunk = ceil_div(n, replicas);
     const uint32_t beg = min(n, replica * chunk), end = min(n, beg + chunk);
@@ -866,8 +849,7 @@ __global__ void __launch_bounds__(1024) k_scatter_binned(const BinHeader *__rest
         for (uint32_t i = threadIdx.x; i < 2u * kBinRows; i += blockDim.x) acc64[i] = 0ull;
     __syncthreads();
     if (set_max != nullptr) {
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) mx = max(mx, (uint32_t)__shfl_xor((int)mx, d, 64));
+        mx = wave_max(mx);
         if (lane == 0 && mx) atomicMax(&smax, mx);
         __syncthreads();
         gb = smax;

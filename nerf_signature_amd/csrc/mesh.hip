@@ -7,7 +7,7 @@
 //   triangles: by cell in C order, then in table order (mc_tables.h); int32 triples of vertex ids.
 // Four launches: count (per-node case + edge bits, per-block totals) -> scan of the block totals (one workgroup) -> vertex emit (per-node
 // vertex base, in-block ballot offsets) -> triangle emit (ids through the vertex bases of the nodes that own the cell's edges).
-#include "common.h"
+#include "wave.h"
 #include "mc_tables.h"
 
 namespace nsig {
@@ -86,11 +86,8 @@ __global__ void __launch_bounds__(kMcThreads) k_mc_count(const float *__restrict
         nv += (uint32_t)__popc(bits);
         nt += mc_tri_count[cas];
     }
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) {
-        nv += __shfl_xor(nv, o, 64);
-        nt += __shfl_xor(nt, o, 64);
-    }
+    nv = wave_sum(nv);
+    nt = wave_sum(nt);
     if (lane == 0) {
         red[0][wid] = nv;
         red[1][wid] = nt;
@@ -109,32 +106,18 @@ __global__ void __launch_bounds__(kMcThreads) k_mc_count(const float *__restrict
 }
 
 // Pass 2: exclusive prefix sums of the 2 nb workgroup totals, in place; totals[0] = V, totals[1] = T.  One 1024-thread workgroup, each
-// thread a contiguous run of entries (the k_march_scan pattern), one array after the other.
+// thread a contiguous run of entries, the runs' sums through block_exclusive_sum (as k_march_scan), one array after the other.
 __global__ void __launch_bounds__(1024) k_mc_scan(uint32_t *__restrict__ sums, uint32_t nb, uint32_t *__restrict__ totals) {
     __shared__ uint32_t wave_tot[16];
-    const uint32_t tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    const uint32_t tid = threadIdx.x;
     const uint32_t chunk = ceil_div(nb, 1024u);
     const uint32_t beg = min(nb, tid * chunk), end = min(nb, beg + chunk);
     for (uint32_t a = 0; a < 2; ++a) {
         uint32_t *s = sums + size_t(a) * nb;
         uint32_t sum = 0;
         for (uint32_t i = beg; i < end; ++i) sum += s[i];
-        uint32_t incl = sum;
-#pragma unroll
-        for (int dd = 1; dd < 64; dd <<= 1) {
-            const uint32_t v = __shfl_up(incl, dd, 64);
-            if ((int)lane >= dd) incl += v;
-        }
-        if (lane == 63) wave_tot[wid] = incl;
-        __syncthreads();
-        uint32_t base = 0, total = 0;
-#pragma unroll
-        for (int w = 0; w < 16; ++w) {
-            const uint32_t v = wave_tot[w];
-            if (w < (int)wid) base += v;
-            total += v;
-        }
-        uint32_t off = base + incl - sum;
+        uint32_t total;
+        uint32_t off = block_exclusive_sum<16>(sum, wave_tot, &total);
         for (uint32_t i = beg; i < end; ++i) {
             const uint32_t c = s[i];
             s[i] = off;

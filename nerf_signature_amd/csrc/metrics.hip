@@ -19,7 +19,7 @@
 // No atomics anywhere: the same inputs give the same bits.  pred and truth enter every expression symmetrically: swapping them changes no bit.
 #include <math.h>
 
-#include "common.h"
+#include "wave.h"
 
 namespace nsig {
 
@@ -63,8 +63,7 @@ static inline RangeScratch range_split(void *scratch, uint32_t B, uint64_t n) {
 // Sum over the workgroup in a fixed order (wave butterfly, then the waves in index order); the result is valid in thread 0.
 __device__ inline double block_sum(double v, double *red) {
     const uint32_t tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
+    v = wave_sum(v);
     if (lane == 0) red[wid] = v;
     __syncthreads();
     double s = 0.0;
@@ -78,8 +77,7 @@ __device__ inline double block_sum(double v, double *red) {
 
 __device__ inline float block_min(float v, float *red) {
     const uint32_t tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v = fminf(v, __shfl_xor(v, o, 64));
+    v = wave_min(v);
     if (lane == 0) red[wid] = v;
     __syncthreads();
     float s = v;

@@ -10,7 +10,7 @@
 //
 // Built with -ffp-contract=off: every fused multiply-add below is explicit, so the integer outputs
 // (sample counts) are reproducible bit-for-bit against the CPU oracle (see oracle/raymarch_ref.c).
-#include "common.h"
+#include "wave.h"
 
 #include <float.h>
 
@@ -288,13 +288,7 @@ __global__ __launch_bounds__(kWeightedThreads) void k_sample_rays_weighted(
             uint32_t cnt[4], mine = 0u;
 #pragma unroll
             for (uint32_t j = 0; j < 4u; ++j) { cnt[j] = bins[255u - (4u * lane + j)]; mine += cnt[j]; }
-            uint32_t run = mine;
-#pragma unroll
-            for (uint32_t d = 1; d < 64u; d <<= 1) {
-                const uint32_t v = __shfl_up(run, d);
-                if (lane >= d) run += v;
-            }
-            run -= mine;        // keys in the bins above this lane's
+            uint32_t run = wave_prefix_sum(mine, (int)lane) - mine;        // keys in the bins above this lane's
 #pragma unroll
             for (uint32_t j = 0; j < 4u; ++j) {
                 if (run < need && run + cnt[j] >= need) { found[0] = 255u - (4u * lane + j); found[1] = run; }
@@ -666,27 +660,13 @@ __global__ void __launch_bounds__(256) k_march_index(const float *__restrict__ r
 __global__ void __launch_bounds__(1024) k_march_scan(const int32_t *__restrict__ counts, uint32_t N,
                                                      int32_t *__restrict__ rays, int32_t *__restrict__ counter) {
     __shared__ int32_t wave_tot[16];
-    const uint32_t tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    const uint32_t tid = threadIdx.x;
     const uint32_t chunk = ceil_div(N, 1024u);
     const uint32_t beg = min(N, tid * chunk), end = min(N, beg + chunk);
     int32_t sum = 0;
     for (uint32_t i = beg; i < end; ++i) sum += counts[i];
-    int32_t incl = sum;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int32_t v = __shfl_up(incl, d, 64);
-        if ((int)lane >= d) incl += v;
-    }
-    if (lane == 63) wave_tot[wid] = incl;
-    __syncthreads();
-    int32_t base = 0, total = 0;
-#pragma unroll
-    for (int w = 0; w < 16; ++w) {
-        const int32_t v = wave_tot[w];
-        if (w < (int)wid) base += v;
-        total += v;
-    }
-    int32_t off = base + incl - sum;
+    int32_t total;
+    int32_t off = block_exclusive_sum<16>(sum, wave_tot, &total);
     for (uint32_t i = beg; i < end; ++i) {
         const int32_t c = counts[i];
         rays[3 * (size_t)i] = (int32_t)i;
@@ -711,8 +691,7 @@ __global__ void __launch_bounds__(1024) k_march_scan_sums(const int32_t *__restr
         const uint32_t i = base + tid + 1024u * u;
         s += i < N ? counts[i] : 0;
     }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) s += __shfl_xor(s, d, 64);
+    s = wave_sum(s);
     if (lane == 0) wave_tot[wid] = s;
     __syncthreads();
     if (tid == 0) {
@@ -733,8 +712,8 @@ __global__ void __launch_bounds__(1024) k_march_scan_apply(const int32_t *__rest
         all += v;
         if (b < blockIdx.x) before += v;
     }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) { before += __shfl_xor(before, d, 64); all += __shfl_xor(all, d, 64); }
+    before = wave_sum(before);
+    all = wave_sum(all);
     if (lane == 0) { wave_tot[wid] = before; part[wid] = all; }
     __syncthreads();
     before = 0; all = 0;
@@ -749,18 +728,7 @@ __global__ void __launch_bounds__(1024) k_march_scan_apply(const int32_t *__rest
         c[u] = first + u < N ? counts[first + u] : 0;
         sum += c[u];
     }
-    int32_t incl = sum;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int32_t v = __shfl_up(incl, d, 64);
-        if ((int)lane >= d) incl += v;
-    }
-    if (lane == 63) wave_tot[wid] = incl;
-    __syncthreads();
-    int32_t off = before + incl - sum;
-#pragma unroll
-    for (int w = 0; w < 16; ++w)
-        if (w < (int)wid) off += wave_tot[w];
+    int32_t off = before + block_exclusive_sum<16>(sum, wave_tot);
 #pragma unroll
     for (uint32_t u = 0; u < 4; ++u) {
         const uint32_t i = first + u;
@@ -774,6 +742,55 @@ __global__ void __launch_bounds__(1024) k_march_scan_apply(const int32_t *__rest
     if (blockIdx.x == 0 && tid == 0) { counter[0] = all; counter[1] = (int32_t)N; }
 }
 
+// Where a ray's samples start and how many it has: the (id, offset, count) table in global memory, or the exclusive prefix sums [N + 1] in LDS.
+struct RayTable {
+    const int32_t *__restrict__ rays;
+    __device__ uint32_t offset(uint32_t i) const { return (uint32_t)rays[3 * (size_t)i + 1]; }
+    __device__ uint32_t count(uint32_t i) const { return (uint32_t)rays[3 * (size_t)i + 2]; }
+};
+struct LdsOffsets {
+    const int32_t *off;
+    __device__ uint32_t offset(uint32_t i) const { return (uint32_t)off[i]; }
+    __device__ uint32_t count(uint32_t i) const { return (uint32_t)off[i + 1] - (uint32_t)off[i]; }
+};
+
+// Output row m of the training march: its ray by binary search in the offsets, then the point, the direction and the two deltas; zeros for a row past `total`
+// or of a ray that does not fit.
+template <typename Offsets>
+__device__ __forceinline__ void write_sample_row(uint32_t m, uint32_t total, Offsets tab, const float *__restrict__ rays_o, const float *__restrict__ rays_d,
+                                                 const GridView &g, uint32_t max_steps, uint32_t N, uint32_t M, const float *__restrict__ nears,
+                                                 const float *__restrict__ noises, const float *__restrict__ t_rec, float *__restrict__ xyzs,
+                                                 float *__restrict__ dirs, float *__restrict__ deltas) {
+    float px = 0, py = 0, pz = 0, qx = 0, qy = 0, qz = 0, d0 = 0, d1 = 0;
+    if (m < total) {
+        uint32_t lo = 0, hi = N;      // last ray whose offset <= m (rays with no samples share their successor's offset)
+        while (hi - lo > 1) {
+            const uint32_t mid = (lo + hi) >> 1;
+            if (tab.offset(mid) <= m) lo = mid; else hi = mid;
+        }
+        const uint32_t off = tab.offset(lo), cnt = tab.count(lo);
+        if (off + cnt <= M) {  // raymarching.cu:416: a ray that does not fit writes nothing
+            const uint32_t s = m - off;
+            const float *rec = t_rec + (size_t)lo * max_steps;
+            const float t = rec[s];
+            const float3 rd = *reinterpret_cast<const float3 *>(rays_d + 3 * (size_t)lo), ro = *reinterpret_cast<const float3 *>(rays_o + 3 * (size_t)lo);
+            qx = rd.x; qy = rd.y; qz = rd.z;
+            px = clampf(fmaf(t, qx, ro.x), -g.bound, g.bound);
+            py = clampf(fmaf(t, qy, ro.y), -g.bound, g.bound);
+            pz = clampf(fmaf(t, qz, ro.z), -g.bound, g.bound);
+            d0 = step_len(g, t);
+            float last;
+            if (s == 0) last = start_param(g, nears[lo], noises ? noises[lo] : 0.0f);
+            else { const float tp = rec[s - 1]; last = tp + step_len(g, tp); }
+            d1 = (t + d0) - last;
+        }
+    }
+    // three stores per row instead of eight (12 + 12 + 8 bytes)
+    *reinterpret_cast<float3 *>(xyzs + 3 * (size_t)m) = make_float3(px, py, pz);
+    *reinterpret_cast<float3 *>(dirs + 3 * (size_t)m) = make_float3(qx, qy, qz);
+    *reinterpret_cast<float2 *>(deltas + 2 * (size_t)m) = make_float2(d0, d1);
+}
+
 // Training march, pass 3 (raymarching.cu:422-479 without the second walk): one lane per output row.
 __global__ void k_march_write(const float *__restrict__ rays_o, const float *__restrict__ rays_d, GridView g,
                               uint32_t max_steps, uint32_t N, uint32_t M, const float *__restrict__ nears,
@@ -781,37 +798,8 @@ __global__ void k_march_write(const float *__restrict__ rays_o, const float *__r
                               const int32_t *__restrict__ rays, const int32_t *__restrict__ counter,
                               float *__restrict__ xyzs, float *__restrict__ dirs, float *__restrict__ deltas) {
     const uint32_t total = (uint32_t)counter[0];
-    for (uint32_t m = blockIdx.x * blockDim.x + threadIdx.x; m < M; m += gridDim.x * blockDim.x) {
-        float px = 0, py = 0, pz = 0, qx = 0, qy = 0, qz = 0, d0 = 0, d1 = 0;
-        if (m < total) {
-            // last ray whose offset <= m (rays with no samples share their successor's offset)
-            uint32_t lo = 0, hi = N;
-            while (hi - lo > 1) {
-                const uint32_t mid = (lo + hi) >> 1;
-                if ((uint32_t)rays[3 * (size_t)mid + 1] <= m) lo = mid; else hi = mid;
-            }
-            const uint32_t off = (uint32_t)rays[3 * (size_t)lo + 1], cnt = (uint32_t)rays[3 * (size_t)lo + 2];
-            if (off + cnt <= M) {  // raymarching.cu:416: a ray that does not fit writes nothing
-                const uint32_t s = m - off;
-                const float *rec = t_rec + (size_t)lo * max_steps;
-                const float t = rec[s];
-                const float3 rd = *reinterpret_cast<const float3 *>(rays_d + 3 * (size_t)lo), ro = *reinterpret_cast<const float3 *>(rays_o + 3 * (size_t)lo);
-                qx = rd.x; qy = rd.y; qz = rd.z;
-                px = clampf(fmaf(t, qx, ro.x), -g.bound, g.bound);
-                py = clampf(fmaf(t, qy, ro.y), -g.bound, g.bound);
-                pz = clampf(fmaf(t, qz, ro.z), -g.bound, g.bound);
-                d0 = step_len(g, t);
-                float last;
-                if (s == 0) last = start_param(g, nears[lo], noises ? noises[lo] : 0.0f);
-                else { const float tp = rec[s - 1]; last = tp + step_len(g, tp); }
-                d1 = (t + d0) - last;
-            }
-        }
-        // three stores per row instead of eight (12 + 12 + 8 bytes)
-        *reinterpret_cast<float3 *>(xyzs + 3 * (size_t)m) = make_float3(px, py, pz);
-        *reinterpret_cast<float3 *>(dirs + 3 * (size_t)m) = make_float3(qx, qy, qz);
-        *reinterpret_cast<float2 *>(deltas + 2 * (size_t)m) = make_float2(d0, d1);
-    }
+    for (uint32_t m = blockIdx.x * blockDim.x + threadIdx.x; m < M; m += gridDim.x * blockDim.x)
+        write_sample_row(m, total, RayTable{rays}, rays_o, rays_d, g, max_steps, N, M, nears, noises, t_rec, xyzs, dirs, deltas);
 }
 
 // Passes 2 + 3 in ONE launch for ray counts whose offsets fit in LDS (the training step's 4096 / 4608 rays): every workgroup computes the
@@ -830,7 +818,7 @@ __global__ void __launch_bounds__(256) k_march_scan_write(const float *__restric
                                                           float *__restrict__ deltas) {
     extern __shared__ int32_t off[];      // [N + 1]: counts, then in place their exclusive prefix sums; off[N] = total
     __shared__ int32_t wave_tot[4];
-    const uint32_t tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    const uint32_t tid = threadIdx.x;
     {   // all of a thread's loads in flight together (one L2 round trip per batch of 16, not one per element): N <= 48 * 256
         constexpr uint32_t kBatchLoads = 16;
         for (uint32_t base = 0; base < N; base += 256u * kBatchLoads) {
@@ -852,18 +840,7 @@ __global__ void __launch_bounds__(256) k_march_scan_write(const float *__restric
     const uint32_t beg = min(N, tid * chunk), end = min(N, beg + chunk);
     int32_t sum = 0;
     for (uint32_t i = beg; i < end; ++i) sum += off[i];
-    int32_t incl = sum;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int32_t v = __shfl_up(incl, d, 64);
-        if ((int)lane >= d) incl += v;
-    }
-    if (lane == 63) wave_tot[wid] = incl;
-    __syncthreads();
-    int32_t run = incl - sum;
-#pragma unroll
-    for (int w = 0; w < 4; ++w)
-        if (w < (int)wid) run += wave_tot[w];
+    int32_t run = block_exclusive_sum<4>(sum, wave_tot);
     const bool first = blockIdx.x == 0;
     for (uint32_t i = beg; i < end; ++i) {
         const int32_t c = off[i];
@@ -881,35 +858,8 @@ __global__ void __launch_bounds__(256) k_march_scan_write(const float *__restric
     }
     __syncthreads();
     const uint32_t total = (uint32_t)off[N];
-    for (uint32_t m = blockIdx.x * blockDim.x + threadIdx.x; m < M; m += gridDim.x * blockDim.x) {
-        float px = 0, py = 0, pz = 0, qx = 0, qy = 0, qz = 0, d0 = 0, d1 = 0;
-        if (m < total) {
-            uint32_t lo = 0, hi = N;      // last ray whose offset <= m (rays with no samples share their successor's offset)
-            while (hi - lo > 1) {
-                const uint32_t mid = (lo + hi) >> 1;
-                if ((uint32_t)off[mid] <= m) lo = mid; else hi = mid;
-            }
-            const uint32_t o0 = (uint32_t)off[lo], cnt = (uint32_t)off[lo + 1] - o0;
-            if (o0 + cnt <= M) {  // raymarching.cu:416: a ray that does not fit writes nothing
-                const uint32_t s = m - o0;
-                const float *rec = t_rec + (size_t)lo * max_steps;
-                const float t = rec[s];
-                const float3 rd = *reinterpret_cast<const float3 *>(rays_d + 3 * (size_t)lo), ro = *reinterpret_cast<const float3 *>(rays_o + 3 * (size_t)lo);
-                qx = rd.x; qy = rd.y; qz = rd.z;
-                px = clampf(fmaf(t, qx, ro.x), -g.bound, g.bound);
-                py = clampf(fmaf(t, qy, ro.y), -g.bound, g.bound);
-                pz = clampf(fmaf(t, qz, ro.z), -g.bound, g.bound);
-                d0 = step_len(g, t);
-                float last;
-                if (s == 0) last = start_param(g, nears[lo], noises ? noises[lo] : 0.0f);
-                else { const float tp = rec[s - 1]; last = tp + step_len(g, tp); }
-                d1 = (t + d0) - last;
-            }
-        }
-        *reinterpret_cast<float3 *>(xyzs + 3 * (size_t)m) = make_float3(px, py, pz);
-        *reinterpret_cast<float3 *>(dirs + 3 * (size_t)m) = make_float3(qx, qy, qz);
-        *reinterpret_cast<float2 *>(deltas + 2 * (size_t)m) = make_float2(d0, d1);
-    }
+    for (uint32_t m = blockIdx.x * blockDim.x + threadIdx.x; m < M; m += gridDim.x * blockDim.x)
+        write_sample_row(m, total, LdsOffsets{off}, rays_o, rays_d, g, max_steps, N, M, nears, noises, t_rec, xyzs, dirs, deltas);
 }
 
 // ----------------------------------------------------------------------------- compositing (training)
@@ -920,22 +870,6 @@ __global__ void __launch_bounds__(256) k_march_scan_write(const float *__restric
 // exit `T < T_thresh` becomes a prefix mask: sample j is accumulated iff the transmittance after sample j-1 is still
 // >= T_thresh (the reference tests after accumulating, :557).  Products and sums associate differently from the
 // serial loop, so results agree to fp32 round-off, not bit for bit (they never could: the reference uses __expf).
-
-template <typename Op>
-__device__ inline float wave_scan(float v, int lane, Op op) {  // inclusive scan over the 64 lanes
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const float t = __shfl_up(v, d, 64);
-        if (lane >= d) v = op(v, t);
-    }
-    return v;
-}
-
-__device__ inline float wave_sum(float v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
-    return v;
-}
 
 struct Chunk {
     float alpha, w, T_after, c0, c1, c2, dt, dreal;
@@ -1081,14 +1015,11 @@ __global__ void __launch_bounds__(256) k_composite_bwd(const float *__restrict__
 
 // ----------------------------------------------------------------------------- inference
 
-// raymarching.cu:701-805: march up to n_step occupied samples from rays_t[id].
-__global__ void k_march_burst(uint32_t n_alive, uint32_t n_step, const int32_t *__restrict__ rays_alive,
-                              const float *__restrict__ rays_t, const float *__restrict__ rays_o,
-                              const float *__restrict__ rays_d, GridView g, const float *__restrict__ fars,
-                              float *__restrict__ xyzs, float *__restrict__ dirs, float *__restrict__ deltas,
-                              const float *__restrict__ noises) {
-    const uint32_t n = blockIdx.x * blockDim.x + threadIdx.x;
-    if (n >= n_alive) return;
+// raymarching.cu:701-805: slot n of a burst marches up to n_step occupied samples of its ray from rays_t[id] into its n_step rows; returns the rows written.
+__device__ __forceinline__ uint32_t burst_walk(uint32_t n, uint32_t n_step, const int32_t *__restrict__ rays_alive, const float *__restrict__ rays_t,
+                                               const float *__restrict__ rays_o, const float *__restrict__ rays_d, const GridView &g,
+                                               const float *__restrict__ fars, float *__restrict__ xyzs, float *__restrict__ dirs,
+                                               float *__restrict__ deltas, const float *__restrict__ noises) {
     const int32_t id = rays_alive[n];
     const Ray r(rays_o + 3 * (size_t)id, rays_d + 3 * (size_t)id);
     const float far = fars[id];
@@ -1107,6 +1038,17 @@ __global__ void k_march_burst(uint32_t n_alive, uint32_t n_step, const int32_t *
             px += 3; pd += 3; pl += 2; ++step;
         } else t = leave_cell(g, t, t_exit);
     }
+    return step;
+}
+
+__global__ void k_march_burst(uint32_t n_alive, uint32_t n_step, const int32_t *__restrict__ rays_alive,
+                              const float *__restrict__ rays_t, const float *__restrict__ rays_o,
+                              const float *__restrict__ rays_d, GridView g, const float *__restrict__ fars,
+                              float *__restrict__ xyzs, float *__restrict__ dirs, float *__restrict__ deltas,
+                              const float *__restrict__ noises) {
+    const uint32_t n = blockIdx.x * blockDim.x + threadIdx.x;
+    if (n >= n_alive) return;
+    burst_walk(n, n_step, rays_alive, rays_t, rays_o, rays_d, g, fars, xyzs, dirs, deltas, noises);
 }
 
 // The eval loop with its control state on the device (rm_eval_*): ctl = {n_alive, n_step, rows = n_alive * n_step, samples marched so far}.  A round's
@@ -1117,24 +1059,9 @@ __global__ void k_march_burst_ctl(const uint32_t *__restrict__ ctl, const int32_
     const uint32_t n_alive = ctl[0], n_step = ctl[1];
     const uint32_t n = blockIdx.x * blockDim.x + threadIdx.x;
     if (n >= n_alive) return;
-    const int32_t id = rays_alive[n];
-    const Ray r(rays_o + 3 * (size_t)id, rays_d + 3 * (size_t)id);
-    const float far = fars[id];
-    float t = start_param(g, rays_t[id], noises ? noises[n] : 0.0f);
-    float last = t;
-    float *px = xyzs + 3 * (size_t)n * n_step, *pd = dirs + 3 * (size_t)n * n_step, *pl = deltas + 2 * (size_t)n * n_step;
-    uint32_t step = 0;
-    float x, y, z, dt, t_exit;
-    while (t < far && step < n_step) {
-        if (probe(g, r, t, x, y, z, dt, t_exit)) {
-            px[0] = x; px[1] = y; px[2] = z;
-            pd[0] = r.dx; pd[1] = r.dy; pd[2] = r.dz;
-            t += dt;
-            pl[0] = dt; pl[1] = t - last;
-            last = t;
-            px += 3; pd += 3; pl += 2; ++step;
-        } else t = leave_cell(g, t, t_exit);
-    }
+    uint32_t step = burst_walk(n, n_step, rays_alive, rays_t, rays_o, rays_d, g, fars, xyzs, dirs, deltas, noises);
+    const size_t row = (size_t)n * n_step + step;
+    float *px = xyzs + 3 * row, *pd = dirs + 3 * row, *pl = deltas + 2 * row;
     for (; step < n_step; ++step) {      // the ray ended inside the burst: zero rows (rm_march zero-fills its whole buffers up front; the compositor stops at delta 0)
         px[0] = px[1] = px[2] = 0.0f;
         pd[0] = pd[1] = pd[2] = 0.0f;
@@ -1143,14 +1070,12 @@ __global__ void k_march_burst_ctl(const uint32_t *__restrict__ ctl, const int32_
     }
 }
 
-// Stable compaction (as k_compact_alive) + the next round's control words: n_alive' = survivors (0 once max_steps samples have been marched:
-// renderer_wtmk.py:335), n_step' = clamp(N / n_alive', 1, 8) (:340), rows', samples += n_step.
-__global__ void __launch_bounds__(1024) k_compact_alive_ctl(uint32_t *__restrict__ ctl, const int32_t *__restrict__ in, int32_t *__restrict__ out, uint32_t N,
-                                                            uint32_t max_steps) {
+// Stable compaction of the non-negative ray ids of in[0, n) by one 1024-thread workgroup: ballot + popcount inside a wave, wave bases through LDS,
+// a running base across 1024-element rounds (alive lists are at most a few 10^5 long).  Returns the survivor count, valid in thread 0.
+__device__ __forceinline__ uint32_t compact_alive_block(const int32_t *__restrict__ in, uint32_t n, int32_t *__restrict__ out) {
     __shared__ uint32_t wave_cnt[16];
     __shared__ uint32_t running;
     const uint32_t tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-    const uint32_t n = ctl[0], n_step = ctl[1], marched = ctl[3];
     if (tid == 0) running = 0;
     __syncthreads();
     for (uint32_t base = 0; base < n; base += 1024) {
@@ -1173,7 +1098,16 @@ __global__ void __launch_bounds__(1024) k_compact_alive_ctl(uint32_t *__restrict
         if (tid == 0) running += round_total;
         __syncthreads();
     }
-    if (tid == 0 && n > 0) {
+    return running;
+}
+
+// Stable compaction (compact_alive_block) + the next round's control words: n_alive' = survivors (0 once max_steps samples have been marched:
+// renderer_wtmk.py:335), n_step' = clamp(N / n_alive', 1, 8) (:340), rows', samples += n_step.
+__global__ void __launch_bounds__(1024) k_compact_alive_ctl(uint32_t *__restrict__ ctl, const int32_t *__restrict__ in, int32_t *__restrict__ out, uint32_t N,
+                                                            uint32_t max_steps) {
+    const uint32_t n = ctl[0], n_step = ctl[1], marched = ctl[3];
+    const uint32_t running = compact_alive_block(in, n, out);
+    if (threadIdx.x == 0 && n > 0) {
         const uint32_t done = marched + n_step;
         const uint32_t alive = done < max_steps ? running : 0u;
         const uint32_t next = alive ? min(max(N / alive, 1u), 8u) : 1u;
@@ -1233,36 +1167,10 @@ __global__ void k_eval_begin(uint32_t N, uint32_t *__restrict__ ctl, int32_t *__
     }
 }
 
-// Stable compaction of the non-negative ray ids: ballot + popcount inside a wave, wave bases through LDS,
-// a running base across 1024-element rounds.  One workgroup (alive lists are at most a few 10^5 long).
 __global__ void __launch_bounds__(1024) k_compact_alive(const int32_t *__restrict__ in, uint32_t n,
                                                         int32_t *__restrict__ out, int32_t *__restrict__ n_out) {
-    __shared__ uint32_t wave_cnt[16];
-    __shared__ uint32_t running;
-    const uint32_t tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-    if (tid == 0) running = 0;
-    __syncthreads();
-    for (uint32_t base = 0; base < n; base += 1024) {
-        const uint32_t i = base + tid;
-        const int32_t v = i < n ? in[i] : -1;
-        const bool keep = v >= 0;
-        const unsigned long long ballot = __ballot(keep);
-        const uint32_t before = __popcll(ballot & ((1ull << lane) - 1ull));
-        if (lane == 0) wave_cnt[wid] = __popcll(ballot);
-        __syncthreads();
-        uint32_t wave_base = running, round_total = 0;
-#pragma unroll
-        for (int w = 0; w < 16; ++w) {
-            const uint32_t c = wave_cnt[w];
-            if (w < (int)wid) wave_base += c;
-            round_total += c;
-        }
-        if (keep) out[wave_base + before] = v;
-        __syncthreads();
-        if (tid == 0) running += round_total;
-        __syncthreads();
-    }
-    if (tid == 0) *n_out = (int32_t)running;
+    const uint32_t survivors = compact_alive_block(in, n, out);
+    if (threadIdx.x == 0) *n_out = (int32_t)survivors;
 }
 
 }  // namespace nsig

@@ -11,6 +11,7 @@
 // The level scatter of the base-table gradients lives beside its siblings in hashgrid.hip (hg_levels_plan / hg_levels_scatter).
 #include "hashgrid.h"
 #include "mfma.h"
+#include "wave.h"
 
 namespace nsig {
 
@@ -235,8 +236,7 @@ __global__ void __launch_bounds__(1024) k_clean_loss(const float *__restrict__ i
         s += d * d;
         g_image[i] = k * d;
     }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) s += __shfl_xor(s, d, 64);
+    s = wave_sum(s);
     if ((threadIdx.x & 63u) == 0) scratch[threadIdx.x >> 6] = s;
     __syncthreads();
     if (threadIdx.x == 0) {

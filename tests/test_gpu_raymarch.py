@@ -617,3 +617,55 @@ def test_eval_composite_against_float64(n_alive0, density_scale):
     print(f"\nrm_eval_composite n_alive={n_alive0} density_scale={density_scale}: largest |kernel - float64| / bound: " + ", ".join(f"{k} {v:.3f}" for v, k in ratios))
     assert all(v <= 1.0 for v, _ in ratios), ratios
     assert log.rounds > 1
+
+
+_COMPACT_SENTINEL = -7
+
+
+def _compact_fills(n):
+    """ray ids in a shuffled order (so that a reordering shows), with -1 for the dead: all alive, all dead, about 40 % dead at seeded random places, only the last alive"""
+    rng = np.random.RandomState(1000 + n)
+    ids = rng.permutation(n).astype(np.int32)
+    dead = np.full(n, -1, np.int32)
+    return {"all_alive": ids, "all_dead": dead, "random": np.where(rng.rand(n) < 0.4, -1, ids).astype(np.int32),
+            "last_only": np.concatenate([dead[:-1], ids[-1:]])}
+
+
+@pytest.mark.parametrize("n", [1, 63, 64, 65, 1023, 1024, 1025, 2048, 3001])
+def test_compaction_pair_against_numpy(n):
+    """rm_compact_alive and rm_eval_compact against `alive[alive >= 0]` (order kept) around the wave size and the 1024-element round: entries past the survivor
+    count keep the buffer's sentinel, and rm_eval_compact leaves the next round's control words of its kernel's comment -- survivors (0 once
+    marched + n_step >= max_steps), clamp(N / alive, 1, 8) (1 when no ray survives), their product, marched + n_step -- or nothing at all when ctl[0] == 0."""
+    from nerf_signature_amd import _native as nv
+    N, n_step, marched = 4 * n, 3, 10
+    for name, alive in _compact_fills(n).items():
+        want = alive[alive >= 0]
+        k = want.shape[0]
+        src = _cuda(alive)
+
+        def check_out(out, count, what):
+            got = out.cpu().numpy()
+            np.testing.assert_array_equal(got[:count], want[:count], err_msg=f"{what} {name} n={n}")
+            np.testing.assert_array_equal(got[count:], np.full(n - count, _COMPACT_SENTINEL, np.int32), err_msg=f"{what} {name} n={n}: past the survivors")
+
+        out = torch.full((n,), _COMPACT_SENTINEL, dtype=torch.int32, device="cuda")
+        n_out = torch.full((1,), _COMPACT_SENTINEL, dtype=torch.int32, device="cuda")
+        nv.call("rm_compact_alive", nv.ptr(src), n, nv.ptr(out), nv.ptr(n_out), nv.stream())
+        assert int(n_out.item()) == k, (name, n)
+        check_out(out, k, "rm_compact_alive")
+
+        for max_steps in (1024, marched + n_step):      # not reached; reached by this round
+            ctl = _cuda(np.array([n, n_step, n * n_step, marched], np.uint32).view(np.int32))
+            out = torch.full((n,), _COMPACT_SENTINEL, dtype=torch.int32, device="cuda")
+            nv.call("rm_eval_compact", nv.ptr(ctl), N, max_steps, nv.ptr(src), nv.ptr(out), nv.stream())
+            check_out(out, k, "rm_eval_compact")
+            survivors = k if marched + n_step < max_steps else 0
+            nxt = min(max(N // survivors, 1), 8) if survivors else 1
+            assert ctl.cpu().numpy().view(np.uint32).tolist() == [survivors, nxt, survivors * nxt, marched + n_step], (name, n, max_steps)
+
+        idle = [0, n_step, 0, marched]
+        ctl = _cuda(np.array(idle, np.uint32).view(np.int32))
+        out = torch.full((n,), _COMPACT_SENTINEL, dtype=torch.int32, device="cuda")
+        nv.call("rm_eval_compact", nv.ptr(ctl), N, 1024, nv.ptr(src), nv.ptr(out), nv.stream())
+        check_out(out, 0, "rm_eval_compact with ctl[0] == 0")
+        assert ctl.cpu().numpy().view(np.uint32).tolist() == idle, (name, n)
