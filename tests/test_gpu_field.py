@@ -9,6 +9,7 @@ import pytest
 import torch
 
 import closed_form as cf
+import mlp_ref as mr
 from oracle import field_ref as fr
 
 pytestmark = pytest.mark.gpu
@@ -672,3 +673,253 @@ def test_mixed_plane_sets_equal_fp32_plane_sets_bit_for_bit(fo, tables, monkeypa
         assert float(sig.abs().max()) > 0
     finally:
         nv.call("mlp_set_precision", before)
+
+
+# ---- the render-path MLP kernels: position independence in both arithmetics, float64 chain bound in split bf16 (tests/mlp_ref.py) --------------------------------
+
+
+@pytest.fixture(scope="module")
+def walk():
+    """The walking-count case (every MLP launch has waves that walk three tiles or more, the last tile partial), the same upstream gradients without
+    the scaled blocks, and a seeded permutation of the rows: computed once, never modified."""
+    n = mr.walking_count(torch.cuda.get_device_properties(0).multi_processor_count)
+    pts, dirs, gs, gc = (t.cuda() for t in mr.case(n))
+    gs_plain, gc_plain = (t.cuda() for t in mr.case(n, scaled=False)[2:])
+    perm = torch.from_numpy(np.random.RandomState(77).permutation(n)).cuda()
+    return {"n": n, "pts": pts, "dirs": dirs, "gs": gs, "gc": gc, "gs_plain": gs_plain, "gc_plain": gc_plain, "perm": perm, "inv": torch.argsort(perm)}
+
+
+def _point_words(masks, M):
+    """Mask words [tiles * 32, 6] -> the six words of each live point [M, 6] (layer, lane half): lane p of a tile is point p, wherever the tile sits."""
+    return masks.view(-1, 3, 2, 32).permute(0, 3, 1, 2).reshape(-1, 6)[:M]
+
+
+FWD_ROUTES = ["fused_geo_masks", "planes_masks", "planes_geo", "planes_f32_masks", "rows", "color"]
+
+
+def _fwd_route(fo, route, pts, dirs, base_d, S, packed, monkeypatch, geo_in=None):
+    """One forward entry point / route on the rows given -> the list of its per-point outputs."""
+    from nerf_signature_amd import _native as nv
+    M = pts.shape[0]
+    monkeypatch.setenv("NERFSIG_HALF_PLANES", "0" if route == "planes_f32_masks" else "1")
+    if route == "color":
+        return [fo.field_color(dirs, geo_in, packed)]
+    if route == "rows":
+        base_ptrs = nv.ptr_array([t.detach() for t in base_d])
+        ws = torch.zeros(int(nv.fn("hg_planes_bytes")(M)), dtype=torch.uint8, device="cuda")
+        rows = torch.tensor([M], dtype=torch.int32, device="cuda")
+        sig, rgb = torch.full((M,), float("nan"), device="cuda"), torch.full((M, 3), float("nan"), device="cuda")
+        layout = fo.encode_planes(pts, M, 1.0, base_ptrs, S, ws, rows)
+        nv.call("field_fwd_rows", nv.ptr(pts), nv.ptr(dirs), M, nv.ptr(rows), 1.0, base_ptrs, nv.ptr(S), nv.ptr(packed), nv.ptr(sig), nv.ptr(rgb), nv.ptr(ws), layout, nv.stream())
+        return [sig, rgb]
+    kw = {"fused_geo_masks": dict(planes=False, want_geo=True, want_masks=True), "planes_masks": dict(planes=True, want_masks=True),
+          "planes_geo": dict(planes=True, want_geo=True), "planes_f32_masks": dict(planes=True, want_masks=True)}[route]
+    s, c, geo, masks = fo.field_forward(pts, dirs, 1.0, base_d, S, packed, **kw)
+    return [s, c] + ([geo] if geo is not None else []) + ([_point_words(masks, M)] if masks is not None else [])
+
+
+@pytest.mark.parametrize("route", FWD_ROUTES)
+def test_forward_routes_are_position_independent_and_within_the_chain_bound_against_float64(fo, tables, walk, route, mlp_prec, monkeypatch):
+    """field_fwd (planes NULL | a plane set: pipelined launch with masks, plain loop with geo features | fp32 planes under the fp16 MLP), field_fwd_rows and
+    field_color_fwd.  A row's outputs do not depend on where the row sits: for every edge count M the outputs of pts[:M] are the first M rows of the
+    walking-count run (where waves walk up to three tiles) bit for bit (sigma, rgb, geo, the mask words), and so is a run on a seeded permutation of the rows,
+    un-permuted -- every tile, workgroup and grid edge thereby reduces to rows the oracle tests judge.  Split bf16: sigma, geo and rgb against float64 within the chain bound at the walking count
+    and at 1, 33, 1025 rows (fp16: the worst-case chain bound is as large as the logits; nothing is asserted against it)."""
+    base, cb, base_d, cb_d = tables
+    _, sp, cp = _params(tables)
+    packed = fo.pack_weights(sp, cp)
+    S = fo.codebook_presum(fo.select_tables(cb_d[:64], fo.message_bits(torch.from_numpy(cf.messages(32)[2]))))
+    n, pts, dirs = walk["n"], walk["pts"], walk["dirs"]
+    geo_all = fo.field_forward(pts, None, 1.0, base_d, S, packed, want_rgb=False, want_geo=True)[2] if route == "color" else None
+    run = lambda idx: _fwd_route(fo, route, pts[idx].contiguous(), dirs[idx].contiguous(), base_d, S, packed, monkeypatch, None if geo_all is None else geo_all[idx].contiguous())
+    big = run(slice(0, n))
+    torch.cuda.synchronize()
+    assert all(not torch.isnan(t.float()).any() for t in big)
+    for a, b in zip(big, run(walk["perm"])):
+        assert torch.equal(a, b[walk["inv"]]), "a permutation of the rows changed a row's output"
+    for M in mr.EDGE_COUNTS:
+        for a, b in zip(big, run(slice(0, M))):
+            assert b.shape[0] == M and torch.equal(a[:M], b), (M, "the first M rows alone give other bits")
+    if mlp_prec == "bf16x3":
+        W = mr.split_params(sp, cp)
+        feat = fo.encode((pts + 1) / 2, base_d, S).double().cpu()
+        ref = mr.forward(feat, dirs.cpu(), W)          # (field_color_fwd was given field_fwd's geo features: the chain from the features holds for its rgb)
+        b = mr.forward_chain_bound(ref, W, mr.U_BF16X3)      # (the features are exact: every encoder route equals hg_encode_fwd bit for bit, test (e) below)
+        names = {"color": ["rgb"], "rows": ["sigma", "rgb"], "planes_masks": ["sigma", "rgb"], "planes_f32_masks": ["sigma", "rgb"]}.get(route, ["sigma", "rgb", "geo"])
+        r = {nm: mr.ratio(t, ref[nm], b[nm]) for nm, t in zip(names, big)}
+        for M in (1, 33, 1025):
+            for nm, t in zip(names, run(slice(0, M))):
+                r[f"{nm}@{M}"] = mr.ratio(t, ref[nm][:M], b[nm][:M])
+        print(f"\n[c] {route}: largest error / chain bound " + ", ".join(f"{k} {v:.4f}" for k, v in r.items()))
+        assert max(r.values()) <= 1.0, r
+
+
+@pytest.mark.parametrize("pipe", [0, 3])
+def test_backward_given_masks_is_position_independent_and_within_the_chain_bound_against_float64(fo, tables, walk, pipe, mlp_prec):
+    """field_bwd (dfeat_out, rec_out, G) and field_bwd_planned + the planned scatter, fed the sigma, rgb and masks the forward produced -- given those the
+    backward is a linear map of the upstream gradient, so a float64 reference has no kink ambiguity and no row is excluded.  Both arithmetics: d feature[30:32]
+    of pts[:M] is the walking-count run's first M rows bit for bit, and so is a permuted run un-permuted (the fp16 path's power-of-two normalisation is per
+    point: checked here, not assumed).  Split bf16: d feature against mlp_ref's backward-given-masks within the chain bound over ALL rows (zero rows, rows
+    scaled by 2^30 and 2^-40 included); G of the atomic and of the planned route against the float64 scatter of the reference's d feature, the scatter's own
+    tolerance widened by the scattered chain bound -- with the seeded gradients, where the 2^30 block is the sum, and with the same gradients unscaled."""
+    from nerf_signature_amd import _native as nv
+    base, cb, base_d, cb_d = tables
+    _, sp, cp = _params(tables)
+    packed = fo.pack_weights(sp, cp)
+    S = fo.codebook_presum(fo.select_tables(cb_d[:64], fo.message_bits(torch.from_numpy(cf.messages(32)[2]))))
+    n = walk["n"]
+    before = nv.fn("mlp_get_pipelined")()
+    nv.call("mlp_set_pipelined", pipe)
+    try:
+        def run(idx, scatter=False, grads=("gs", "gc")):
+            pts, dirs, gs, gc = (walk[k][idx].contiguous() for k in ("pts", "dirs") + grads)
+            s, c, _, masks = fo.field_forward(pts, dirs, 1.0, base_d, S, packed, want_masks=True)
+            dfeat, rec = fo.field_backward(pts, 1.0, gs, gc, s, c, masks, packed, want_dfeat=True, want_rec=True)
+            assert torch.equal(rec[:, 5:7].contiguous(), dfeat)
+            out = {"dfeat": dfeat, "rec": rec[:, :7].contiguous(), "sigma": s, "rgb": c, "masks": masks}
+            if scatter:
+                out["G"] = torch.zeros(1 << 19, 2, device="cuda")
+                assert fo.field_backward(pts, 1.0, gs, gc, s, c, masks, packed, G=out["G"], want_dfeat=True).equal(dfeat)
+                out["G_planned"] = torch.zeros(1 << 19, 2, device="cuda")
+                fo.field_backward_planned(pts, 1.0, gs, gc, s, c, masks, packed, fo.ScatterPlan(pts, 1.0), out["G_planned"])
+            return out
+        big = run(slice(0, n), scatter=True)
+        torch.cuda.synchronize()
+        assert not torch.isnan(big["dfeat"]).any()
+        other = run(walk["perm"])
+        assert torch.equal(big["dfeat"], other["dfeat"][walk["inv"]]) and torch.equal(big["rec"], other["rec"][walk["inv"]])
+        for M in mr.EDGE_COUNTS:
+            small = run(slice(0, M))
+            assert torch.equal(big["dfeat"][:M], small["dfeat"]) and torch.equal(big["rec"][:M], small["rec"]), M
+        if mlp_prec == "bf16x3":
+            W = mr.split_params(sp, cp)
+            x01 = ((walk["pts"] + 1.0) / 2.0).cpu()
+            r = {}
+            # twice: the seeded gradients (d feature is per row: every row judged; G is a sum over rows that the 2^30 block dominates, and the planned route's
+            # fixed-point quantum follows the largest gradient) and the same gradients unscaled, where G sees every row
+            for tag, got, grads in (("", big, ("gs", "gc")), ("_plain", run(slice(0, n), scatter=True, grads=("gs_plain", "gc_plain")), ("gs_plain", "gc_plain"))):
+                bits = mr.unpack_masks(got["masks"], n)
+                ref = mr.backward(walk[grads[0]].cpu(), walk[grads[1]].cpu(), got["sigma"].cpu(), got["rgb"].cpu(), bits, W)
+                bound = mr.backward_chain_bound(ref, bits, W, mr.U_BF16X3)
+                want, e = ref["d_feat"][:, 30:32], bound["d_feat"][:, 30:32]
+                r["d_feat" + tag] = mr.ratio(got["dfeat"], want, e)
+                Gref, stats = fr.scatter_ref(x01, want, CB_RES), fr.scatter_row_stats(x01, want, CB_RES)
+                carried = fr.scatter_ref(x01, e, CB_RES)
+                quantum = fr.fixed_quantum(float(got["dfeat"].abs().max()), 4 * n)
+                r["G" + tag] = mr.ratio(got["G"], Gref, fr.scatter_tolerance(Gref, stats, False) + carried)
+                r["G_planned" + tag] = mr.ratio(got["G_planned"], Gref, fr.scatter_tolerance(Gref, stats, True, quantum=quantum) + carried)
+            print(f"\n[d] pipelined={pipe}: largest error / bound " + ", ".join(f"{k} {v:.4f}" for k, v in r.items()))
+            assert max(r.values()) <= 1.0, r
+    finally:
+        nv.call("mlp_set_pipelined", before)
+
+
+# ---- the hot-path plane encoders on the edge points ---------------------------------------------------------------------------------------------------------
+
+def _edge_rows(M, bound, seed):
+    """M positions in [-bound, bound]^3: seeded rows with closed_form.points() (box faces, exact and nearly exact cell boundaries of several levels) mapped
+    to the box and placed first, last (an odd count then shifts the lane pairing) and, from an odd row on, across the 256-point tile boundary.  (Near -bound
+    an fp32 position is coarser than the unit-box coordinate it stands for: a point a few ulp off a cell boundary can land ON it after the trip through
+    [-bound, bound].  The exact boundaries, the box faces and the points off a boundary by more than 2^-24 survive; the full set is hg_encode_fwd's own test.)"""
+    rng = np.random.RandomState(seed)
+    E = (cf.points() * np.float32(2 * bound) - np.float32(bound)).astype(np.float32)
+    x = ((rng.rand(M, 3) * 2 - 1) * bound).astype(np.float32)
+    n = min(M, 256)
+    x[:n] = E[:n]
+    n = min(M, 40)
+    x[M - n:] = E[:n]
+    if M > 300:
+        x[225:289] = E[:64]
+    return torch.from_numpy(x).cuda()
+
+
+def _f32_planes(ws, M):
+    st = (M + 31) // 32 * 32
+    return ws.view(torch.float32).view(17, st, 2)
+
+
+@pytest.mark.parametrize("bound", [1.0, 2.0])
+def test_plane_encoders_against_float64_bit_exact_on_the_edge_points(fo, tables, bound, mlp_prec):
+    """hg_encode_planes, hg_encode_planes_rows, hg_encode_planes_mixed (fp16 MLP) and hg_encode_codebook_plane, with and without the pre-summed codebook, at every
+    edge count: k_encode_planes shares axis_cell and trilerp with the stand-alone k_encode (csrc/hashgrid.h), which the golden vectors pin bit-exactly -- so every
+    plane equals hg_encode_fwd's feature pair bit for bit (lane pairs trade corners by DPP: the same corners must arrive), the codebook plane the literal
+    one-table gather, and level 15 + codebook the fused channel 30:32.  Mixed sets: levels 0..14 are the fp32 value rounded to fp16, nearest even.  Rows between
+    the count and the stride are never consumed (NaN there changes nothing downstream); rows past a device row count's last tile are untouched."""
+    from nerf_signature_amd import _native as nv
+    base, cb, base_d, cb_d = tables
+    _, sp, cp = _params(tables)
+    packed = fo.pack_weights(sp, cp)
+    S = fo.codebook_presum(fo.select_tables(cb_d[:64], fo.message_bits(torch.from_numpy(cf.messages(32)[2]))))
+    base_ptrs = nv.ptr_array([t.detach() for t in base_d])
+    for M in mr.EDGE_COUNTS:
+        pts = _edge_rows(M, bound, seed=M)
+        x01 = (pts + bound) / (2 * bound)
+        st = (M + 31) // 32 * 32
+        nbytes = int(nv.fn("hg_planes_bytes")(M))
+        assert nbytes == 17 * st * 8
+        clean, marked = fo.encode(x01, base_d), fo.encode(x01, base_d, S)
+        cbf = fo.codebook_encode_literal(x01, [S])
+        assert torch.equal(clean[:, 30:] + cbf, marked[:, 30:])
+        if M == 1025:      # ... and the pinned encoder itself against a float64 trilinear blend: 7 fp32 lerps of 3 roundings each and the three 1 - w: 16 u of the largest corner
+            xc = x01.cpu()
+            for l, res in enumerate(fr.level_resolutions(16, 16, 2048)):
+                rows_l, w_l, _ = fr.voxel_lookup(xc, res)
+                corners = base[l][rows_l].double()
+                err = (clean[:, 2 * l:2 * l + 2].double().cpu() - fr.trilerp(corners, w_l.double())).abs()
+                assert bool((err <= 16 * fr.U32 * corners.abs().amax(dim=(1, 2)).unsqueeze(-1)).all()), (l, float(err.max()))
+        for s_ in (None, S):
+            ws = torch.full((nbytes // 4,), float("nan"), device="cuda").view(torch.uint8)
+            nv.call("hg_encode_planes", nv.ptr(pts), M, bound, base_ptrs, nv.ptr(s_), nv.ptr(ws), nv.stream())
+            pl = _f32_planes(ws, M)
+            assert torch.equal(pl[:16, :M].permute(1, 0, 2).reshape(M, 32), clean), (M, "hg_encode_planes")
+            if s_ is not None:
+                assert torch.equal(pl[16, :M], cbf) and torch.equal(pl[15, :M] + pl[16, :M], marked[:, 30:]), M
+            # a device row count inside a capacity 1.5 times larger
+            cap = M + (M + 1) // 2
+            big = torch.cat([pts, torch.full((cap - M, 3), float("nan"), device="cuda")])
+            rows = torch.tensor([M], dtype=torch.int32, device="cuda")
+            ws2 = torch.full((int(nv.fn("hg_planes_bytes")(cap)) // 4,), float("nan"), device="cuda").view(torch.uint8)
+            nv.call("hg_encode_planes_rows", nv.ptr(big), cap, nv.ptr(rows), bound, base_ptrs, nv.ptr(s_), nv.ptr(ws2), nv.stream())
+            pl2 = _f32_planes(ws2, cap)
+            n_pl = 17 if s_ is not None else 16
+            assert torch.equal(pl2[:n_pl, :M], pl[:n_pl, :M]), (M, "hg_encode_planes_rows")
+            assert torch.isnan(pl2[:, st:]).all(), (M, "rows past the device count's last tile were written")
+            # the rows between M and the stride are never consumed: NaN there, the same outputs
+            sig, rgb = (torch.empty(M, device="cuda"), torch.empty(M, 3, device="cuda"))
+            dirs = mr.case(M)[1].cuda()
+            outs = []
+            for poison in (False, True):
+                if poison:
+                    pl[:, M:] = float("nan")
+                nv.call("field_fwd", nv.ptr(pts), nv.ptr(dirs), M, bound, base_ptrs, nv.ptr(s_), nv.ptr(packed), nv.ptr(sig), nv.ptr(rgb), None, None, nv.ptr(ws), fo.PLANES_F32, nv.stream())
+                outs.append((sig.clone(), rgb.clone()))
+            assert torch.equal(outs[0][0], outs[1][0]) and torch.equal(outs[0][1], outs[1][1]) and not torch.isnan(outs[1][0]).any() and not torch.isnan(outs[1][1]).any(), M
+            # the codebook level alone into a set whose base planes are there: plane 16 the same bits, the rest untouched
+            if s_ is not None:
+                ws3 = torch.full((nbytes // 4,), float("nan"), device="cuda").view(torch.uint8)
+                nv.call("hg_encode_planes", nv.ptr(pts), M, bound, base_ptrs, None, nv.ptr(ws3), nv.stream())
+                pl3 = _f32_planes(ws3, M)
+                keep = pl3[:16].clone()
+                nv.call("hg_encode_codebook_plane", nv.ptr(pts), M, bound, nv.ptr(S), nv.ptr(ws3), fo.PLANES_F32, None, nv.stream())
+                assert torch.equal(pl3[16, :M], cbf) and torch.equal(pl3[:16, :M], keep[:, :M]), (M, "hg_encode_codebook_plane")
+            if mlp_prec == "f16":
+                for rows_dev in (None, rows):
+                    cap_m, src = (M, pts) if rows_dev is None else (cap, big)
+                    stm = (cap_m + 31) // 32 * 32
+                    wm = torch.full((int(nv.fn("hg_planes_bytes")(cap_m)) // 4,), float("nan"), device="cuda").view(torch.uint8)
+                    nv.call("hg_encode_planes_mixed", nv.ptr(src), cap_m, nv.ptr(rows_dev), bound, base_ptrs, nv.ptr(s_), nv.ptr(wm), nv.stream())
+                    halves = wm[:15 * stm * 4].view(torch.float16).view(15, stm, 2)
+                    tail = wm[15 * stm * 4:15 * stm * 4 + 2 * stm * 8].view(torch.float32).view(2, stm, 2)
+                    assert torch.equal(halves[:, :M].view(torch.int16), clean[:, :30].reshape(M, 15, 2).permute(1, 0, 2).half().view(torch.int16)), (M, "mixed levels 0..14")
+                    assert torch.equal(tail[0, :M], clean[:, 30:]), (M, "mixed level 15")
+                    if s_ is not None:
+                        assert torch.equal(tail[1, :M], cbf), (M, "mixed codebook level")
+                        wm2 = wm.clone()
+                        tail2 = wm2[15 * stm * 4:15 * stm * 4 + 2 * stm * 8].view(torch.float32).view(2, stm, 2)
+                        tail2[1] = float("nan")
+                        if rows_dev is None:
+                            nv.call("hg_encode_codebook_plane", nv.ptr(src), M, bound, nv.ptr(S), nv.ptr(wm2), fo.PLANES_MIXED, None, nv.stream())
+                            assert torch.equal(tail2[1, :M], cbf) and torch.equal(wm2[:15 * stm * 4], wm[:15 * stm * 4]), (M, "hg_encode_codebook_plane, mixed")
+                    if rows_dev is not None:
+                        words = wm[:15 * stm * 4].view(torch.int32).view(15, stm)      # (the fill is an fp32 NaN: as words, whatever a plane's element type)
+                        assert bool((words[:, st:] == 0x7FC00000).all()) and torch.isnan(tail[:, st:]).all(), (M, "mixed rows past the device count")

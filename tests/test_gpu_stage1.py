@@ -10,6 +10,7 @@ import pytest
 import torch
 
 import closed_form as cf
+import mlp_ref as mr
 from oracle import field_ref as fr
 
 pytestmark = pytest.mark.gpu
@@ -881,3 +882,172 @@ def test_level_scatter_adam_vs_float64_sum_then_torch_adam(case):
             err = (got.double().cpu() - ref.double()).abs()
             assert bool((err <= tol).all()), (case, l, name, float((err - tol).max()))
         assert float(sure.double().mean()) > 0 and bool(((p[l].cpu() == p0[l]) | (g64 != 0)).all())      # rows without a gradient keep their parameters
+
+
+# ---- the stage-1 MLP kernels against float64, layer by layer (tests/mlp_ref.py; proven on the CPU in tests/test_mlp_cpu.py) ---------------------------------------
+
+
+_F64_MODEL = []
+
+
+def _f64_model():
+    """One clean model for all the float64 tests (none of them modifies it)."""
+    if not _F64_MODEL:
+        _F64_MODEL.append(_clean_model()[0])
+    return _F64_MODEL[0]
+
+
+def _counts(group):
+    if group == "edges":
+        return mr.EDGE_COUNTS
+    return (mr.walking_count(torch.cuda.get_device_properties(0).multi_processor_count),)
+
+
+def _f64_case(M, device_rows, scaled=True):
+    """The seeded case of M rows on the device; device_rows: inside buffers 1.5 times larger, every input past the live rows NaN, the count on the device."""
+    pts, dirs, gs, gc = mr.case(M, scaled=scaled)
+    if not device_rows:
+        return tuple(t.cuda() for t in (pts, dirs, gs, gc)), None, None
+    cap = M + (M + 1) // 2
+    pad = lambda t: torch.cat([t, torch.full((cap - M,) + tuple(t.shape[1:]), float("nan"))]).cuda()
+    return tuple(pad(t) for t in (pts, dirs, gs, gc)), cap, torch.tensor([M, 0], dtype=torch.int32, device="cuda")
+
+
+def _mlp_pass(m, pts, dirs, gs, gc, capacity=None, rows=None, fused=True, half=False):
+    """The MLP entry points alone (forward trace, backward trace + weight gradients; no table scatter) -> (traces, sigma gradient, colour gradient);
+    with a capacity every buffer starts as NaN; the weight-gradient slabs (float partial sums, one per workgroup) always do: a workgroup that owns no
+    tile must still write its slab, or the reduction that adds every slab shows it."""
+    from nerf_signature_amd import _native as nv, fieldops as fo, stage1
+    tr = stage1._Traces(pts.shape[0] if capacity is None else capacity, pts.device, fused=fused, half=half)
+    if capacity is not None:
+        for t in [tr.planes, *tr.act, *(tr.d or []), tr.d_planes]:
+            t.fill_(float("nan"))
+    assert tr.wgrad_scratch.numel() % 4 == 0
+    tr.wgrad_scratch.view(torch.float32).fill_(float("nan"))
+    packed = fo.pack_weights(m.sigma_net.params, m.color_net.params)
+    stage1._forward_trace(tr, pts, dirs, m.bound, nv.ptr_array([t.detach() for t in m.encoder.tables()]), packed, rows=rows)
+    g_sp, g_cp = torch.empty(3072, device=pts.device), torch.empty(7168, device=pts.device)
+    stage1._backward_trace(tr, gs, gc, packed, g_sp, g_cp, rows=rows)
+    return tr, g_sp, g_cp
+
+
+def _rows(t, M):
+    """A feature-major trace [width, stride] -> the live rows [M, width] in float64 on the CPU."""
+    return t[:, :M].t().double().cpu()
+
+
+def _planes_rows(planes, M):
+    return planes[:16, :M].permute(1, 0, 2).reshape(M, 32).double().cpu()      # feature 2 l + c
+
+
+def _saved_forward(tr, M):
+    hs, cin, h1, h2 = (_rows(a, M) for a in tr.act)
+    return {"hs": hs, "cin": cin, "h1": h1, "h2": h2, "sigma": tr.sig[:M].double().cpu(), "rgb": tr.rgb[:M].double().cpu()}
+
+
+def _note(worst, ratios):
+    for n, v in ratios.items():
+        worst[n] = max(worst.get(n, 0.0), v)
+
+
+@pytest.mark.parametrize("group", ["edges", "walking"])
+@pytest.mark.parametrize("device_rows", [False, True], ids=["host_rows", "device_rows"])
+@pytest.mark.parametrize("half", [False, True], ids=["f32_traces", "f16_traces"])
+@pytest.mark.parametrize("pipe", [0, 3])
+def test_trace_kernels_against_float64_layer_by_layer(pipe, half, device_rows, group):
+    """field_fwd_trace / _rows / _f16 and field_bwd_trace / _rows (split bf16 always), under both pipelining masks, at every row count around the launch's
+    granularities and at one count where every launch has waves that walk three tiles: from the plane set the kernel read, every saved layer input, sigma and rgb
+    equal the float64 product of the previous SAVED input within mlp_ref's single-layer bound, element by element (fp16 rows: one more fp16 rounding of the
+    stored value and of the input it stands for); every saved pre-activation gradient and d_planes likewise, from the previous one and the masks; a mask bit is
+    "the saved activation > 0" exactly and the reference's sign outside the bound's band; the band holds at most 1 % of the (row, neuron) pairs.
+    fp16 traces go with the one-launch backward, which saves no gradients: its d_planes are the two-launch route's bit for bit (fp32 rows, same masks).
+    Measured: fp32 traces at most 0.61 of the bound (the colour seed), fp16 traces 0.998 on the SH rows -- the stored value's own rounding to nearest attains
+    its unit 2^-11; band share 0.68 %."""
+    from nerf_signature_amd import _native as nv
+    m = _f64_model()
+    W = mr.split_params(m.sigma_net.params, m.color_net.params)
+    u = mr.U_BF16X3
+    before = nv.fn("mlp_get_pipelined")()
+    worst, in_band, pairs = {}, 0, 0
+    nv.call("mlp_set_pipelined", pipe)
+    try:
+        for M in _counts(group):
+            (pts, dirs, gs, gc), cap, rows = _f64_case(M, device_rows)
+            tr = _mlp_pass(m, pts, dirs, gs, gc, capacity=cap, rows=rows, fused=half, half=half)[0]
+            t2 = tr if not half else _mlp_pass(m, pts, dirs, gs, gc, capacity=cap, rows=rows, fused=False)[0]
+            torch.cuda.synchronize()
+            feat, k = _planes_rows(tr.planes, M), _saved_forward(tr, M)
+            assert not any(bool(torch.isnan(v).any()) for v in k.values()), M
+            r = mr.forward_layer_ratios(feat, dirs[:M].cpu(), k, W, u, half=half)
+            # masks: the kernel's own saved activation, exactly; the reference's sign outside the band
+            bits = mr.unpack_masks(tr.masks, M)
+            own = torch.cat([k["hs"] > 0, k["h1"] > 0, k["h2"] > 0], dim=-1)
+            if half:                                       # (an fp16 row may flush a tiny positive activation to 0: the bits are the fp32 route's)
+                assert bool((bits | ~own).all()) and torch.equal(bits, mr.unpack_masks(t2.masks, M)), M
+            else:
+                assert torch.equal(bits, own), (M, int((bits != own).sum()))
+            e_in = (lambda a: mr.F16_EPS * a.abs() + mr.F16_TINY) if half else (lambda a: None)
+            pre = torch.cat([feat @ W["W1s"].t(), k["cin"] @ W["Wc1"].t(), k["h1"] @ W["Wc2"].t()], dim=-1)
+            band = torch.cat([mr.product_bound(feat, W["W1s"].t(), u), mr.product_bound(k["cin"], W["Wc1"].t(), u, e_in(k["cin"])),
+                              mr.product_bound(k["h1"], W["Wc2"].t(), u, e_in(k["h1"]))], dim=-1)
+            clear = pre.abs() > band
+            assert torch.equal(bits[clear], (pre > 0)[clear]), (M, int((bits != (pre > 0))[clear].sum()))
+            ref = mr.forward(feat, dirs[:M].cpu(), W)
+            cb = mr.forward_chain_bound(ref, W, u)
+            in_band += int(torch.cat([ref[n].abs() <= cb[n] for n in ("pre_s", "pre_1", "pre_2")], dim=-1).sum())
+            pairs += 192 * M
+            # backward: the two-launch route's saved gradients (the fp16 route reads the same sigma, rgb and masks)
+            d_hs, d_so, d_h1, d_h2, d_out = (_rows(t, M) for t in t2.d)
+            kb = {"d_hs": d_hs, "d_so": d_so, "d_h1": d_h1, "d_h2": d_h2, "d_out": d_out, "d_feat": _planes_rows(t2.d_planes, M)}
+            assert not any(bool(torch.isnan(v).any()) for v in kb.values()), M
+            r.update(mr.backward_layer_ratios(gs[:M].cpu(), gc[:M].cpu(), t2.sig[:M].cpu(), t2.rgb[:M].cpu(), bits, kb, W, u))
+            if half:
+                assert torch.equal(tr.d_planes[:, :M], t2.d_planes[:, :M]) and torch.equal(tr.sig[:M], t2.sig[:M]) and torch.equal(tr.rgb[:M], t2.rgb[:M]), M
+            if cap is not None and tr.stride > (M + 31) // 32 * 32:      # nothing past the live tiles was written
+                assert torch.isnan(tr.act[0][:, (M + 31) // 32 * 32:].float()).all() and torch.isnan(t2.d_planes[:, (M + 31) // 32 * 32:]).all(), M
+            _note(worst, r)
+            assert max(r.values()) <= 1.0, (M, r)
+    finally:
+        nv.call("mlp_set_pipelined", before)
+    share = in_band / pairs
+    print(f"\n[a] pipelined={pipe} {'f16' if half else 'f32'} traces, {'device' if device_rows else 'host'} rows, {group}: largest error / bound "
+          + ", ".join(f"{n} {v:.3f}" for n, v in worst.items()) + f"; band share {100 * share:.3f} %")
+    assert share <= 0.01
+
+
+@pytest.mark.parametrize("group", ["edges", "walking"])
+@pytest.mark.parametrize("device_rows", [False, True], ids=["host_rows", "device_rows"])
+@pytest.mark.parametrize("entry", ["field_wgrad", "field_bwd_wgrad", "field_bwd_wgrad_f16"])
+def test_weight_gradients_against_float64_at_every_row_count(entry, device_rows, group):
+    """field_wgrad, field_bwd_wgrad and field_bwd_wgrad_f16: each of the five gradients against the float64 product d^T input of the very rows the kernel read,
+    element by element within the single-layer bound of a K = rows product; from one live row (32 or more workgroups, all but one without a tile, every slab
+    summed) to a count where every launch has waves that walk several tiles.  The one-launch routes save no pre-activation gradients: the d factors are the two-launch
+    route's, whose d_planes theirs equal bit for bit.  Rows 3..15 of the padded colour head exactly 0; two runs, the same bits.  Every count twice: with the
+    seeded gradients (one block of rows scaled by 2^30, which then IS the sum and its bound) and with the same gradients unscaled, where every row weighs the
+    same and one stale, dropped or doubled row of a tile leaves the bound (tests/test_mlp_cpu.py: the stale-rows mutant, at every count with a partial tile).
+    The slabs start as NaN (_mlp_pass)."""
+    m = _f64_model()
+    u = mr.U_BF16X3
+    fused, half = entry != "field_wgrad", entry == "field_bwd_wgrad_f16"
+    worst = {}
+    for M, scaled in [(M, sc) for M in _counts(group) for sc in (True, False)]:
+        (pts, dirs, gs, gc), cap, rows = _f64_case(M, device_rows, scaled)
+        t2, s2, c2 = _mlp_pass(m, pts, dirs, gs, gc, capacity=cap, rows=rows, fused=False)
+        if fused:
+            tr, g_s, g_c = _mlp_pass(m, pts, dirs, gs, gc, capacity=cap, rows=rows, fused=True, half=half)
+            assert torch.equal(tr.d_planes[:, :M], t2.d_planes[:, :M]), M
+            again = _mlp_pass(m, pts, dirs, gs, gc, capacity=cap, rows=rows, fused=True, half=half)
+        else:
+            tr, g_s, g_c = t2, s2, c2
+            again = _mlp_pass(m, pts, dirs, gs, gc, capacity=cap, rows=rows, fused=False)
+        assert torch.equal(g_s, again[1]) and torch.equal(g_c, again[2]), M
+        inputs = dict(_saved_forward(tr, M), feat=_planes_rows(tr.planes, M))
+        d = dict(zip(("d_hs", "d_so", "d_h1", "d_h2", "d_out"), (_rows(t, M) for t in t2.d)))
+        want_s, want_c = mr.weight_grads(d, inputs)
+        b_s, b_c = mr.weight_grad_bounds(d, inputs, u)
+        tag = "" if scaled else "_plain"
+        r = {"sigma" + tag: mr.ratio(g_s, want_s, b_s), "colour" + tag: mr.ratio(g_c, want_c, b_c)}
+        _note(worst, r)
+        assert max(r.values()) <= 1.0, (M, scaled, r)
+        assert float(g_c[6144 + 3 * 64:].abs().max()) == 0.0, M
+    print(f"\n[b] {entry}, {'device' if device_rows else 'host'} rows, {group}: largest error / bound " + ", ".join(f"{n} {v:.4f}" for n, v in worst.items()))
