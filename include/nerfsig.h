@@ -196,6 +196,17 @@ int rg_sample_rays(const float *poses, uint32_t P, const float *images, float fx
                    uint32_t N, const int32_t *step_counter, uint32_t stride, uint32_t offset, uint64_t seed, float *rays_o, float *rays_d,
                    float *gt, int64_t *inds_out, int32_t *pose_out, nsig_stream_t stream);
 
+/* rg_sample_rays without a store: the step's camera is DRAWN -- one orbit pose looking at the origin, the closed form of the reference's rand_poses
+ * (nerf/provider_wtmk.py:60-96): theta = theta0 + u0 (theta1 - theta0) (polar), phi = phi0 + u1 (phi1 - phi0), u0 / u1 = words 0 / 1 of sequence 5 of the
+ * counter hash of (seed, k = step * stride + offset), on the 24-bit grid (>> 8, * 2^-24); with s/c = sin/cos:
+ *   right (-c_p, 0, s_p), up (c_t s_p, -s_t, c_t c_p), forward (-s_t s_p, -c_t, -s_t c_p), centre radius * (s_t s_p, c_t, s_t c_p).
+ * Writes the pose (row-major [4,4]) to pose_out, N pixel indices uniform in [0,H*W) (sequence 0 of (seed, step), as rg_sample_rays) to inds_out (int64 [N], or
+ * NULL) and their rays to rays_o / rays_d [N,3] -- the arithmetic of rg_get_rays on that pose and those indices, bit for bit.  One launch; step = *step_counter
+ * (a DEVICE int32, NULL = 0): capturable. */
+int rg_sample_rays_orbit(float fx, float fy, float cx, float cy, uint32_t H, uint32_t W, uint32_t N, const int32_t *step_counter, uint32_t stride,
+                         uint32_t offset, uint64_t seed, float radius, float theta0, float theta1, float phi0, float phi1, float *rays_o, float *rays_d,
+                         int64_t *inds_out, float *pose_out, nsig_stream_t stream);
+
 /* rg_sample_rays drawing from an error map (the reference's --error_map loader, nerf/utils.py:105-114 + nerf/provider.py:300-321): error_map [P, grid*grid]
  * float32 holds one weight per cell of a grid x grid partition of every image (1 <= grid <= 128; the reference fixes 128); N cells (1 <= N <= grid*grid) of row
  * p are drawn WITHOUT replacement with probability proportional to their weight, as torch.multinomial(replacement=False) draws them: the exponential race
@@ -369,6 +380,16 @@ int mlp_set_pipelined(int mask);
 int field_fwd(const float *xyzs, const float *dirs, uint32_t M, float bound, const float *const *base_tables_host,
               const float *S, const void *packed, float *sigmas, float *rgbs, float *geo_feat, uint32_t *masks,
               const void *planes, int planes_layout, nsig_stream_t stream);
+
+/* field_fwd with a clean twin: each 32-point tile loads its planes ONCE and evaluates the MLP chain twice -- with plane 16 (the codebook level) added into
+ * level 15 as field_fwd does (sigmas, rgbs, geo_feat, masks: the same bits as field_fwd with S), and with plane 16 ignored (sigmas_clean [M], rgbs_clean [M,3]:
+ * the same bits as field_fwd with S = NULL over a plane set encoded without S; outputs only -- no masks, no geo features).  The clean field at the points of a
+ * watermarked render, for one more pass of the MLP and no second march or encode.  Every arithmetic and plane layout field_fwd reads planes in (fp16 with
+ * NSIG_PLANES_MIXED or NSIG_PLANES_F32, split-bf16 with NSIG_PLANES_F32; both settings of mlp_set_pipelined bit 0).  planes == NULL (the fused route), S == NULL
+ * and a missing output are refused. */
+int field_fwd_twin(const float *xyzs, const float *dirs, uint32_t M, float bound, const float *const *base_tables_host,
+                   const float *S, const void *packed, float *sigmas, float *rgbs, float *geo_feat, uint32_t *masks,
+                   const void *planes, int planes_layout, float *sigmas_clean, float *rgbs_clean, nsig_stream_t stream);
 
 /* The encoder of field_fwd as its own pass: planes[level][point] (float2; 16 base levels + the pre-summed codebook as
  * plane 16), hg_planes_bytes(M) bytes.  Workgroup (tile, slot = blockIdx % 8) encodes only the levels assigned to

@@ -20,6 +20,7 @@ SIGNATURES = {
     "nsig_last_error": [],
     "nsig_host_device_pointer": [_vp],
     "rg_sample_rays": [_vp, _u32, _vp, _fl, _fl, _fl, _fl, _u32, _u32, _u32, _vp, _u32, _u32, _c.c_uint64, _vp, _vp, _vp, _vp, _vp, _vp],
+    "rg_sample_rays_orbit": [_fl, _fl, _fl, _fl, _u32, _u32, _u32, _vp, _u32, _u32, _c.c_uint64, _fl, _fl, _fl, _fl, _fl, _vp, _vp, _vp, _vp, _vp],
     "rg_sample_rays_weighted": [_vp, _u32, _vp, _fl, _fl, _fl, _fl, _u32, _u32, _u32, _vp, _u32, _u32, _c.c_uint64, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "rg_blend_random_background": [_vp, _u32, _vp, _c.c_uint64, _vp, _vp, _vp],
     "rg_sample_rays_rgba": [_vp, _u32, _vp, _fl, _fl, _fl, _fl, _u32, _u32, _u32, _vp, _u32, _u32, _c.c_uint64, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
@@ -81,6 +82,7 @@ SIGNATURES = {
     "hg_warm_tables": [_vp, _vp, _vp, _vp],
     "hg_encode_codebook_plane": [_vp, _u32, _fl, _vp, _vp, _int, _vp, _vp],
     "field_fwd": [_vp, _vp, _u32, _fl, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _int, _vp],
+    "field_fwd_twin": [_vp, _vp, _u32, _fl, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _int, _vp, _vp, _vp],
     "field_color_fwd": [_vp, _vp, _u32, _vp, _vp, _vp],
     "opt_adam_dense_host": [_u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _fl, _fl, _fl, _fl, _vp],
     "opt_adam_dense": [_u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _fl, _fl, _fl, _fl, _vp, _vp],

@@ -255,11 +255,14 @@ __global__ void __launch_bounds__(256) k_encode_codebook_plane(const float *__re
 // (~0.9 us of a tile) cannot cover that.  Here every wait is for something issued a whole evaluation earlier:
 //     head of tile i:  wait for planes + directions of tile i (requested at the head of tile i-1)
 //                      -> issue the STORES of tile i-1's results (held in 7 registers) -> request planes + directions of tile i+1 -> evaluate tile i.
-template <typename P, bool kMixed>
+// kTwin (field_fwd_twin): the tile's planes are loaded once and the MLP chain runs twice -- with plane 16 added into level 15 (sigmas / rgbs / masks, as ever) and with
+// plane 16 ignored (sigmas_clean / rgbs_clean: the field without a message at the same points).  The two first-layer operands differ in ONE word, level 15's pair.
+template <typename P, bool kMixed, bool kTwin = false>
 __device__ inline void field_fwd_pipelined(const char *lds, int lane, const float *__restrict__ dirs, uint32_t M, bool add_codebook,
                                            const float2 *__restrict__ planes, uint32_t stride, float *__restrict__ sigmas, float *__restrict__ rgbs,
-                                           uint32_t *__restrict__ masks) {
+                                           uint32_t *__restrict__ masks, float *__restrict__ sigmas_clean = nullptr, float *__restrict__ rgbs_clean = nullptr) {
     static_assert(!kMixed || P::kMfmaPerProduct == 1, "mixed plane sets carry fp16 operands: the fp16 MLP only");
+    static_assert(!kTwin || P::kMfmaPerProduct == 1, "the pipelined launch is the fp16 MLP's");
     constexpr size_t kHalf = kFwdBytes;
     const int p = lane & 31, h = lane >> 5;
     const uint32_t n_tiles = ceil_div(M, 32u);
@@ -293,11 +296,16 @@ __device__ inline void field_fwd_pipelined(const char *lds, int lane, const floa
     bool have = false;
     float psigma = 0.0f, prgb[3] = {0.0f, 0.0f, 0.0f};
     uint32_t pmask[3] = {0u, 0u, 0u};
+    [[maybe_unused]] float pcsigma = 0.0f, pcrgb[3] = {0.0f, 0.0f, 0.0f};      // (kTwin: the clean results of the previous tile)
     auto store_prev = [&]() {
         const uint32_t s = ptile * 32 + p;
         if (s < M && h == 0) {
             sigmas[s] = psigma;
             rgbs[3 * (size_t)s] = prgb[0]; rgbs[3 * (size_t)s + 1] = prgb[1]; rgbs[3 * (size_t)s + 2] = prgb[2];
+            if constexpr (kTwin) {
+                sigmas_clean[s] = pcsigma;
+                rgbs_clean[3 * (size_t)s] = pcrgb[0]; rgbs_clean[3 * (size_t)s + 1] = pcrgb[1]; rgbs_clean[3 * (size_t)s + 2] = pcrgb[2];
+            }
         }
         if (masks != nullptr) {      // (a render without gradients keeps no ReLU masks)
             uint32_t *mrow = masks + (size_t)ptile * 192 + lane;
@@ -306,6 +314,11 @@ __device__ inline void field_fwd_pipelined(const char *lds, int lane, const floa
     };
     for (uint32_t tile = first; tile < n_tiles; tile += step) {
         typename P::Op feat[2];
+        [[maybe_unused]] uint32_t clean_top = 0u;      // (kTwin) level 15's operand word without the codebook
+        if constexpr (kTwin) {
+            clean_top = cvt_pk_f16(nf[7].x, nf[7].y);
+            if constexpr (kMixed) clean_top = h ? clean_top : nh[7];
+        }
         if (add_codebook && h) {  // codebook added into channels 30:32 (network_wtmk_tcnn.py:106)
             nf[7].x = nf[7].x + nc.x;
             nf[7].y = nf[7].y + nc.y;
@@ -320,6 +333,7 @@ __device__ inline void field_fwd_pipelined(const char *lds, int lane, const floa
             for (int q = 0; q < 8; ++q) P::put2(feat[q >> 2], q & 3, nf[q].x, nf[q].y);
         }
         float dx = nd.x, dy = nd.y, dz = nd.z;
+        if constexpr (kTwin) asm volatile("" : "+v"(clean_top));
         // A compiler barrier that consumes this tile's inputs: the wait for them (vmcnt counts in order) is placed HERE, where only they and
         // long-acknowledged stores are outstanding -- left free, the compiler issues the next tile's requests first and then has to drain them too.
         if constexpr (P::kMfmaPerProduct == 1)
@@ -331,60 +345,23 @@ __device__ inline void field_fwd_pipelined(const char *lds, int lane, const floa
         if (tile + step < n_tiles) request(tile + step);
         asm volatile("" ::: "memory");
 
-        f32x16 hid[2];
-        typename P::Op b4[4];
-        f32x16 so[1];
-        if constexpr (P::kMfmaPerProduct == 1) {
-            // fp16: every layer's weight fragments are fetched from LDS as ONE burst, issued in front of the vector work that precedes the layer
-            // (the ReLU / packing of the layer before: ~260 cycles) -- fetched one by one, each right in front of its MFMA, a fragment's LDS
-            // latency (~100 cycles) was paid 24 times per tile: half of a wave's cycles were spent parked on lgkmcnt (SQ_WAIT_ANY).
-            f16x8 a0[4], a1[4];
-            load_frags(lds, F0, lane, a0);
-            load_frags(lds, F1, lane, a1);
-            __builtin_amdgcn_sched_barrier(0);
-            mfma_regs<2, 2>(a0, feat, hid);
-            pmask[0] = relu_to_operand<P>(hid, b4);
-            mfma_regs<1, 4>(a1, b4, so);
-        } else {
-            mfma_layer<P, 2, 2>(lds, kHalf, F0, lane, feat, hid);
-            pmask[0] = relu_to_operand<P>(hid, b4);
-            mfma_layer<P, 1, 4>(lds, kHalf, F1, lane, b4, so);
-        }
-        psigma = expf(so[0][0]);  // trunc_exp forward (activation.py:9); row 0 of the sigma head lives in lane half 0
-        float geo8[8];
-#pragma unroll
-        for (int r = 0; r < 8; ++r) geo8[r] = so[0][r];
-        if (h == 0) geo8[0] = 1.0f;  // the slot of row 0 carries the padded constant input (weight column 31)
-        if constexpr (P::kMfmaPerProduct == 1) {     // color_branch() with the fragment bursts in front of the vector work
-            f16x8 a2[4], a3[8], a4[4];
-            load_frags(lds, F2, lane, a2);
-            load_frags(lds, F3, lane, a3);
-            __builtin_amdgcn_sched_barrier(0);
-            const float ux = (dx + 1.0f) / 2.0f, uy = (dy + 1.0f) / 2.0f, uz = (dz + 1.0f) / 2.0f;   // (network_wtmk_tcnn.py:114-115)
-            float sh[16];
-            sh16(ux * 2.0f - 1.0f, uy * 2.0f - 1.0f, uz * 2.0f - 1.0f, sh);
-            typename P::Op cin[2];
-            const uint32_t hm = 0u - (uint32_t)h;     // a bit select (v_bfi): written as `h ? sh[8 + j] : sh[j]` the compiler indexes a scratch copy of sh[]
-            auto pick = [&](int j) { return __uint_as_float((__float_as_uint(sh[j]) & ~hm) | (__float_as_uint(sh[8 + j]) & hm)); };
-#pragma unroll
-            for (int j = 0; j < 8; j += 2) {
-                P::put2(cin[0], j >> 1, pick(j), pick(j + 1));
-                P::put2(cin[1], j >> 1, geo8[j], geo8[j + 1]);
-            }
-            mfma_regs<2, 2>(a2, cin, hid);
-            load_frags(lds, F4, lane, a4);
-            __builtin_amdgcn_sched_barrier(0);
-            pmask[1] = relu_to_operand<P>(hid, b4);
-            mfma_regs<2, 4>(a3, b4, hid);
-            pmask[2] = relu_to_operand<P>(hid, b4);
-            mfma_regs<1, 4>(a4, b4, so);
-#pragma unroll
-            for (int c = 0; c < 3; ++c) prgb[c] = 1.0f / (1.0f + expf(-so[0][c]));  // rows 0..2 live in lane half 0
-        } else {
-            uint32_t mask_c[2] = {0u, 0u};
-            color_branch<P>(lds, lane, h, dx, dy, dz, geo8, mask_c, prgb);
-            pmask[1] = mask_c[0];
-            pmask[2] = mask_c[1];
+#define CHAIN_MASK pmask
+#define CHAIN_SIGMA psigma
+#define CHAIN_RGB prgb
+#include "field_chain_pipelined.h"
+#undef CHAIN_MASK
+#undef CHAIN_SIGMA
+#undef CHAIN_RGB
+        if constexpr (kTwin) {      // the same chain on the clean operand; its ReLU flags are not kept
+            uint32_t clean_mask[3];
+            feat[1].v[3] = clean_top;
+#define CHAIN_MASK clean_mask
+#define CHAIN_SIGMA pcsigma
+#define CHAIN_RGB pcrgb
+#include "field_chain_pipelined.h"
+#undef CHAIN_MASK
+#undef CHAIN_SIGMA
+#undef CHAIN_RGB
         }
         ptile = tile;
         have = true;
@@ -408,6 +385,17 @@ k_field_fwd_train(const float *__restrict__ dirs, uint32_t M, bool add_codebook,
     }
     stage_weights(lds, packed + P::kFwdOffset, (int)P::kFwdLds);
     field_fwd_pipelined<P, kMixed>(lds, threadIdx.x & 63, dirs, M, add_codebook, planes, stride, sigmas, rgbs, masks);
+}
+
+// field_fwd_twin's pipelined launch: the same two workgroups per CU; two waves per SIMD leave the second chain's results their registers.
+template <typename P, bool kMixed>
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2)))
+k_field_fwd_train_twin(const float *__restrict__ dirs, uint32_t M, const float2 *__restrict__ planes, uint32_t stride, const char *__restrict__ packed,
+                       float *__restrict__ sigmas, float *__restrict__ rgbs, uint32_t *__restrict__ masks, float *__restrict__ sigmas_clean,
+                       float *__restrict__ rgbs_clean) {
+    extern __shared__ __attribute__((aligned(16))) char lds[];
+    stage_weights(lds, packed + P::kFwdOffset, (int)P::kFwdLds);
+    field_fwd_pipelined<P, kMixed, true>(lds, threadIdx.x & 63, dirs, M, true, planes, stride, sigmas, rgbs, masks, sigmas_clean, rgbs_clean);
 }
 
 template <typename P, int kPlanes, bool kTrace = false>
@@ -466,38 +454,72 @@ __global__ void __launch_bounds__(256) k_field_fwd(const float *__restrict__ xyz
                 }
         }
 
-        f32x16 hid[2];
-        typename P::Op b4[4];
-        mfma_layer<P, 2, 2>(lds, kHalf, F0, lane, feat, hid);
-        const uint32_t mask_s = relu_to_operand<P>(hid, b4);
-        if (kTrace) store_rows64(trace.hs, stride, s, h, hid, [](float v, int) { return v > 0.0f ? v : 0.0f; });
-        f32x16 so[1];
-        mfma_layer<P, 1, 4>(lds, kHalf, F1, lane, b4, so);
+#define CHAIN_SIGMAS sigmas
+#define CHAIN_RGBS rgbs
+#define CHAIN_GEO geo_out
+#define CHAIN_MASKS masks
+#include "field_chain_plain.h"
+#undef CHAIN_SIGMAS
+#undef CHAIN_RGBS
+#undef CHAIN_GEO
+#undef CHAIN_MASKS
+    }
+}
 
-        // rows 0..15 of the sigma head: register r (< 8) of half h is row_of_reg(h, r); row 0 is log-density
-        const bool live = s < M;
-        if (live && h == 0) sigmas[s] = expf(so[0][0]);  // trunc_exp forward (activation.py:9)
-        if (geo_out != nullptr && live) {
+// field_fwd_twin's plain loop (the split-bf16 MLP; the fp16 MLP with mlp_set_pipelined bit 0 clear or with geo features asked for): k_field_fwd<P, 1> over a plane set
+// with a codebook plane, each tile's planes loaded once and the chain evaluated twice -- with plane 16 added into level 15 (every output of k_field_fwd) and with plane
+// 16 ignored (sigmas_clean / rgbs_clean, nothing else).
+template <typename P>
+__global__ void __launch_bounds__(256) k_field_fwd_twin(const float *__restrict__ dirs, uint32_t M, const float2 *__restrict__ planes, uint32_t stride,
+                                                        const char *__restrict__ packed, float *__restrict__ sigmas, float *__restrict__ rgbs,
+                                                        float *__restrict__ geo_out, uint32_t *__restrict__ masks, bool mixed, float *__restrict__ sigmas_clean,
+                                                        float *__restrict__ rgbs_clean) {
+    extern __shared__ __attribute__((aligned(16))) char lds[];
+    stage_weights(lds, packed + P::kFwdOffset, (int)P::kFwdLds);
+    constexpr size_t kHalf = kFwdBytes;
+    constexpr bool kTrace = false;
+    const ActTrace trace{};
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    const int p = lane & 31, h = lane >> 5;
+    const uint32_t n_tiles = ceil_div(M, 32u);
+    for (uint32_t tile = blockIdx.x * 4 + wid; tile < n_tiles; tile += gridDim.x * 4) {
+        const uint32_t s = tile * 32 + p;
+        const uint32_t sl = min(s, M - 1);
+        float2 f[8];
 #pragma unroll
-            for (int r = 0; r < 8; ++r) {
-                const int rho = row_of_reg(h, r);
-                if (rho >= 1) geo_out[15 * (size_t)s + rho - 1] = so[0][r];
-            }
-        }
-        uint32_t mask_c[2] = {0u, 0u};
-        if (rgbs != nullptr) {
-            float geo8[8];
+        for (int q = 0; q < 8; ++q) f[q] = load_plane(planes, stride, 8 * (q >> 2) + (q & 3) + 4 * h, s, mixed);
+        typename P::Op feat[2], feat_clean;
 #pragma unroll
-            for (int r = 0; r < 8; ++r) geo8[r] = so[0][r];
-            if (h == 0) geo8[0] = 1.0f;  // the slot of row 0 carries the padded constant input (weight column 31)
-            float rgb[3];
-            color_branch<P>(lds, lane, h, dirs[3 * (size_t)sl], dirs[3 * (size_t)sl + 1], dirs[3 * (size_t)sl + 2], geo8, mask_c, rgb,
-                            kTrace ? &trace : nullptr, stride, s);
-            if (live && h == 0) { rgbs[3 * (size_t)s] = rgb[0]; rgbs[3 * (size_t)s + 1] = rgb[1]; rgbs[3 * (size_t)s + 2] = rgb[2]; }
+        for (int q = 0; q < 8; ++q) P::put2(feat[q >> 2], q & 3, f[q].x, f[q].y);
+        feat_clean = feat[1];      // the second K-step's operand with level 15 as it is
+        if (h) {  // codebook added into channels 30:32 (network_wtmk_tcnn.py:106)
+            const float2 c = load_plane(planes, stride, NSIG_BASE_LEVELS, s, mixed);
+            P::put2(feat[1], 3, f[7].x + c.x, f[7].y + c.y);
         }
-        if (masks != nullptr) {
-            uint32_t *mrow = masks + (size_t)tile * 192 + lane;
-            mrow[0] = mask_s; mrow[64] = mask_c[0]; mrow[128] = mask_c[1];
+        {
+#define CHAIN_SIGMAS sigmas
+#define CHAIN_RGBS rgbs
+#define CHAIN_GEO geo_out
+#define CHAIN_MASKS masks
+#include "field_chain_plain.h"
+#undef CHAIN_SIGMAS
+#undef CHAIN_RGBS
+#undef CHAIN_GEO
+#undef CHAIN_MASKS
+        }
+        feat[1] = feat_clean;
+        {
+            float *const no_geo = nullptr;
+            uint32_t *const no_masks = nullptr;
+#define CHAIN_SIGMAS sigmas_clean
+#define CHAIN_RGBS rgbs_clean
+#define CHAIN_GEO no_geo
+#define CHAIN_MASKS no_masks
+#include "field_chain_plain.h"
+#undef CHAIN_SIGMAS
+#undef CHAIN_RGBS
+#undef CHAIN_GEO
+#undef CHAIN_MASKS
         }
     }
 }
@@ -1064,7 +1086,8 @@ NSIG_EXPORT int hg_encode_codebook_plane(const float *xyzs, uint32_t M, float bo
 
 static int field_fwd_impl(const float *xyzs, const float *dirs, uint32_t M, float bound, const float *const *base_tables_host,
                           const float *S, const void *packed, float *sigmas, float *rgbs, float *geo_feat, uint32_t *masks,
-                          const void *planes, int planes_layout, const uint32_t *rows_dev, nsig_stream_t stream) {
+                          const void *planes, int planes_layout, const uint32_t *rows_dev, nsig_stream_t stream, float *sigmas_clean = nullptr,
+                          float *rgbs_clean = nullptr) {
     if (M == 0) return NSIG_OK;
     NSIG_REQUIRE(xyzs && packed && sigmas, "field_fwd: null pointer");
     NSIG_REQUIRE(rgbs == nullptr || dirs != nullptr, "field_fwd: dirs is required when rgbs is requested");
@@ -1086,6 +1109,17 @@ static int field_fwd_impl(const float *xyzs, const float *dirs, uint32_t M, floa
     if (int e = check_layout(planes_layout, "field_fwd")) return e;
     const bool mixed = planes_layout == NSIG_PLANES_MIXED;
     NSIG_REQUIRE(!mixed || f16, "field_fwd: this plane set was written in the mixed (fp16) layout; the split-bf16 MLP needs hg_encode_planes");
+    if (sigmas_clean != nullptr) {      // field_fwd_twin (it checked its own arguments): the same choice of loop as below
+        if (f16 && fwd_pipelined() && geo_feat == nullptr) {
+            if (mixed) k_field_fwd_train_twin<F16, true><<<field_grid(M, true, 2), 256, F16::kFwdLds, st>>>(dirs, M, pl, stride, pk, sigmas, rgbs, masks, sigmas_clean, rgbs_clean);
+            else k_field_fwd_train_twin<F16, false><<<field_grid(M, true, 2), 256, F16::kFwdLds, st>>>(dirs, M, pl, stride, pk, sigmas, rgbs, masks, sigmas_clean, rgbs_clean);
+        } else if (f16) {
+            k_field_fwd_twin<F16><<<field_grid(M, true), 256, F16::kFwdLds, st>>>(dirs, M, pl, stride, pk, sigmas, rgbs, geo_feat, masks, mixed, sigmas_clean, rgbs_clean);
+        } else {
+            k_field_fwd_twin<Bf16x3><<<field_grid(M, true), 256, Bf16x3::kFwdLds, st>>>(dirs, M, pl, stride, pk, sigmas, rgbs, geo_feat, masks, false, sigmas_clean, rgbs_clean);
+        }
+        return check_launch("field_fwd_twin");
+    }
     if (f16 && fwd_pipelined() && dirs != nullptr && rgbs != nullptr && geo_feat == nullptr) {    // the training render's launch (masks) and staged no-grad renders
         if (mixed) k_field_fwd_train<F16, true><<<field_grid(M, true, 2), 256, F16::kFwdLds, st>>>(dirs, M, S != nullptr, pl, stride, pk, sigmas, rgbs, masks, rows_dev);
         else k_field_fwd_train<F16, false><<<field_grid(M, true, 2), 256, F16::kFwdLds, st>>>(dirs, M, S != nullptr, pl, stride, pk, sigmas, rgbs, masks, rows_dev);
@@ -1100,6 +1134,15 @@ NSIG_EXPORT int field_fwd(const float *xyzs, const float *dirs, uint32_t M, floa
                           const float *S, const void *packed, float *sigmas, float *rgbs, float *geo_feat, uint32_t *masks,
                           const void *planes, int planes_layout, nsig_stream_t stream) {
     return field_fwd_impl(xyzs, dirs, M, bound, base_tables_host, S, packed, sigmas, rgbs, geo_feat, masks, planes, planes_layout, nullptr, stream);
+}
+
+NSIG_EXPORT int field_fwd_twin(const float *xyzs, const float *dirs, uint32_t M, float bound, const float *const *base_tables_host, const float *S,
+                               const void *packed, float *sigmas, float *rgbs, float *geo_feat, uint32_t *masks, const void *planes, int planes_layout,
+                               float *sigmas_clean, float *rgbs_clean, nsig_stream_t stream) {
+    NSIG_REQUIRE(sigmas && rgbs && sigmas_clean && rgbs_clean && dirs, "field_fwd_twin: null pointer (both results carry sigmas and rgbs; dirs is required)");
+    NSIG_REQUIRE(planes != nullptr, "field_fwd_twin: needs a plane set (hg_encode_planes / _mixed with S): the fused no-planes route has no plane 16 to leave out");
+    NSIG_REQUIRE(S != nullptr, "field_fwd_twin: S is NULL -- without a codebook both results are field_fwd's");
+    return field_fwd_impl(xyzs, dirs, M, bound, base_tables_host, S, packed, sigmas, rgbs, geo_feat, masks, planes, planes_layout, nullptr, stream, sigmas_clean, rgbs_clean);
 }
 
 NSIG_EXPORT int field_fwd_rows(const float *xyzs, const float *dirs, uint32_t M_capacity, const uint32_t *rows_dev, float bound,

@@ -105,6 +105,19 @@ __global__ void k_packbits(const float *__restrict__ grid, uint32_t n_bytes, flo
     else for (uint32_t b = 0; b < nb; ++b) bits[first + b] = (uint8_t)(word >> (8 * b));
 }
 
+// The ray through pixel centre (i, j) of a pinhole camera with the row-major [4,4] camera-to-world pose Pm (nerf/utils_wtmk_disen.py:131-137).  The ONE place
+// the ray arithmetic is written: k_get_rays, both store samplers (write_sampled_ray) and the orbit sampler call it, so their rays agree bit for bit.
+__device__ inline void pixel_ray(const float *__restrict__ Pm, float fx, float fy, float cx, float cy, float i, float j, float *__restrict__ o, float *__restrict__ d) {
+    const float x = (i - cx) / fx, y = (j - cy) / fy, z = 1.0f;                               // (:131-133), zs == 1
+    const float nrm = sqrtf(x * x + y * y + z * z);                                          // torch.norm(dim=-1)
+    const float dx = x / nrm, dy = y / nrm, dz = z / nrm;
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+        d[r] = dx * Pm[4 * r] + dy * Pm[4 * r + 1] + dz * Pm[4 * r + 2];                      // directions @ R^T (:135)
+        o[r] = Pm[4 * r + 3];                                                                // camera centre (:137)
+    }
+}
+
 // get_rays (nerf/utils_wtmk_disen.py:121-141) for given pixel indices: one lane per ray, no [B, H*W] meshgrid.
 __global__ void k_get_rays(const float *__restrict__ poses, float fx, float fy, float cx, float cy, uint32_t H, uint32_t W,
                            const int64_t *__restrict__ inds, uint32_t B, uint32_t N, float *__restrict__ rays_o,
@@ -114,16 +127,7 @@ __global__ void k_get_rays(const float *__restrict__ poses, float fx, float fy, 
     const uint32_t b = gid / N, n = gid % N;
     const int64_t ind = inds ? inds[(size_t)b * N + n] : (int64_t)n;
     const float i = (float)(ind % (int64_t)W) + 0.5f, j = (float)(ind / (int64_t)W) + 0.5f;  // pixel centres (:76-77)
-    const float x = (i - cx) / fx, y = (j - cy) / fy, z = 1.0f;                               // (:131-133), zs == 1
-    const float nrm = sqrtf(x * x + y * y + z * z);                                          // torch.norm(dim=-1)
-    const float dx = x / nrm, dy = y / nrm, dz = z / nrm;
-    const float *P = poses + 16 * (size_t)b;                                                  // row-major [4,4]
-    float *o = rays_o + 3 * (size_t)gid, *d = rays_d + 3 * (size_t)gid;
-#pragma unroll
-    for (int r = 0; r < 3; ++r) {
-        d[r] = dx * P[4 * r] + dy * P[4 * r + 1] + dz * P[4 * r + 2];                          // directions @ R^T (:135)
-        o[r] = P[4 * r + 3];                                                                 // camera centre (:137)
-    }
+    pixel_ray(poses + 16 * (size_t)b, fx, fy, cx, cy, i, j, rays_o + 3 * (size_t)gid, rays_d + 3 * (size_t)gid);
 }
 
 // One training batch straight from a device-resident store of poses and images (the loader step in front of the
@@ -177,16 +181,7 @@ __device__ inline void write_sampled_ray(const float *__restrict__ poses, const 
                                          uint32_t W, uint32_t p, uint32_t ind, uint32_t n, float *__restrict__ rays_o, float *__restrict__ rays_d,
                                          float *__restrict__ gt, int64_t *__restrict__ inds_out, uint32_t bg_base, float *__restrict__ bg_out) {
     const float i = (float)(ind % W) + 0.5f, j = (float)(ind / W) + 0.5f;                      // as k_get_rays
-    const float x = (i - cx) / fx, y = (j - cy) / fy, z = 1.0f;
-    const float nrm = sqrtf(x * x + y * y + z * z);
-    const float dx = x / nrm, dy = y / nrm, dz = z / nrm;
-    const float *Pm = poses + 16 * (size_t)p;
-    float *o = rays_o + 3 * (size_t)n, *d = rays_d + 3 * (size_t)n;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        d[c] = dx * Pm[4 * c] + dy * Pm[4 * c + 1] + dz * Pm[4 * c + 2];
-        o[c] = Pm[4 * c + 3];
-    }
+    pixel_ray(poses + 16 * (size_t)p, fx, fy, cx, cy, i, j, rays_o + 3 * (size_t)n, rays_d + 3 * (size_t)n);
     if constexpr (RGBA) {
         blend_random_background(reinterpret_cast<const float4 *>(images)[(size_t)p * H * W + ind], bg_base, n, bg_out, gt);
     } else {
@@ -212,6 +207,43 @@ __global__ void k_sample_rays(const float *__restrict__ poses, uint32_t P, const
     write_sampled_ray<RGBA>(poses, images, fx, fy, cx, cy, H, W, p, ind, n, rays_o, rays_d, gt, inds_out,
                             RGBA ? draw_base(seed_lo, seed_hi, step, kBackgroundStream) : 0u, bg_out);
     if (pose_out != nullptr && n == 0) pose_out[0] = (int32_t)p;
+}
+
+// rg_sample_rays without a store: the step's camera is drawn, not looked up.  One orbit pose looking at the origin -- the closed form blocks.rand_poses documents
+// (the reference's rand_poses, nerf/provider_wtmk.py:60-96: polar angle first) -- from the two first words of sequence 5 of the counter hash of
+// (seed, k = step * stride + offset), on torch.rand's 24-bit grid; products in rand_poses' order, every one rounded on its own.  Every lane derives the same pose
+// (the same instructions on the same words: the same bits); lane 0 of the launch writes it out.
+constexpr uint32_t kOrbitStream = 5u;
+__device__ inline void orbit_pose(uint32_t seed_lo, uint32_t seed_hi, uint32_t k, float radius, float theta0, float theta1, float phi0, float phi1, float (&Pm)[16]) {
+    const uint32_t base = draw_base(seed_lo, seed_hi, k, kOrbitStream);
+    const float u_t = (float)(draw_word(base, 0u) >> 8) * (1.0f / 16777216.0f), u_p = (float)(draw_word(base, 1u) >> 8) * (1.0f / 16777216.0f);      // [0, 1)
+    const float theta = __fadd_rn(__fmul_rn(u_t, __fsub_rn(theta1, theta0)), theta0);      // torch.rand(size) * (hi - lo) + lo
+    const float phi = __fadd_rn(__fmul_rn(u_p, __fsub_rn(phi1, phi0)), phi0);
+    const float st = sinf(theta), ct = cosf(theta), sp = sinf(phi), cp = cosf(phi);
+    const float rs = __fmul_rn(radius, st);
+    Pm[0] = -cp;   Pm[1] = __fmul_rn(ct, sp);   Pm[2] = -__fmul_rn(st, sp);   Pm[3] = __fmul_rn(rs, sp);
+    Pm[4] = 0.0f;  Pm[5] = -st;                 Pm[6] = -ct;                  Pm[7] = __fmul_rn(radius, ct);
+    Pm[8] = sp;    Pm[9] = __fmul_rn(ct, cp);   Pm[10] = -__fmul_rn(st, cp);  Pm[11] = __fmul_rn(rs, cp);
+    Pm[12] = 0.0f; Pm[13] = 0.0f;               Pm[14] = 0.0f;                Pm[15] = 1.0f;
+}
+
+__global__ void k_sample_rays_orbit(float fx, float fy, float cx, float cy, uint32_t H, uint32_t W, uint32_t N, const int32_t *__restrict__ step_counter,
+                                    uint32_t stride, uint32_t offset, uint32_t seed_lo, uint32_t seed_hi, float radius, float theta0, float theta1, float phi0,
+                                    float phi1, float *__restrict__ rays_o, float *__restrict__ rays_d, int64_t *__restrict__ inds_out, float *__restrict__ pose_out) {
+    const uint32_t n = blockIdx.x * blockDim.x + threadIdx.x;
+    if (n >= N) return;
+    const uint32_t step = step_counter ? (uint32_t)step_counter[0] : 0u;
+    float Pm[16];
+    orbit_pose(seed_lo, seed_hi, step * stride + offset, radius, theta0, theta1, phi0, phi1, Pm);
+    const uint32_t r = draw_word(draw_base(seed_lo, seed_hi, step, 0u), n);
+    const uint32_t ind = (uint32_t)(((uint64_t)r * ((uint64_t)H * W)) >> 32);                  // uniform in [0, H*W), as k_sample_rays
+    const float i = (float)(ind % W) + 0.5f, j = (float)(ind / W) + 0.5f;                      // as k_get_rays
+    pixel_ray(Pm, fx, fy, cx, cy, i, j, rays_o + 3 * (size_t)n, rays_d + 3 * (size_t)n);
+    if (inds_out != nullptr) inds_out[n] = (int64_t)ind;
+    if (n == 0) {
+#pragma unroll
+        for (int e = 0; e < 16; ++e) pose_out[e] = Pm[e];
+    }
 }
 
 // The same batch drawn from pose p's error map (the reference's --error_map loader: nerf/utils.py:105-114 draws N of the map's G x G cells with
@@ -1590,6 +1622,20 @@ NSIG_EXPORT int rg_sample_rays_rgba(const float *poses, uint32_t P, const float 
                                     float *gt, float *bg_out, int64_t *inds_out, int32_t *pose_out, nsig_stream_t stream) {
     return sample_rays<true>("rg_sample_rays_rgba", poses, P, images, fx, fy, cx, cy, H, W, N, step_counter, stride, offset, seed, rays_o, rays_d, gt, inds_out,
                              pose_out, bg_out, stream);
+}
+
+NSIG_EXPORT int rg_sample_rays_orbit(float fx, float fy, float cx, float cy, uint32_t H, uint32_t W, uint32_t N, const int32_t *step_counter, uint32_t stride,
+                                     uint32_t offset, uint64_t seed, float radius, float theta0, float theta1, float phi0, float phi1, float *rays_o, float *rays_d,
+                                     int64_t *inds_out, float *pose_out, nsig_stream_t stream) {
+    NSIG_REQUIRE(rays_o && rays_d && pose_out, "rg_sample_rays_orbit: null pointer");
+    NSIG_REQUIRE(N >= 1, "rg_sample_rays_orbit: N must be at least 1 (lane 0 writes the pose)");
+    NSIG_REQUIRE(H > 0 && W > 0 && fx != 0.0f && fy != 0.0f, "rg_sample_rays_orbit: bad image size or focal length");
+    NSIG_REQUIRE((uint64_t)H * W < (1ull << 32), "rg_sample_rays_orbit: image too large");
+    NSIG_REQUIRE(radius > 0.0f && theta0 <= theta1 && phi0 <= phi1, "rg_sample_rays_orbit: radius must be positive and the angle ranges ordered");
+    NSIG_REQUIRE(theta0 > 0.0f && theta1 < 3.14159265f, "rg_sample_rays_orbit: polar angles must lie strictly inside (0, pi): the look-at frame is undefined at the poles");
+    k_sample_rays_orbit<<<ceil_div(N, 256u), 256, 0, as_stream(stream)>>>(fx, fy, cx, cy, H, W, N, step_counter, stride, offset, (uint32_t)seed, (uint32_t)(seed >> 32),
+                                                                          radius, theta0, theta1, phi0, phi1, rays_o, rays_d, inds_out, pose_out);
+    return check_launch("rg_sample_rays_orbit");
 }
 
 template <bool RGBA>

@@ -142,10 +142,20 @@ def encode_planes(xyzs, M, bound, base_ptrs, S, planes, rows_dev=None):
     return PLANES_F32
 
 
-def field_forward(xyzs, dirs, bound, base_tables, S, packed, want_rgb=True, want_geo=False, want_masks=False, planes=None, fixed=None):
+def field_forward(xyzs, dirs, bound, base_tables, S, packed, want_rgb=True, want_geo=False, want_masks=False, planes=None, fixed=None, twin=False):
     """sigma [M], rgb [M,3] | None, geo_feat [M,15] | None, masks | None -> field_fwd.
     planes: True/False forces the two-kernel (XCD-partitioned encoder + MLP) / fused route; None picks by size.
-    fixed: a FixedPoints built from these very points -- its base planes are reused, only the codebook level is gathered."""
+    fixed: a FixedPoints built from these very points -- its base planes are reused, only the codebook level is gathered.
+    twin: the clean field at the same points as well (field_fwd_twin: the planes loaded once, the MLP chain evaluated with and without the codebook plane) --
+    returns (sigma, rgb, geo_feat, masks, sigma_clean [M], rgb_clean [M,3]).  Always through a plane set; needs S and want_rgb; no `fixed` points."""
+    if twin:
+        if S is None or not want_rgb:
+            raise ValueError("field_forward(twin=True) needs a codebook pre-sum S and the colour branch: without a message both results are the same field")
+        if fixed is not None:
+            raise NotImplementedError("field_forward(twin=True) with fixed= points: the kept plane set is completed in place per step (not supported yet)")
+        if planes is not None and not planes:
+            raise ValueError("field_forward(twin=True) reads a plane set: the fused route (planes=False) has no codebook plane to leave out")
+        planes = True
     xyzs = xyzs.contiguous().float()
     M, dev = xyzs.shape[0], xyzs.device
     sigmas = torch.empty(M, dtype=torch.float32, device=dev)
@@ -166,6 +176,11 @@ def field_forward(xyzs, dirs, bound, base_tables, S, packed, want_rgb=True, want
     elif use_planes:
         ws = torch.empty(int(nv.fn("hg_planes_bytes")(M)), dtype=torch.uint8, device=dev)
         layout = encode_planes(xyzs, M, bound, base_ptrs, S, ws)
+    if twin:
+        sigmas_clean, rgbs_clean = torch.empty_like(sigmas), torch.empty_like(rgbs)
+        nv.call("field_fwd_twin", nv.ptr(xyzs), nv.ptr(dirs), M, float(bound), base_ptrs, nv.ptr(S), nv.ptr(packed), nv.ptr(sigmas), nv.ptr(rgbs), nv.ptr(geo),
+                nv.ptr(masks), nv.ptr(ws), layout, nv.ptr(sigmas_clean), nv.ptr(rgbs_clean), nv.stream())
+        return sigmas, rgbs, geo, masks, sigmas_clean, rgbs_clean
     nv.call("field_fwd", nv.ptr(xyzs), nv.ptr(dirs) if want_rgb else None, M, float(bound), base_ptrs, nv.ptr(S), nv.ptr(packed),
             nv.ptr(sigmas), nv.ptr(rgbs), nv.ptr(geo), nv.ptr(masks), nv.ptr(ws), layout, nv.stream())
     return sigmas, rgbs, geo, masks
@@ -482,11 +497,13 @@ class _FieldFunction(Function):
 
     tabs: the 16 frozen base tables and the D selected codebook tables (_Tables).  `diff` are the autograd inputs among them: without a sink every selected
     table -- backward returns the fan-out of the shared gradient for each (unselected tables are not inputs, so their grad stays None exactly as in the
-    reference); with a sink the gradient accumulates there, autograd sees None, and ONE selected table is passed only so that the node is recorded."""
+    reference); with a sink the gradient accumulates there, autograd sees None, and ONE selected table is passed only so that the node is recorded.
+    twin: returns (sigma, rgb, sigma_clean, rgb_clean) -- the clean field at the same points from the same launch (field_forward(twin=True)), marked
+    non-differentiable: it depends on nothing that trains."""
 
     @staticmethod
     @_fwd32
-    def forward(ctx, xyzs, dirs, bound, packed, S, sink, tabs, fixed, *diff):
+    def forward(ctx, xyzs, dirs, bound, packed, S, sink, tabs, fixed, twin, *diff):
         base, sel = tabs.base, tabs.sel
         n_sel = len(sel)
         need_grad = n_sel > 0 and len(diff) > 0
@@ -496,7 +513,7 @@ class _FieldFunction(Function):
         else:
             # before the encoder is enqueued: a plan on its own stream forks right behind the march, not behind this forward pass
             ctx.plan = ScatterPlan(xyzs, bound) if need_grad and xyzs.shape[0] >= binned_min_points() else None
-        sigmas, rgbs, _, masks = field_forward(xyzs, dirs, bound, base, S, packed, want_masks=need_grad, fixed=fixed)
+        sigmas, rgbs, _, masks, *clean = field_forward(xyzs, dirs, bound, base, S, packed, want_masks=need_grad, fixed=fixed, twin=twin)
         ctx.bound, ctx.n_diff, ctx.need_grad, ctx.sink = bound, len(diff), need_grad, sink
         if need_grad:
             # the saved ReLU masks are laid out for the arithmetic the forward ran in (csrc/field.hip mask_bit<P>): the backward must run in the same
@@ -505,16 +522,24 @@ class _FieldFunction(Function):
             if sink is not None:
                 sink.selected = list(sel)
                 ctx.sink_selected = sink.selected
+        if twin:
+            ctx.mark_non_differentiable(*clean)
+            ctx.set_materialize_grads(False)      # (or every backward zero-fills two gradients for the clean pair, which nothing reads)
+            return sigmas, rgbs, clean[0], clean[1]
         return sigmas, rgbs
 
     @staticmethod
     @_bwd
-    def backward(ctx, g_sigma, g_rgb):
-        head = (None,) * 8
+    def backward(ctx, g_sigma, g_rgb, *g_clean):
+        head = (None,) * 9
         if not ctx.need_grad:
             return head + (None,) * ctx.n_diff
         xyzs, sigmas, rgbs, masks, packed = ctx.saved_tensors
         plan, ctx.plan = ctx.plan, None
+        if g_sigma is None:      # (only without materialised gradients: the twin)
+            g_sigma = torch.zeros_like(sigmas)
+        if g_rgb is None:
+            g_rgb = torch.zeros_like(rgbs)
         if nv.fn("mlp_get_precision")() != ctx.mlp_precision:
             raise RuntimeError("mlp_set_precision was called between a field forward pass and its backward: the saved ReLU masks belong to the forward's "
                                "arithmetic (run the backward before switching, or switch before the forward)")
@@ -643,9 +668,12 @@ def color_apply(dirs, geo_feat, packed, color_params):
     return _ColorFunction.apply(dirs, geo_feat, packed, color_params)
 
 
-def field_apply(xyzs, dirs, bound, packed, base_tables, selected, S=None, sink=None, fixed=None):
+def field_apply(xyzs, dirs, bound, packed, base_tables, selected, S=None, sink=None, fixed=None, twin=False):
     """(sigma, rgb) with autograd to the selected codebook tables.  S: their pre-sum (computed here if omitted).
-    fixed: the FixedPoints of exactly these points (rays that do not change between steps), or None."""
+    fixed: the FixedPoints of exactly these points (rays that do not change between steps), or None.
+    twin: (sigma, rgb, sigma_clean, rgb_clean) -- see _FieldFunction."""
+    if twin and not len(selected):
+        raise ValueError("field_apply(twin=True) without a message: the field is already the clean one")
     if len(selected) and S is None:
         S = codebook_presum(selected)
     if not torch.is_grad_enabled():
@@ -655,4 +683,4 @@ def field_apply(xyzs, dirs, bound, packed, base_tables, selected, S=None, sink=N
         diff = tuple(selected) if any(t.requires_grad for t in selected) else ()
     else:           # the gradient goes to the sink: one differentiable input is enough to have the node recorded
         diff = next(((t,) for t in selected if t.requires_grad), ())
-    return _FieldFunction.apply(xyzs, dirs, bound, packed, S, sink, _Tables(base_tables, selected), fixed, *diff)
+    return _FieldFunction.apply(xyzs, dirs, bound, packed, S, sink, _Tables(base_tables, selected), fixed, bool(twin), *diff)

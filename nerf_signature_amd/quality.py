@@ -25,7 +25,13 @@ from .trainer import BIT_ACC, PSNRMeter
 README = dict(iters=1000, lambda_w=0.005, lambda_i=1.0, lr=1e-2)       # README.md:45 + main_nerf_wtmk.py:21
 
 
-def watermark_stage(scene="hotdog", device="cuda", n_poses=8, n_test_poses=10, codebook_scale=1e-4, n_rays=4096, seed=0):
+ORBIT_THETA = (0.6, 1.5)      # the polar range the stage's stored poses are drawn from (bench.py's): online targets draw their cameras from the same
+
+
+def watermark_stage(scene="hotdog", device="cuda", n_poses=8, n_test_poses=10, codebook_scale=1e-4, n_rays=4096, seed=0, online_targets=False):
+    """online_targets: no clean-render pre-pass and no image store -- `poses` / `clean` are None, train() draws a new orbit camera every step
+    (rays.OrbitRaySampler) and the step renders its own target (the content render's clean twin); the held-out views' clean images are rendered when
+    test_views asks for them."""
     from .network import NeRFNetwork
     dev = torch.device(device)
     cfg = synthetic.SCENES[scene]
@@ -40,6 +46,9 @@ def watermark_stage(scene="hotdog", device="cuda", n_poses=8, n_test_poses=10, c
     prng = np.random.RandomState(77)          # (bench.py's poses)
     mk = lambda n: torch.from_numpy(np.stack([synthetic.orbit_pose(0.6 + 0.9 * prng.rand(), 2 * np.pi * prng.rand(), cfg["radius"]) for _ in range(n)])).to(dev)
     poses, test_poses = mk(n_poses), mk(n_test_poses)
+    if online_targets:
+        return dict(model=model, scene=scene, device=dev, D=D, H=H, W=W, intr=intr, render_kwargs=kw, block_o=bo, block_d=bd, poses=None, clean=None,
+                    test_poses=test_poses, clean_test=None, n_rays=n_rays, radius=cfg["radius"])
     with torch.no_grad():     # "ground truth" = the clean model's render of the same pose (provider_wtmk.py:408-416)
         clean = blocks.clean_render(model, poses, intr, H, W, kw, max_ray_batch=H * W).reshape(n_poses, H * W, 3).clamp_(0, 1).contiguous()
         clean_test = blocks.clean_render(model, test_poses, intr, H, W, kw, max_ray_batch=H * W).reshape(n_test_poses, H, W, 3).clamp_(0, 1).contiguous()
@@ -82,10 +91,15 @@ def train(stage, steps=None, mode="graphed", lambda_w=README["lambda_w"], lambda
     msgs = messages(D, start + steps + 1, msg_seed)[start:]
     from . import dp as _dp
     world, rank = _dp.world_size(), _dp.rank()          # data-parallel: every rank draws its own content batches (pose k * world + rank, own pixel stream)
-    sampler = rays.DeviceRaySampler(stage["poses"], stage["clean"], stage["intr"], H, W, n_rays, stride=world, offset=rank, seed=sampler_seed + rank)
-    content = {k: torch.empty(1, n_rays, 3, dtype=torch.float32, device=dev) for k in ("rays_o", "rays_d", "images")}
+    online = stage["clean"] is None      # watermark_stage(online_targets=True): cameras drawn per step, the target rendered inside the step
+    if online:
+        sampler = rays.OrbitRaySampler(stage["intr"], H, W, n_rays, stage["radius"], ORBIT_THETA, (0.0, 2 * np.pi), stride=world, offset=rank, seed=sampler_seed + rank,
+                                       device=dev)
+    else:
+        sampler = rays.DeviceRaySampler(stage["poses"], stage["clean"], stage["intr"], H, W, n_rays, stride=world, offset=rank, seed=sampler_seed + rank)
+    content = {k: torch.empty(1, n_rays, 3, dtype=torch.float32, device=dev) for k in (("rays_o", "rays_d") if online else ("rays_o", "rays_d", "images"))}
     counter = torch.full((1,), start, dtype=torch.int32, device=dev)
-    sampler.sample_into(counter, content["rays_o"], content["rays_d"], content["images"])
+    sampler.sample_into(counter, content["rays_o"], content["rays_d"], content.get("images"))
     data = {"watermark": {"rays_o_block": stage["block_o"], "rays_d_block": stage["block_d"]}, "content": content}
     extra = {} if distortion == "none" else {"distortion": distortion}
     graphed = mode in ("graphed", "fixed", "rccl1")
@@ -113,7 +127,7 @@ def train(stage, steps=None, mode="graphed", lambda_w=README["lambda_w"], lambda
 
         def one(k):
             counter.fill_(start + k + 1)  # the captured loop's opening kernel counts the replay before the step draws its batch
-            sampler.sample_into(counter, content["rays_o"], content["rays_d"], content["images"])
+            sampler.sample_into(counter, content["rays_o"], content["rays_d"], content.get("images"))
             used_lr[0] = float(optimizer.param_groups[0]["lr"])
             return loop.step(data, msgs[k])
     else:
@@ -201,6 +215,9 @@ def test_views(stage, seed=9876, max_ray_batch=4096):
         with torch.no_grad():
             message = torch.randint(0, 2, (D,), generator=gen).float().to(dev)
             r = rays.get_rays(stage["test_poses"][b:b + 1], stage["intr"], H, W, -1)
+            if stage["clean_test"] is None:      # (online targets: no pre-pass rendered the held-out views either)
+                stage["clean_test"] = blocks.clean_render(model, stage["test_poses"], stage["intr"], H, W, stage["render_kwargs"], max_ray_batch=H * W) \
+                    .reshape(-1, H, W, 3).clamp_(0, 1).contiguous()
             data = {"rays_o": r["rays_o"], "rays_d": r["rays_d"], "images": stage["clean_test"][b:b + 1], "H": H, "W": W}
             pred, _, gt, _, _, _, _ = trainer.eval_step(model, data, message, dict(stage["render_kwargs"], max_ray_batch=max_ray_batch), render_whole=True)
         yield pred, gt
@@ -232,10 +249,10 @@ test_views.__test__ = test_image.__test__ = test_image_metrics.__test__ = False
 LAST_STAGE = None      # (tools/converge.py's two-rank run compares the ranks' final models)
 
 
-def run(mode="graphed", steps=None, scene="hotdog", n_messages=200, **train_kw):
-    """watermark_stage + train + both evaluations -> the `quality` record of bench.py."""
+def run(mode="graphed", steps=None, scene="hotdog", n_messages=200, online_targets=False, **train_kw):
+    """watermark_stage + train + both evaluations -> the `quality` record of bench.py.  online_targets: see watermark_stage."""
     global LAST_STAGE
-    stage = LAST_STAGE = watermark_stage(scene)
+    stage = LAST_STAGE = watermark_stage(scene, online_targets=online_targets)
     before = test_bitacc(stage, min(n_messages, 50))[0]
     rec = train(stage, steps, mode, **train_kw)
     t0 = time.perf_counter()
@@ -248,7 +265,7 @@ def run(mode="graphed", steps=None, scene="hotdog", n_messages=200, **train_kw):
     psnr = float(host_psnr.measure())
     torch.cuda.synchronize()
     sel = [c for c in rec["adam_steps"]]
-    return {"mode": mode, "steps": rec["steps"], "bit_acc": acc, "wrong_bits_mean": wrong_mean, "wrong_bits_worst_message": wrong_max, "psnr_db": psnr, "ssim": ssim,
+    return {"mode": mode, "online_targets": bool(online_targets), "steps": rec["steps"], "bit_acc": acc, "wrong_bits_mean": wrong_mean, "wrong_bits_worst_message": wrong_max, "psnr_db": psnr, "ssim": ssim,
             **({} if distorted is None else {"bit_acc_distorted_blocks": distorted}),
             "wall_s": rec["wall_s"], "capture_s": rec["prepare_s"], "train_ms_per_step": rec["ms_per_step"], "eval_wall_s": time.perf_counter() - t0, "bit_acc_before_training": before,
             "n_messages": n_messages, "n_test_views": int(stage["test_poses"].shape[0]), "overflowed": rec["overflowed"], "recaptures": rec["recaptures"],

@@ -140,3 +140,42 @@ class DeviceRaySampler:
                 raise ValueError(f"DeviceRaySampler: buffers must hold {self.n_rays} x 3 float32 values")
         nv.call("rg_error_map_update", nv.ptr(self.error_map), self.poses.shape[0], self.error_grid, nv.ptr(self.pose_word), nv.ptr(self.inds_coarse),
                 nv.ptr(pred), nv.ptr(gt), self.n_rays, nv.stream())
+
+
+class OrbitRaySampler:
+    """DeviceRaySampler without a store (rg_sample_rays_orbit): every call DRAWS its camera -- one orbit pose looking at the origin, blocks.rand_poses' closed
+    form with theta ~ U[theta_range], phi ~ U[phi_range] at `radius`, from the counter hash of (seed, step * stride + offset) -- then n_rays uniform pixels and
+    their rays, in one launch with `step` read from a device counter: capturable, like the store samplers.  There are no images to take a ground truth from:
+    a training step fed by this sampler renders its own target (trainer.train_step without content["images"]: the clean twin of the content render), so
+    the watermark stage needs a checkpoint, intrinsics and a camera radius -- no dataset, and every step sees a new pose.  The last pose drawn is kept in
+    `pose` [4,4] (device)."""
+
+    def __init__(self, intrinsics, H, W, n_rays, radius, theta_range=(1.0471975511965976, 2.0943951023931953), phi_range=(0.0, 6.283185307179586), stride=1, offset=0,
+                 seed=0, device="cuda"):
+        self.intr = tuple(float(v) for v in intrinsics)
+        self.H, self.W, self.n_rays, self.stride, self.offset, self.seed = int(H), int(W), int(n_rays), int(stride), int(offset), int(seed)
+        self.radius = float(radius)
+        self.theta_range, self.phi_range = (float(theta_range[0]), float(theta_range[1])), (float(phi_range[0]), float(phi_range[1]))
+        if self.n_rays < 1:
+            raise ValueError("OrbitRaySampler: n_rays must be at least 1")
+        self.images, self.error_map, self.channels = None, None, 3
+        self.pose = torch.zeros(4, 4, dtype=torch.float32, device=device)
+
+    @torch.no_grad()
+    def sample_into(self, step_counter, rays_o, rays_d, gt=None, inds_out=None, pose_out=None, keys_out=None, bg=None):
+        """step_counter: int32 device tensor [1] (or None = step 0).  rays_o / rays_d: float32 buffers of n_rays * 3 elements.  pose_out: float32 [4,4] that
+        receives the drawn pose (default: self.pose).  gt / keys_out / bg belong to samplers with a store and are refused."""
+        if gt is not None or keys_out is not None or bg is not None:
+            raise ValueError("OrbitRaySampler: no image store to take a ground truth (gt=), race keys (keys_out=) or backgrounds (bg=) from; the step renders its "
+                             "own target (trainer.train_step without content[\"images\"])")
+        for t in (rays_o, rays_d):
+            if t.numel() != self.n_rays * 3 or t.dtype != torch.float32:
+                raise ValueError(f"OrbitRaySampler: buffers must hold {self.n_rays} x 3 float32 values")
+        if inds_out is not None and (inds_out.numel() != self.n_rays or inds_out.dtype != torch.int64):
+            raise ValueError(f"OrbitRaySampler: inds_out must hold {self.n_rays} int64 values")
+        pose = self.pose if pose_out is None else pose_out
+        if pose.numel() != 16 or pose.dtype != torch.float32:
+            raise ValueError("OrbitRaySampler: pose_out must hold 4 x 4 float32 values")
+        fx, fy, cx, cy = self.intr
+        nv.call("rg_sample_rays_orbit", fx, fy, cx, cy, self.H, self.W, self.n_rays, nv.ptr(step_counter), self.stride, self.offset, self.seed, self.radius,
+                *self.theta_range, *self.phi_range, nv.ptr(rays_o), nv.ptr(rays_d), nv.ptr(inds_out), nv.ptr(pose), nv.stream())

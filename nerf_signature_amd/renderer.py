@@ -379,7 +379,15 @@ class NeRFRenderer(nn.Module):
         self._premarched = raymarching.MarchRecord(o, d, xyzs, dirs, deltas, rays, nears, fars).made_for(rays_o, rays_d, float(dt_gamma), int(max_steps), self.grid_key())
 
     def run_cuda(self, rays_o, rays_d, message, dt_gamma=0, bg_color=None, perturb=False, force_all_rays=False, max_steps=1024,
-                 T_thresh=1e-4, **kwargs):
+                 T_thresh=1e-4, clean_twin=False, **kwargs):
+        """clean_twin (training path, with a message): results["clean_image"] is the image of the SAME samples through the field without the message -- the clean
+        field comes out of the watermarked render's own MLP launch (field_fwd_twin) and goes through the same compositing forward and render tail, with the same
+        deltas, rays and background; no gradient flows through it.  Bit for bit the "image" of this call with message=None."""
+        if clean_twin and not self.training:
+            raise NotImplementedError("clean_twin: the eval loop terminates rays per field (a ray leaves the alive list when ITS transmittance falls under T_thresh), "
+                                      "so a watermarked and a clean image would not share samples; the twin exists on the training path (model.train())")
+        if clean_twin and message is None:
+            raise ValueError("clean_twin needs a message: without one \"image\" is the clean image")
         bg_color = self._background(bg_color)
         prefix, o, d = self._flatten_rays(rays_o, rays_d)
         plain = self.training and force_all_rays and not perturb      # (the render that march_ahead and premarch march for)
@@ -400,23 +408,29 @@ class NeRFRenderer(nn.Module):
         if self.training:
             bg = _background_tensor(bg_color, o) if o.is_cuda else None
             out = self._march_and_composite_train(o, d, message, nears, fars, dt_gamma, perturb, force_all_rays, max_steps, T_thresh, finish=bg,
-                                                  marched=marched, limits=(self.aabb_train, self.min_near) if march_limits else None)
-            weights_sum, depth, image = out
+                                                  marched=marched, limits=(self.aabb_train, self.min_near) if march_limits else None, clean_twin=clean_twin)
+            weights_sum, depth, image = out[:3]
+            clean = None
+            if clean_twin:
+                clean = out[3][2] if bg is not None else self._finish(prefix, out[3][2], out[3][1], out[3][0], bg_color, nears, fars)[0]
+                clean = {"clean_image": clean.view(*prefix, 3)}
             if bg is not None:   # the tail was done by the compositing launch
-                return {"depth": depth.view(*prefix), "image": image.view(*prefix, 3), "weights_sum": weights_sum}
+                return {"depth": depth.view(*prefix), "image": image.view(*prefix, 3), "weights_sum": weights_sum, **(clean or {})}
         else:
             weights_sum, depth, image = self._march_and_composite_eval(o, d, message, nears, fars, dt_gamma, perturb, max_steps, T_thresh)
         image, depth = self._finish(prefix, image, depth, weights_sum, bg_color, nears, fars)
         results = {"depth": depth, "image": image}
         if self.training:
             results["weights_sum"] = weights_sum
+            results.update(clean or {})
         return results
 
     def _march_and_composite_train(self, o, d, message, nears, fars, dt_gamma, perturb, force_all_rays, max_steps, T_thresh, finish=None,
-                                   marched=None, limits=None):
+                                   marched=None, limits=None, clean_twin=False):
         """All samples of all rays at once, then one differentiable composite (renderer_wtmk.py:280-321)."""
         if marched is not None:      # the samples were marched ahead of this step (march_ahead)
-            return self._field_and_composite(marched.xyzs, marched.dirs, marched.deltas, marched.rays, message, nears, fars, finish, T_thresh, marched.fixed)
+            return self._field_and_composite(marched.xyzs, marched.dirs, marched.deltas, marched.rays, message, nears, fars, finish, T_thresh, marched.fixed,
+                                             clean_twin)
         counter = self.step_counter[self.local_step % 16]  # ring of the last 16 (points, rays) totals
         self.local_step += 1
         capacity = self.capacity_for(o.shape[0])
@@ -432,15 +446,25 @@ class NeRFRenderer(nn.Module):
                                                                    nears, fars, counter, self.mean_count, perturb, 128, force_all_rays,
                                                                    dt_gamma, max_steps)
         self._last_rays = rays if self._keep_rays else None      # (render's fused staging reads the per-ray counts)
-        return self._field_and_composite(xyzs, dirs, deltas, rays, message, nears, fars, finish, T_thresh)
+        return self._field_and_composite(xyzs, dirs, deltas, rays, message, nears, fars, finish, T_thresh, clean_twin=clean_twin)
 
-    def _field_and_composite(self, xyzs, dirs, deltas, rays, message, nears, fars, finish, T_thresh, fixed=None):
+    def _field_and_composite(self, xyzs, dirs, deltas, rays, message, nears, fars, finish, T_thresh, fixed=None, clean_twin=False):
         # fixed: rays declared constant (NeRFNetwork.fix_rays) -- base planes and scatter plan are kept beside the samples
-        sigmas, rgbs = self(xyzs, dirs, message) if fixed is None else self(xyzs, dirs, message, fixed=fixed)
+        # clean_twin: a fourth result, the (weights_sum, depth, image) of the clean field at the same samples -- the same compositing launch once more, no gradient
+        if clean_twin:
+            if fixed is not None:
+                raise NotImplementedError("clean_twin for rays declared constant (fix_rays): their kept plane set is not read by the twin launch")
+            sigmas, rgbs, sigmas_clean, rgbs_clean = self(xyzs, dirs, message, twin=True)
+        else:
+            sigmas, rgbs = self(xyzs, dirs, message) if fixed is None else self(xyzs, dirs, message, fixed=fixed)
         sigmas = sigmas if self.density_scale == 1 else self.density_scale * sigmas
-        if finish is not None:
-            return _CompositeFinish.apply(sigmas, rgbs, deltas, rays, nears, fars, finish, T_thresh)
-        return raymarching.composite_rays_train(sigmas, rgbs, deltas, rays, T_thresh)
+        composite = ((lambda s, c: _CompositeFinish.apply(s, c, deltas, rays, nears, fars, finish, T_thresh)) if finish is not None
+                     else (lambda s, c: raymarching.composite_rays_train(s, c, deltas, rays, T_thresh)))
+        out = composite(sigmas, rgbs)
+        if clean_twin:
+            with torch.no_grad():
+                out = tuple(out) + (tuple(composite(sigmas_clean if self.density_scale == 1 else self.density_scale * sigmas_clean, rgbs_clean)),)
+        return out
 
     def _march_and_composite_eval(self, o, d, message, nears, fars, dt_gamma, perturb, max_steps, T_thresh):
         """Bursts of 1..8 samples over the still-alive rays (renderer_wtmk.py:323-367).
@@ -672,6 +696,10 @@ class NeRFRenderer(nn.Module):
         return {"depth": depth, "image": image}
 
     def render(self, rays_o, rays_d, message=None, staged=False, max_ray_batch=4096, **kwargs):
+        if kwargs.get("clean_twin") and (staged or not self.cuda_ray):
+            raise NotImplementedError("clean_twin exists on the unstaged occupancy-grid training path only (cuda_ray=True, staged=False): the uniform-sample path "
+                                      "re-samples depths from the field's own weights, so the two images would not share samples, and a staged render assembles "
+                                      "\"image\" and \"depth\" chunk by chunk and carries nothing else")
         _run = self.run_cuda if self.cuda_ray else self.run
         B, N = rays_o.shape[:2]
         device = rays_o.device

@@ -132,12 +132,32 @@ def train_step(model, data, message, render_kwargs, lambda_w=1.0, lambda_i=1.0, 
     block_graph: a blockgraph.BlockDecodeGraph (eager callers with constant block rays: the drop-in Trainer.train_step) -- the block render and the
     decoder, forward and backward, replayed as two captured graphs once the rays are kept; it declines (and the eager launches run) whenever it does not apply.
 
+    content without 'images' (online targets): the step renders its own ground truth -- the content render runs with clean_twin=True and its detached
+    "clean_image", the clean model's image of the very same rays and samples (what the reference's pre-pass renders per training pose and stores,
+    provider_wtmk.py:408-421), is gt_rgb.  Same arithmetic from there on, on every stream arrangement below.
+    WARNING: the trigger is the ABSENCE of the key.  A loader that forgot its images no longer fails here with a KeyError -- it trains against the clean twin.  An
+    'images' key that is present but None is taken for exactly that bug and refused (ValueError): leave the key out to ask for online targets.
+
     side_stream: a torch.cuda.Stream on which the content render is issued.  It depends on nothing the block render or the
     decoder produce, and both chains are sequences of small latency-bound launches, so they overlap (forward and -- autograd
     replays a node on the stream it ran on -- backward); the shared codebook gradient is accumulated with atomics by both."""
     wm, content = data["watermark"], data["content"]
     kw = dict(render_kwargs)
     kw.update(staged=False, bg_color=1, perturb=False, force_all_rays=True)
+    online = "images" not in content
+    if not online and content["images"] is None:
+        raise ValueError("train_step: content['images'] is None; a stored-image step needs the images, a step that renders its own target (online targets) "
+                         "has no 'images' key at all")
+    if online and color_space == "linear":
+        raise NotImplementedError("online targets with color_space='linear': the conversion applies to stored sRGB images (utils_wtmk_disen.py:603-604); the clean "
+                                  "twin is already in the model's own space")
+
+    def render_content():
+        """(prediction, ground truth) of the content rays: the stored images, or the clean twin of this very render."""
+        out = model.render(content["rays_o"], content["rays_d"], message, **kw, **({"clean_twin": True} if online else {}))
+        return out["image"], (out["clean_image"].detach() if online else content["images"])
+
+    gt_rgb = None
     if presum_adopt:   # the previous step's optimiser kernel left this message's pre-sum in the buffer (GraphedWatermarkLoop): no pass here
         model.adopt_presum(message)
     main = None
@@ -154,8 +174,10 @@ def train_step(model, data, message, render_kwargs, lambda_w=1.0, lambda_i=1.0, 
         # then waits for that event only (network._presum_consumed).
         if not blocks_first:
             with torch.cuda.stream(side_stream):
-                content_pred_rgb = model.render(content["rays_o"], content["rays_d"], message, **kw)["image"]
+                content_pred_rgb, gt_rgb = render_content()
             content_pred_rgb.record_stream(main)
+            if online:
+                gt_rgb.record_stream(main)
     block_o, block_d, shard = local_blocks(wm)
     graphed = None
     eager_caller = block_graph is not None and main is None and shard is None and not presum_adopt
@@ -164,7 +186,7 @@ def train_step(model, data, message, render_kwargs, lambda_w=1.0, lambda_i=1.0, 
                 and model.point_capacity is None and not torch.cuda.is_current_stream_capturing())
     if eager_caller and (distortion is None or isinstance(distortion, DistortionLayer)):
         whole = None
-        if hasattr(block_graph, "usable_content") and content["images"].shape[-1] == 3:
+        if hasattr(block_graph, "usable_content") and not online and content["images"].shape[-1] == 3:
             whole = (content["rays_o"], content["rays_d"], content["images"], float(lambda_w), float(lambda_i))
             if not block_graph.usable_content(whole, loss_w is loss_w_bce, color_space):
                 whole = None
@@ -184,8 +206,8 @@ def train_step(model, data, message, render_kwargs, lambda_w=1.0, lambda_i=1.0, 
     if main is not None and blocks_first:
         # (the fork above is the content render's only parent; captured BEHIND the block render it is enqueued behind it: GraphedWatermarkLoop)
         with torch.cuda.stream(side_stream):
-            content_pred_rgb = model.render(content["rays_o"], content["rays_d"], message, **kw)["image"]
-            if content_backward_now is not None and color_space == "srgb" and content["images"].shape == content_pred_rgb.shape \
+            content_pred_rgb, gt_rgb = render_content()
+            if content_backward_now is not None and color_space == "srgb" and gt_rgb.shape == content_pred_rgb.shape \
                     and content_pred_rgb.requires_grad:
                 # content_backward_now = the scale of the image loss's seed (lambda_i x the data-parallel factor).  d(mean((c - gt)^2))/dc needs
                 # nothing of the block render or the decoder, so the content render's backward follows its forward directly, on its stream: one chain
@@ -194,10 +216,12 @@ def train_step(model, data, message, render_kwargs, lambda_w=1.0, lambda_i=1.0, 
                 # computes the same MSE for the returned value, from the detached prediction; the seed is the same number it would leave.
                 content_done = torch.cuda.Event()
                 content_done.record(side_stream)      # what the loss kernel waits for: the forward, not the backward behind it
-                early_seed = (content_pred_rgb.detach() - content["images"]) * (2.0 / content_pred_rgb.numel())
+                early_seed = (content_pred_rgb.detach() - gt_rgb) * (2.0 / content_pred_rgb.numel())
                 if float(content_backward_now) != 1.0:
                     early_seed = early_seed * float(content_backward_now)
         content_pred_rgb.record_stream(main)
+        if online:
+            gt_rgb.record_stream(main)
     if main is not None:
         fo.flush_plans()          # the block render's scatter plan: on the plan stream, behind the content render
     image = outputs["image"] if graphed is None else None
@@ -235,12 +259,13 @@ def train_step(model, data, message, render_kwargs, lambda_w=1.0, lambda_i=1.0, 
         decoded = model.msg_decoder(model.normalization(pred_rgb_dist.permute(0, 3, 1, 2)))
     if color_space == "linear":      # utils_wtmk_disen.py:603-604: converted IN PLACE, every step, as the reference does (its loader hands out fresh tensors)
         content["images"][..., :3] = srgb_to_linear(content["images"][..., :3])
-    if content["images"].shape[-1] != 3:
+    if not online and content["images"].shape[-1] != 3:
         # C == 4: the reference itself cannot run this branch in the watermark stage -- `bg_color` is assigned only when C == 3 or bg_radius > 0
         # (utils_wtmk_disen.py:585-586) and read unconditionally at :590: UnboundLocalError
         raise NotImplementedError("RGBA ground truth: the reference's train_step raises UnboundLocalError here (bg_color is only assigned for 3-channel images, "
                                   "utils_wtmk_disen.py:585-590); blend the alpha channel into the images before the step")
-    gt_rgb = content["images"]
+    if not online:
+        gt_rgb = content["images"]
     if main is not None and content_done is not None:
         # issued HERE, behind the decoder's forward launches: this runtime signals another queue only at the end of the run of launches a queue was
         # handed in one piece -- issued right behind the content render's forward, the loss kernel would wait for this backward as well
@@ -257,7 +282,7 @@ def train_step(model, data, message, render_kwargs, lambda_w=1.0, lambda_i=1.0, 
         #  waiting for it here would make the capturing stream depend on an event recorded outside the capture)
         main.wait_stream(side_stream)
     elif main is None:
-        content_pred_rgb = model.render(content["rays_o"], content["rays_d"], message, **kw)["image"]
+        content_pred_rgb, gt_rgb = render_content()
     keys = (keys_dev if keys_dev is not None and keys_dev.device == decoded.device else message.to(decoded.device)).unsqueeze(-1)
     if loss_w is loss_w_bce and decoded.is_cuda and all(t.dtype == torch.float32 for t in (content_pred_rgb, gt_rgb, decoded, keys)) \
             and gt_rgb.shape == content_pred_rgb.shape and keys.shape == decoded.shape:
@@ -530,7 +555,9 @@ class GraphedWatermarkLoop:
         self._refix_pending = False
         self._kept_key = None
         # content_sampler (rays.DeviceRaySampler): the step draws its own content batch -- pose, pixels, rays, ground truth -- on the
-        # device, inside the captured graph, from the replay count; `data` / `next_data` then carry no content part
+        # device, inside the captured graph, from the replay count; `data` / `next_data` then carry no content part.  A sampler without an image
+        # store (rays.OrbitRaySampler, DeviceRaySampler(images=None)) goes with a content part without "images": the step renders its own target
+        # (train_step's online targets) -- one compositing launch more in the captured step, no image buffer anywhere
         if getattr(content_sampler, "error_map", None) is not None:
             raise ValueError("GraphedWatermarkLoop: content_sampler draws from an error map, which only stage 1 updates (stage1.GraphedCleanLoop); the reference's "
                              "watermark stage never writes its map (utils_wtmk_disen.py:763), so a map here would stay what it was: pass a uniform sampler")
@@ -666,7 +693,7 @@ class GraphedWatermarkLoop:
                 self.stage_counter += 1      # (the opening kernel counts the replays when it stages the message)
         if self.content_sampler is not None:
             ct = self.data["content"]
-            self.content_sampler.sample_into(self.stage_counter, ct["rays_o"], ct["rays_d"], ct["images"])
+            self.content_sampler.sample_into(self.stage_counter, ct["rays_o"], ct["rays_d"], ct.get("images"))      # (no "images": online targets, see train_step)
         if self.distortion is not None and self.distortion.name != "scaling":      # this step's draws, from (seed, replay count): the same on every rank
             o = self.data["watermark"]["rays_o_block"]
             self.distortion.draw_on_device(self.stage_counter, tuple(o.shape), o.device)
