@@ -28,6 +28,20 @@ inline hipStream_t as_stream(nsig_stream_t s) { return reinterpret_cast<hipStrea
         }                                 \
     } while (0)
 
+inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+// Element i < n of K parallel host lists of device pointers into K arrays of a launch's argument struct, index by index: a null one is refused with null_fmt, one of
+// the first `aligned` lists that is not 16-byte aligned with align_fmt (printf formats taking who and i).
+template <typename T, size_t K>
+int take_pointers(T *const (&dst)[K], T const *const (&src)[K], uint32_t n, const char *who, const char *null_fmt, const char *align_fmt = nullptr, size_t aligned = K) {
+    for (uint32_t i = 0; i < n; ++i) {
+        for (size_t k = 0; k < K; ++k) NSIG_REQUIRE(src[k][i] != nullptr, null_fmt, who, i);
+        for (size_t k = 0; align_fmt && k < aligned; ++k) NSIG_REQUIRE(aligned16(src[k][i]), align_fmt, who, i);
+        for (size_t k = 0; k < K; ++k) dst[k][i] = src[k][i];
+    }
+    return NSIG_OK;
+}
+
 __host__ __device__ inline uint32_t ceil_div(uint32_t a, uint32_t b) { return (a + b - 1) / b; }
 
 __device__ inline float clampf(float v, float lo, float hi) { return fminf(hi, fmaxf(lo, v)); }

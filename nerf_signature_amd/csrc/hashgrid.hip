@@ -12,6 +12,7 @@
 //   (2) for the same reason every selected table receives the SAME gradient G[T,2]; the backward
 //       scatters once into G and a fan-out pass copies G into the D gradient tensors autograd expects.
 #include <cstdlib>
+#include "adam.h"
 #include "hashgrid.h"
 #include "wave.h"
 
@@ -774,17 +775,8 @@ __device__ inline int fixed_scale(uint32_t gmax_bits, uint32_t n) {
     return n > 2048u ? 62 - E - (32 - __builtin_clz(n)) : 51 - E;
 }
 
-// torch.optim.Adam's update of one element (the dense passes further down and the owners' fused form share it)
-__device__ inline void adam_update(float g, float &p, float &m, float &v, float beta1, float beta2, float eps, float step_size, float inv_bc2_sqrt) {
-    m = m + (1.0f - beta1) * (g - m);                 // exp_avg.lerp_(grad, 1 - beta1)
-    v = v * beta2 + ((1.0f - beta2) * g) * g;         // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, value=1 - beta2)
-    const float denom = sqrtf(v) * inv_bc2_sqrt + eps;  // (exp_avg_sq.sqrt() / bias_correction2_sqrt).add_(eps)
-    p = p - step_size * (m / denom);                  // param.addcdiv_(exp_avg, denom, value=-step_size)
-}
-
 // The owners of hg_levels_scatter_adam finish with the optimiser step of their rows: a slice's gradient never leaves the chip (no 64 MiB of G written and read back,
-// no table pass on the step's serial tail).  scratch: k_adam_dense_prepare's two scalars per table ([set] = lr / (1 - beta1^t), [kOwnerAdamMax + set] = 1 / sqrt(1 - beta2^t)).
-constexpr int kOwnerAdamMax = 32;      // (= kDenseMax, the prepare kernel's scratch layout)
+// no table pass on the step's serial tail).  The update is adam.h's; scratch: adam_prepare_launch's two scalars per table ([set] = lr / (1 - beta1^t), [kAdamGroup + set] = 1 / sqrt(1 - beta2^t)).
 struct OwnerAdam {
     float *p[NSIG_BASE_LEVELS], *m[NSIG_BASE_LEVELS], *v[NSIG_BASE_LEVELS];
     const float *scratch;
@@ -897,7 +889,7 @@ __global__ void __launch_bounds__(1024) k_scatter_binned(const BinHeader *__rest
         const size_t first = (size_t)slice * (kBinRows / 2u);
         f32x4_t *pp = reinterpret_cast<f32x4_t *>(adam.p[blockIdx.y]) + first, *pm = reinterpret_cast<f32x4_t *>(adam.m[blockIdx.y]) + first,
                 *pv = reinterpret_cast<f32x4_t *>(adam.v[blockIdx.y]) + first;
-        const float ss = adam.scratch[blockIdx.y], ib = adam.scratch[kOwnerAdamMax + blockIdx.y];
+        const float ss = adam.scratch[blockIdx.y], ib = adam.scratch[kAdamGroup + blockIdx.y];
         f32x4_t p[kTrips], m[kTrips], v[kTrips];
 #pragma unroll
         for (uint32_t u = 0; u < kTrips; ++u) {      // all twelve requests first (the moments stream; the parameters were gathered from by this step's encoder)
@@ -1022,33 +1014,6 @@ __global__ void __launch_bounds__(256) k_level_lookup(const float *__restrict__ 
     weights[3 * (size_t)m] = c.wx; weights[3 * (size_t)m + 1] = c.wy; weights[3 * (size_t)m + 2] = c.wz;
 }
 
-// Fused Adam over the D selected tables (shared gradient): float4 per lane, D x (param, exp_avg, exp_avg_sq) streams.
-struct AdamPtrs {
-    float *p[NSIG_MAX_MESSAGE_DIM];
-    float *m[NSIG_MAX_MESSAGE_DIM];
-    float *v[NSIG_MAX_MESSAGE_DIM];
-    float step_size[NSIG_MAX_MESSAGE_DIM];
-    float inv_bc2_sqrt[NSIG_MAX_MESSAGE_DIM];
-};
-
-__global__ void __launch_bounds__(256) k_codebook_adam(const float4 *__restrict__ G, AdamPtrs a, uint32_t D, float beta1, float beta2, float eps,
-                                                       float grad_scale) {
-    const uint32_t e = blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= NSIG_TABLE_ROWS / 2) return;
-    float4 g = G[e];
-    g.x *= grad_scale; g.y *= grad_scale; g.z *= grad_scale; g.w *= grad_scale;
-    for (uint32_t i = 0; i < D; ++i) {
-        float4 *pp = reinterpret_cast<float4 *>(a.p[i]) + e, *pm = reinterpret_cast<float4 *>(a.m[i]) + e, *pv = reinterpret_cast<float4 *>(a.v[i]) + e;
-        float4 p = *pp, m = *pm, v = *pv;
-        const float ss = a.step_size[i], ib = a.inv_bc2_sqrt[i];
-        adam_update(g.x, p.x, m.x, v.x, beta1, beta2, eps, ss, ib);
-        adam_update(g.y, p.y, m.y, v.y, beta1, beta2, eps, ss, ib);
-        adam_update(g.z, p.z, m.z, v.z, beta1, beta2, eps, ss, ib);
-        adam_update(g.w, p.w, m.w, v.w, beta1, beta2, eps, ss, ib);
-        *pp = p; *pm = m; *pv = v;
-    }
-}
-
 // ----------------------------------------------------------------------------- device-side table selection
 // (every launch argument independent of the message: the enclosing step can be captured in a hipGraph)
 
@@ -1082,130 +1047,16 @@ __global__ void __launch_bounds__(256) k_codebook_presum_sel(PairPtrs tabs, cons
     S[e] = acc;
 }
 
-struct AdamPairPtrs {
-    float *p[2 * NSIG_MAX_MESSAGE_DIM];
-    float *m[2 * NSIG_MAX_MESSAGE_DIM];
-    float *v[2 * NSIG_MAX_MESSAGE_DIM];
-};
-struct StepPtrs {
-    float *s[2 * NSIG_MAX_MESSAGE_DIM];
-};
-
-// one thread per bit: advance the selected table's step count and derive its bias-correction scalars
-__global__ void k_adam_prepare(StepPtrs steps, const float *__restrict__ message, uint32_t D, const float *__restrict__ lr, float beta1, float beta2,
-                               float *__restrict__ scratch) {
-    const uint32_t i = threadIdx.x;
-    if (i >= D) return;
-    float *sp = steps.s[2 * i + (message[i] != 0.0f)];
-    const float step = *sp + 1.0f;
-    *sp = step;
-    // beta^step as exp(step * log(beta)) in double: same value to ~1e-13 relative, a fraction of pow()'s latency in this tiny kernel
-    scratch[i] = (float)((double)*lr / (1.0 - exp((double)step * log((double)beta1))));
-    scratch[D + i] = (float)(1.0 / sqrt(1.0 - exp((double)step * log((double)beta2))));
-}
-
-// Streaming accesses of the optimiser pass: 836 MiB go through once per step; marked non-temporal so that they do not displace the
-// base tables (64 MiB) from the L2 / Infinity Cache right before the next step's gather.
-typedef float nsig_f32x4 __attribute__((ext_vector_type(4)));
-template <bool NT>
-__device__ __forceinline__ float4 ld4(const float4 *p) {
-    if (!NT) return *p;
-    const nsig_f32x4 v = __builtin_nontemporal_load(reinterpret_cast<const nsig_f32x4 *>(p));
-    return make_float4(v.x, v.y, v.z, v.w);
-}
-template <bool NT>
-__device__ __forceinline__ void st4(float4 *p, const float4 &a) {
-    if (!NT) {
-        *p = a;
-        return;
-    }
-    const nsig_f32x4 v = {a.x, a.y, a.z, a.w};
-    __builtin_nontemporal_store(v, reinterpret_cast<nsig_f32x4 *>(p));
-}
-
-// NEXT: the same pass also produces the pre-summed codebook of the NEXT step's message, S_next = sum_i table[2i + next_i]: where the
-// next bit equals the current one the freshly updated row is already in registers, otherwise the partner table's row is read
-// (about D/2 extra 4 MiB streams: +9 % traffic) -- instead of a separate 128 MiB pre-sum pass at the head of the next step.
-// The sum keeps the table order, so S_next is bit-identical to k_codebook_presum_sel's.
-template <bool NEXT, bool NT>
-__global__ void __launch_bounds__(256) k_codebook_adam_sel(const float4 *__restrict__ G, AdamPairPtrs a, const float *__restrict__ message,
-                                                           const float *__restrict__ scratch, uint32_t D, float beta1, float beta2, float eps,
-                                                           float grad_scale, const float *__restrict__ next_message, float4 *__restrict__ S_next) {
-    const uint32_t e = blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= NSIG_TABLE_ROWS / 2) return;
-    float4 g = ld4<NT>(G + e);
-    g.x *= grad_scale; g.y *= grad_scale; g.z *= grad_scale; g.w *= grad_scale;
-    float4 acc = {0.f, 0.f, 0.f, 0.f};
-    const float4 zero = {0.f, 0.f, 0.f, 0.f};
-    // two tables per trip: six 16-byte loads in flight per thread before the first dependent store
-    uint32_t i = 0;
-    for (; i + 2 <= D; i += 2) {
-        const uint32_t j0 = 2 * i + (message[i] != 0.0f), j1 = 2 * i + 2 + (message[i + 1] != 0.0f);
-        float4 *pp0 = reinterpret_cast<float4 *>(a.p[j0]) + e, *pm0 = reinterpret_cast<float4 *>(a.m[j0]) + e, *pv0 = reinterpret_cast<float4 *>(a.v[j0]) + e;
-        float4 *pp1 = reinterpret_cast<float4 *>(a.p[j1]) + e, *pm1 = reinterpret_cast<float4 *>(a.m[j1]) + e, *pv1 = reinterpret_cast<float4 *>(a.v[j1]) + e;
-        bool other0 = false, other1 = false;      // wave-uniform
-        float4 o0 = zero, o1 = zero;
-        if (NEXT) {
-            other0 = (next_message[i] != 0.0f) != (message[i] != 0.0f);
-            other1 = (next_message[i + 1] != 0.0f) != (message[i + 1] != 0.0f);
-            if (other0) o0 = ld4<NT>(reinterpret_cast<const float4 *>(a.p[j0 ^ 1u]) + e);
-            if (other1) o1 = ld4<NT>(reinterpret_cast<const float4 *>(a.p[j1 ^ 1u]) + e);
-        }
-        float4 p0 = ld4<NT>(pp0), m0 = ld4<NT>(pm0), v0 = ld4<NT>(pv0), p1 = ld4<NT>(pp1), m1 = ld4<NT>(pm1), v1 = ld4<NT>(pv1);
-        const float ss0 = scratch[i], ib0 = scratch[D + i], ss1 = scratch[i + 1], ib1 = scratch[D + i + 1];
-        adam_update(g.x, p0.x, m0.x, v0.x, beta1, beta2, eps, ss0, ib0);
-        adam_update(g.y, p0.y, m0.y, v0.y, beta1, beta2, eps, ss0, ib0);
-        adam_update(g.z, p0.z, m0.z, v0.z, beta1, beta2, eps, ss0, ib0);
-        adam_update(g.w, p0.w, m0.w, v0.w, beta1, beta2, eps, ss0, ib0);
-        adam_update(g.x, p1.x, m1.x, v1.x, beta1, beta2, eps, ss1, ib1);
-        adam_update(g.y, p1.y, m1.y, v1.y, beta1, beta2, eps, ss1, ib1);
-        adam_update(g.z, p1.z, m1.z, v1.z, beta1, beta2, eps, ss1, ib1);
-        adam_update(g.w, p1.w, m1.w, v1.w, beta1, beta2, eps, ss1, ib1);
-        st4<NT>(pp0, p0); st4<NT>(pm0, m0); st4<NT>(pv0, v0); st4<NT>(pp1, p1); st4<NT>(pm1, m1); st4<NT>(pv1, v1);
-        if (NEXT) {
-            const float4 c0 = other0 ? o0 : p0, c1 = other1 ? o1 : p1;
-            acc.x += c0.x; acc.y += c0.y; acc.z += c0.z; acc.w += c0.w;
-            acc.x += c1.x; acc.y += c1.y; acc.z += c1.z; acc.w += c1.w;
-        }
-    }
-    for (; i < D; ++i) {
-        const uint32_t j = 2 * i + (message[i] != 0.0f);
-        float4 *pp = reinterpret_cast<float4 *>(a.p[j]) + e, *pm = reinterpret_cast<float4 *>(a.m[j]) + e, *pv = reinterpret_cast<float4 *>(a.v[j]) + e;
-        bool other = false;
-        float4 o = zero;
-        if (NEXT) {
-            other = (next_message[i] != 0.0f) != (message[i] != 0.0f);
-            if (other) o = ld4<NT>(reinterpret_cast<const float4 *>(a.p[j ^ 1u]) + e);
-        }
-        float4 p = ld4<NT>(pp), m = ld4<NT>(pm), v = ld4<NT>(pv);
-        const float ss = scratch[i], ib = scratch[D + i];
-        adam_update(g.x, p.x, m.x, v.x, beta1, beta2, eps, ss, ib);
-        adam_update(g.y, p.y, m.y, v.y, beta1, beta2, eps, ss, ib);
-        adam_update(g.z, p.z, m.z, v.z, beta1, beta2, eps, ss, ib);
-        adam_update(g.w, p.w, m.w, v.w, beta1, beta2, eps, ss, ib);
-        st4<NT>(pp, p); st4<NT>(pm, m); st4<NT>(pv, v);
-        if (NEXT) {
-            const float4 c = other ? o : p;
-            acc.x += c.x; acc.y += c.y; acc.z += c.z; acc.w += c.w;
-        }
-    }
-    if (NEXT) S_next[e] = acc;
-}
-
 }  // namespace nsig
 
 using namespace nsig;
-
-static int aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 NSIG_EXPORT int hg_codebook_presum(const float *const *tables_host, uint32_t D, float *S, nsig_stream_t stream) {
     NSIG_REQUIRE(tables_host && S, "hg_codebook_presum: null pointer");
     NSIG_REQUIRE(D >= 1 && D <= NSIG_MAX_MESSAGE_DIM, "hg_codebook_presum: D=%u out of range [1,%d]", D, NSIG_MAX_MESSAGE_DIM);
     CodebookPtrs tabs{};
-    for (uint32_t i = 0; i < D; ++i) {
-        NSIG_REQUIRE(tables_host[i] && aligned16(tables_host[i]), "hg_codebook_presum: table %u is null or not 16-byte aligned", i);
-        tabs.p[i] = tables_host[i];
-    }
+    const char *bad = "%s: table %u is null or not 16-byte aligned";
+    if (int e = take_pointers({tabs.p}, {tables_host}, D, "hg_codebook_presum", bad, bad)) return e;
     NSIG_REQUIRE(aligned16(S), "hg_codebook_presum: S must be 16-byte aligned");
     k_codebook_presum<<<NSIG_TABLE_ROWS / 2 / 256, 256, 0, as_stream(stream)>>>(tabs, D, reinterpret_cast<float4 *>(S));
     return check_launch("hg_codebook_presum");
@@ -1213,11 +1064,7 @@ NSIG_EXPORT int hg_codebook_presum(const float *const *tables_host, uint32_t D, 
 
 static int fill_base(const float *const *host, TablePtrs &base, const char *who) {
     NSIG_REQUIRE(host, "%s: null base table list", who);
-    for (int l = 0; l < NSIG_BASE_LEVELS; ++l) {
-        NSIG_REQUIRE(host[l] != nullptr, "%s: base table %d is null", who, l);
-        base.p[l] = host[l];
-    }
-    return NSIG_OK;
+    return take_pointers({base.p}, {host}, NSIG_BASE_LEVELS, who, "%s: base table %u is null");
 }
 
 NSIG_EXPORT int hg_encode_fwd(const float *x01, uint32_t M, const float *const *base_tables_host, const float *S, float *feat,
@@ -1237,10 +1084,7 @@ NSIG_EXPORT int hg_codebook_encode_fwd(const float *x01, uint32_t M, const float
     NSIG_REQUIRE(x01 && tables_host && out, "hg_codebook_encode_fwd: null pointer");
     NSIG_REQUIRE(D >= 1 && D <= NSIG_MAX_MESSAGE_DIM, "hg_codebook_encode_fwd: D=%u out of range", D);
     CodebookPtrs tabs{};
-    for (uint32_t i = 0; i < D; ++i) {
-        NSIG_REQUIRE(tables_host[i] != nullptr, "hg_codebook_encode_fwd: table %u is null", i);
-        tabs.p[i] = tables_host[i];
-    }
+    if (int e = take_pointers({tabs.p}, {tables_host}, D, "hg_codebook_encode_fwd", "%s: table %u is null")) return e;
     k_codebook_encode<<<ceil_div(M, 256), 256, 0, as_stream(stream)>>>(x01, M, tabs, D, 1.0f / kCodebookResolution, out);
     return check_launch("hg_codebook_encode_fwd");
 }
@@ -1257,10 +1101,8 @@ NSIG_EXPORT int hg_fanout_grad(const float *G, float *const *grads_host, uint32_
     NSIG_REQUIRE(G && grads_host, "hg_fanout_grad: null pointer");
     NSIG_REQUIRE(D >= 1 && D <= NSIG_MAX_MESSAGE_DIM, "hg_fanout_grad: D=%u out of range", D);
     GradPtrs grads{};
-    for (uint32_t i = 0; i < D; ++i) {
-        NSIG_REQUIRE(grads_host[i] && aligned16(grads_host[i]), "hg_fanout_grad: gradient %u is null or not 16-byte aligned", i);
-        grads.p[i] = grads_host[i];
-    }
+    const char *bad = "%s: gradient %u is null or not 16-byte aligned";
+    if (int e = take_pointers({grads.p}, {grads_host}, D, "hg_fanout_grad", bad, bad)) return e;
     NSIG_REQUIRE(aligned16(G), "hg_fanout_grad: G must be 16-byte aligned");
     k_fanout<<<NSIG_TABLE_ROWS / 2 / 256, 256, 0, as_stream(stream)>>>(reinterpret_cast<const float4 *>(G), grads, D, accumulate);
     return check_launch("hg_fanout_grad");
@@ -1272,23 +1114,6 @@ NSIG_EXPORT int hg_level_lookup(const float *x01, uint32_t M, float resolution, 
     NSIG_REQUIRE(resolution >= 1.0f, "hg_level_lookup: resolution must be >= 1");
     k_level_lookup<<<ceil_div(M, 256), 256, 0, as_stream(stream)>>>(x01, M, 1.0f / resolution, rows, weights);
     return check_launch("hg_level_lookup");
-}
-
-NSIG_EXPORT int opt_codebook_adam(const float *G, float *const *params_host, float *const *exp_avg_host, float *const *exp_avg_sq_host,
-                                  uint32_t D, float beta1, float beta2, float eps, const float *step_size_host,
-                                  const float *inv_bc2_sqrt_host, float grad_scale, nsig_stream_t stream) {
-    NSIG_REQUIRE(G && params_host && exp_avg_host && exp_avg_sq_host && step_size_host && inv_bc2_sqrt_host, "opt_codebook_adam: null pointer");
-    NSIG_REQUIRE(D >= 1 && D <= NSIG_MAX_MESSAGE_DIM, "opt_codebook_adam: D=%u out of range", D);
-    NSIG_REQUIRE(aligned16(G), "opt_codebook_adam: G must be 16-byte aligned");
-    AdamPtrs a{};
-    for (uint32_t i = 0; i < D; ++i) {
-        NSIG_REQUIRE(params_host[i] && exp_avg_host[i] && exp_avg_sq_host[i], "opt_codebook_adam: table %u has a null pointer", i);
-        NSIG_REQUIRE(aligned16(params_host[i]) && aligned16(exp_avg_host[i]) && aligned16(exp_avg_sq_host[i]), "opt_codebook_adam: table %u is not 16-byte aligned", i);
-        a.p[i] = params_host[i]; a.m[i] = exp_avg_host[i]; a.v[i] = exp_avg_sq_host[i];
-        a.step_size[i] = step_size_host[i]; a.inv_bc2_sqrt[i] = inv_bc2_sqrt_host[i];
-    }
-    k_codebook_adam<<<NSIG_TABLE_ROWS / 2 / 256, 256, 0, as_stream(stream)>>>(reinterpret_cast<const float4 *>(G), a, D, beta1, beta2, eps, grad_scale);
-    return check_launch("opt_codebook_adam");
 }
 
 NSIG_EXPORT int hg_scatter_sliced(const float *rec, uint32_t M, float *G, nsig_stream_t stream) {
@@ -1313,228 +1138,11 @@ NSIG_EXPORT int hg_codebook_presum_sel(const float *const *all_tables_host, cons
     NSIG_REQUIRE(all_tables_host && message && S, "hg_codebook_presum_sel: null pointer");
     NSIG_REQUIRE(D >= 1 && D <= NSIG_MAX_MESSAGE_DIM, "hg_codebook_presum_sel: D=%u out of range [1,%d]", D, NSIG_MAX_MESSAGE_DIM);
     PairPtrs tabs{};
-    for (uint32_t j = 0; j < 2 * D; ++j) {
-        NSIG_REQUIRE(all_tables_host[j] && aligned16(all_tables_host[j]), "hg_codebook_presum_sel: table %u is null or not 16-byte aligned", j);
-        tabs.p[j] = all_tables_host[j];
-    }
+    const char *bad = "%s: table %u is null or not 16-byte aligned";
+    if (int e = take_pointers({tabs.p}, {all_tables_host}, 2 * D, "hg_codebook_presum_sel", bad, bad)) return e;
     NSIG_REQUIRE(aligned16(S), "hg_codebook_presum_sel: S must be 16-byte aligned");
     k_codebook_presum_sel<<<NSIG_TABLE_ROWS / 2 / 256, 256, 0, as_stream(stream)>>>(tabs, message, D, reinterpret_cast<float4 *>(S));
     return check_launch("hg_codebook_presum_sel");
-}
-
-static int codebook_adam_sel(const char *who, const float *G, float *const *params_host, float *const *exp_avg_host, float *const *exp_avg_sq_host,
-                             float *const *steps_host, const float *message, uint32_t D, const float *lr, float beta1, float beta2,
-                             float eps, float grad_scale, float *scratch, const float *next_message, float *S_next, nsig_stream_t stream) {
-    NSIG_REQUIRE(G && params_host && exp_avg_host && exp_avg_sq_host && steps_host && message && lr && scratch, "%s: null pointer", who);
-    NSIG_REQUIRE(D >= 1 && D <= NSIG_MAX_MESSAGE_DIM, "%s: D=%u out of range", who, D);
-    NSIG_REQUIRE(aligned16(G), "%s: G must be 16-byte aligned", who);
-    AdamPairPtrs a{};
-    StepPtrs s{};
-    for (uint32_t j = 0; j < 2 * D; ++j) {
-        NSIG_REQUIRE(params_host[j] && exp_avg_host[j] && exp_avg_sq_host[j] && steps_host[j], "%s: table %u has a null pointer", who, j);
-        NSIG_REQUIRE(aligned16(params_host[j]) && aligned16(exp_avg_host[j]) && aligned16(exp_avg_sq_host[j]), "%s: table %u is not 16-byte aligned", who, j);
-        a.p[j] = params_host[j]; a.m[j] = exp_avg_host[j]; a.v[j] = exp_avg_sq_host[j]; s.s[j] = steps_host[j];
-    }
-    hipStream_t st = as_stream(stream);
-    k_adam_prepare<<<1, NSIG_MAX_MESSAGE_DIM, 0, st>>>(s, message, D, lr, beta1, beta2, scratch);
-    if (int e = check_launch(who)) return e;
-    // non-temporal accesses (same-box A/B of the bench step, three pairs: 1.124-1.138 ms against 1.151-1.157 with plain accesses; the kernel alone takes
-    // the same 160-164 us either way, the next step's gather gains)
-    if (next_message)
-        k_codebook_adam_sel<true, true><<<NSIG_TABLE_ROWS / 2 / 256, 256, 0, st>>>(reinterpret_cast<const float4 *>(G), a, message, scratch, D, beta1, beta2, eps,
-                                                                                 grad_scale, next_message, reinterpret_cast<float4 *>(S_next));
-    else
-        k_codebook_adam_sel<false, false><<<NSIG_TABLE_ROWS / 2 / 256, 256, 0, st>>>(reinterpret_cast<const float4 *>(G), a, message, scratch, D, beta1, beta2, eps,
-                                                                               grad_scale, nullptr, nullptr);
-    return check_launch(who);
-}
-
-NSIG_EXPORT int opt_codebook_adam_sel(const float *G, float *const *params_host, float *const *exp_avg_host, float *const *exp_avg_sq_host,
-                                      float *const *steps_host, const float *message, uint32_t D, const float *lr, float beta1, float beta2,
-                                      float eps, float grad_scale, float *scratch, nsig_stream_t stream) {
-    return codebook_adam_sel("opt_codebook_adam_sel", G, params_host, exp_avg_host, exp_avg_sq_host, steps_host, message, D, lr, beta1, beta2, eps,
-                             grad_scale, scratch, nullptr, nullptr, stream);
-}
-
-NSIG_EXPORT int opt_codebook_adam_sel_next(const float *G, float *const *params_host, float *const *exp_avg_host, float *const *exp_avg_sq_host,
-                                           float *const *steps_host, const float *message, uint32_t D, const float *lr, float beta1, float beta2,
-                                           float eps, float grad_scale, float *scratch, const float *next_message, float *S_next,
-                                           nsig_stream_t stream) {
-    NSIG_REQUIRE(next_message && S_next && aligned16(S_next), "opt_codebook_adam_sel_next: next_message / S_next null or S_next not 16-byte aligned");
-    return codebook_adam_sel("opt_codebook_adam_sel_next", G, params_host, exp_avg_host, exp_avg_sq_host, steps_host, message, D, lr, beta1, beta2, eps,
-                             grad_scale, scratch, next_message, S_next, stream);
-}
-
-// ----------------------------------------------------------------------------- dense multi-tensor Adam (the decoder's parameters)
-
-// torch's fused multi-tensor Adam walks 64K-element chunks, one workgroup each: the decoder's 29 tensors (262k parameters) become
-// ~30 workgroups that each stream 64K elements serially (28 us).  Here a chunk is 1024 elements, so the same update is ~260
-// workgroups of one pass (~3 us).  Same arithmetic as adam_update above (torch.optim.Adam, no weight decay / amsgrad).
-constexpr int kDenseMax = 32;
-constexpr uint32_t kDenseChunk = 1024;
-struct DenseAdam {
-    float *p[kDenseMax], *m[kDenseMax], *v[kDenseMax], *step[kDenseMax];
-    const float *g[kDenseMax];
-    uint32_t numel[kDenseMax], chunk0[kDenseMax + 1];   // chunk0: first chunk of tensor i
-    uint8_t slot[kDenseMax];                            // where the tensor's two step scalars sit in the scratch (k_adam_dense_prepare's index)
-};
-
-__global__ void k_adam_dense_prepare(DenseAdam a, uint32_t n, const float *__restrict__ lr, float beta1, float beta2, float *__restrict__ scratch) {
-    const uint32_t i = threadIdx.x;
-    if (i >= n) return;
-    const float step = *a.step[i] + 1.0f;
-    *a.step[i] = step;
-    scratch[i] = (float)((double)*lr / (1.0 - exp((double)step * log((double)beta1))));
-    scratch[kDenseMax + i] = (float)(1.0 / sqrt(1.0 - exp((double)step * log((double)beta2))));
-}
-
-__global__ void __launch_bounds__(256) k_adam_dense(DenseAdam a, uint32_t n, const float *__restrict__ scratch, float beta1, float beta2, float eps,
-                                                    float grad_scale) {
-    uint32_t i = 0;
-    while (i + 1 < n && blockIdx.x >= a.chunk0[i + 1]) ++i;   // uniform: which tensor this chunk belongs to
-    const uint32_t base = (blockIdx.x - a.chunk0[i]) * kDenseChunk;
-    const float ss = scratch[a.slot[i]], ib = scratch[kDenseMax + a.slot[i]];
-    float *__restrict__ pp = a.p[i], *__restrict__ pm = a.m[i], *__restrict__ pv = a.v[i];
-    const float *__restrict__ pg = a.g[i];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-        const uint32_t e = base + u * 256 + threadIdx.x;
-        if (e < a.numel[i]) {
-            float p = pp[e], m = pm[e], v = pv[e];
-            adam_update(pg[e] * grad_scale, p, m, v, beta1, beta2, eps, ss, ib);
-            pp[e] = p; pm[e] = m; pv[e] = v;
-        }
-    }
-}
-
-// The same update with the per-tensor step size lr / (1 - beta1^t) and 1 / sqrt(1 - beta2^t) computed by the HOST (torch.optim.Adam's non-capturable state
-// keeps its step counts in host tensors: opt_adam_dense_host, the drop-in model's optimiser hook).
-struct DenseScalars {
-    float ss[kDenseMax], ib[kDenseMax];
-};
-__global__ void __launch_bounds__(256) k_adam_dense_host(DenseAdam a, uint32_t n, DenseScalars sc, float beta1, float beta2, float eps, float grad_scale) {
-    uint32_t i = 0;
-    while (i + 1 < n && blockIdx.x >= a.chunk0[i + 1]) ++i;   // uniform: which tensor this chunk belongs to
-    const uint32_t base = (blockIdx.x - a.chunk0[i]) * kDenseChunk;
-    const float ss = sc.ss[i], ib = sc.ib[i];
-    float *__restrict__ pp = a.p[i], *__restrict__ pm = a.m[i], *__restrict__ pv = a.v[i];
-    const float *__restrict__ pg = a.g[i];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-        const uint32_t e = base + u * 256 + threadIdx.x;
-        if (e < a.numel[i]) {
-            float p = pp[e], m = pm[e], v = pv[e];
-            adam_update(pg[e] * grad_scale, p, m, v, beta1, beta2, eps, ss, ib);
-            pp[e] = p; pm[e] = m; pv[e] = v;
-        }
-    }
-}
-
-NSIG_EXPORT int opt_adam_dense_host(uint32_t n, float *const *params_host, const float *const *grads_host, float *const *exp_avg_host,
-                                    float *const *exp_avg_sq_host, const uint32_t *numel_host, const float *step_sizes_host, const float *inv_bc2_host,
-                                    float beta1, float beta2, float eps, float grad_scale, nsig_stream_t stream) {
-    NSIG_REQUIRE(params_host && grads_host && exp_avg_host && exp_avg_sq_host && numel_host && step_sizes_host && inv_bc2_host, "opt_adam_dense_host: null pointer");
-    hipStream_t st = as_stream(stream);
-    for (uint32_t first = 0; first < n; first += kDenseMax) {
-        const uint32_t cnt = n - first < (uint32_t)kDenseMax ? n - first : (uint32_t)kDenseMax;
-        DenseAdam a{};
-        DenseScalars sc{};
-        uint32_t chunks = 0;
-        for (uint32_t i = 0; i < cnt; ++i) {
-            const uint32_t j = first + i;
-            NSIG_REQUIRE(params_host[j] && grads_host[j] && exp_avg_host[j] && exp_avg_sq_host[j] && numel_host[j] > 0,
-                         "opt_adam_dense_host: tensor %u has a null pointer or no elements", j);
-            a.p[i] = params_host[j]; a.g[i] = grads_host[j]; a.m[i] = exp_avg_host[j]; a.v[i] = exp_avg_sq_host[j];
-            a.numel[i] = numel_host[j];
-            a.chunk0[i] = chunks;
-            chunks += ceil_div(numel_host[j], kDenseChunk);
-            sc.ss[i] = step_sizes_host[j];
-            sc.ib[i] = inv_bc2_host[j];
-        }
-        a.chunk0[cnt] = chunks;
-        k_adam_dense_host<<<chunks, 256, 0, st>>>(a, cnt, sc, beta1, beta2, eps, grad_scale);
-        if (int e = check_launch("opt_adam_dense_host")) return e;
-    }
-    return NSIG_OK;
-}
-
-// Large tensors (stage 1: sixteen 4 MiB base tables with their own gradients): 4096-element chunks, float4 per lane, sixteen 16-byte loads in
-// flight per lane before the first dependent store, non-temporal loads and moment stores (a 448 MiB stream that nothing re-reads before it is evicted anyway).
-constexpr uint32_t kDenseChunk4 = 4096, kDenseBigNumel = 1u << 16, kDenseRideAlong = 1024;
-__global__ void __launch_bounds__(256) k_adam_dense_v4(DenseAdam a, uint32_t n, const float *__restrict__ scratch, float beta1, float beta2, float eps,
-                                                       float grad_scale) {
-    uint32_t i = 0;
-    while (i + 1 < n && blockIdx.x >= a.chunk0[i + 1]) ++i;   // uniform: which tensor this chunk belongs to
-    const uint32_t base = (blockIdx.x - a.chunk0[i]) * (kDenseChunk4 / 4), n4 = a.numel[i] / 4;
-    const float ss = scratch[a.slot[i]], ib = scratch[kDenseMax + a.slot[i]];
-    float4 *__restrict__ pp = reinterpret_cast<float4 *>(a.p[i]), *__restrict__ pm = reinterpret_cast<float4 *>(a.m[i]), *__restrict__ pv = reinterpret_cast<float4 *>(a.v[i]);
-    const float4 *__restrict__ pg = reinterpret_cast<const float4 *>(a.g[i]);
-    float4 p[4], m[4], v[4], g[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-        const uint32_t e = min(base + u * 256u + threadIdx.x, n4 - 1u);      // clamped: the duplicate is not stored
-        p[u] = ld4<true>(pp + e); m[u] = ld4<true>(pm + e); v[u] = ld4<true>(pv + e); g[u] = ld4<true>(pg + e);
-    }
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-        const uint32_t e = base + u * 256u + threadIdx.x;
-        if (e >= n4) break;
-        adam_update(g[u].x * grad_scale, p[u].x, m[u].x, v[u].x, beta1, beta2, eps, ss, ib);
-        adam_update(g[u].y * grad_scale, p[u].y, m[u].y, v[u].y, beta1, beta2, eps, ss, ib);
-        adam_update(g[u].z * grad_scale, p[u].z, m[u].z, v[u].z, beta1, beta2, eps, ss, ib);
-        adam_update(g[u].w * grad_scale, p[u].w, m[u].w, v[u].w, beta1, beta2, eps, ss, ib);
-        // the moments stream out; the PARAMETERS go through the caches: the next step's encoder gathers from these 64 MiB (same box, two rounds: encoder 139-141 -> 129-131 us,
-        // this pass 95 -> 91, step -0.6 %, on the sparse grid -1.8 %)
-        st4<false>(pp + e, p[u]); st4<true>(pm + e, m[u]); st4<true>(pv + e, v[u]);
-    }
-}
-
-NSIG_EXPORT int opt_adam_dense(uint32_t n, float *const *params_host, const float *const *grads_host, float *const *exp_avg_host,
-                               float *const *exp_avg_sq_host, float *const *steps_host, const uint32_t *numel_host, const float *lr, float beta1,
-                               float beta2, float eps, float grad_scale, float *scratch, nsig_stream_t stream) {
-    NSIG_REQUIRE(params_host && grads_host && exp_avg_host && exp_avg_sq_host && steps_host && numel_host && lr && scratch, "opt_adam_dense: null pointer");
-    hipStream_t st = as_stream(stream);
-    for (uint32_t first = 0; first < n; first += kDenseMax) {   // 32 tensors per group of launches
-        const uint32_t cnt = n - first < (uint32_t)kDenseMax ? n - first : (uint32_t)kDenseMax;
-        DenseAdam all{}, small{}, big{};
-        uint32_t n_small = 0, n_big = 0, chunks_small = 0, chunks_big = 0;
-        auto vectorisable = [&](uint32_t j) {
-            return numel_host[j] % 4 == 0 && aligned16(params_host[j]) && aligned16(grads_host[j]) && aligned16(exp_avg_host[j]) && aligned16(exp_avg_sq_host[j]);
-        };
-        // a group with a large tensor launches the wide kernel anyway: its medium-sized tensors (stage 1: the two MLPs' 3072 + 7168 parameters beside sixteen 4 MiB
-        // tables) ride along as a few more workgroups instead of a launch of their own on the step's serial tail (the same update, element by element)
-        bool any_big = false;
-        for (uint32_t i = 0; i < cnt; ++i) any_big = any_big || (numel_host[first + i] >= kDenseBigNumel && vectorisable(first + i));
-        for (uint32_t i = 0; i < cnt; ++i) {
-            const uint32_t j = first + i;
-            NSIG_REQUIRE(params_host[j] && grads_host[j] && exp_avg_host[j] && exp_avg_sq_host[j] && steps_host[j] && numel_host[j] > 0,
-                         "opt_adam_dense: tensor %u has a null pointer or no elements", j);
-            all.step[i] = steps_host[j];
-            const bool wide = numel_host[j] >= (any_big ? kDenseRideAlong : kDenseBigNumel) && vectorisable(j);
-            DenseAdam &d = wide ? big : small;
-            uint32_t &k = wide ? n_big : n_small, &chunks = wide ? chunks_big : chunks_small;
-            d.p[k] = params_host[j]; d.g[k] = grads_host[j]; d.m[k] = exp_avg_host[j]; d.v[k] = exp_avg_sq_host[j];
-            d.numel[k] = numel_host[j];
-            d.slot[k] = (uint8_t)i;
-            d.chunk0[k] = chunks;
-            chunks += ceil_div(numel_host[j], wide ? kDenseChunk4 : kDenseChunk);
-            ++k;
-        }
-        small.chunk0[n_small] = chunks_small;
-        big.chunk0[n_big] = chunks_big;
-        float *sc = scratch + (size_t)first * 2;
-        k_adam_dense_prepare<<<1, kDenseMax, 0, st>>>(all, cnt, lr, beta1, beta2, sc);
-        if (int e = check_launch("opt_adam_dense (prepare)")) return e;
-        if (n_big) {
-            k_adam_dense_v4<<<chunks_big, 256, 0, st>>>(big, n_big, sc, beta1, beta2, eps, grad_scale);
-            if (int e = check_launch("opt_adam_dense (wide)")) return e;
-        }
-        if (n_small) {
-            k_adam_dense<<<chunks_small, 256, 0, st>>>(small, n_small, sc, beta1, beta2, eps, grad_scale);
-            if (int e = check_launch("opt_adam_dense")) return e;
-        }
-    }
-    return NSIG_OK;
 }
 
 static size_t binned_scratch_bytes(uint32_t M, uint32_t sets) { return (size_t)sets * (sizeof(BinHeader) + (size_t)4 * M * sizeof(uint4)); }
@@ -1636,10 +1244,7 @@ NSIG_EXPORT int hg_scatter_levels(const float *xyzs, float bound, const void *d_
     NSIG_REQUIRE(bound > 0.0f && stride >= M && M < (1u << 28), "hg_scatter_levels: bad bound, stride < M or M >= 2^28");
     NSIG_REQUIRE((reinterpret_cast<uintptr_t>(scratch) & 15) == 0, "hg_scatter_levels: scratch must be 16-byte aligned");
     ScatterTargets tg{};
-    for (int l = 0; l < NSIG_BASE_LEVELS; ++l) {
-        NSIG_REQUIRE(G_host[l], "hg_scatter_levels: table %d has a null pointer", l);
-        tg.g[l] = G_host[l];
-    }
+    if (int e = take_pointers({tg.g}, {G_host}, NSIG_BASE_LEVELS, "hg_scatter_levels", "%s: table %u has a null pointer")) return e;
     hipStream_t st = as_stream(stream);
     if (M == 0) {
         for (int l = 0; l < NSIG_BASE_LEVELS; ++l)
@@ -1718,10 +1323,7 @@ NSIG_EXPORT int hg_levels_scatter(const float *xyzs, uint32_t M, const uint32_t 
                                   float *const *G_host, nsig_stream_t stream) {
     NSIG_REQUIRE(G_host, "hg_levels_scatter: null pointer");
     ScatterTargets tg{};
-    for (int l = 0; l < NSIG_BASE_LEVELS; ++l) {
-        NSIG_REQUIRE(G_host[l], "hg_levels_scatter: table %d has a null pointer", l);
-        tg.g[l] = G_host[l];
-    }
+    if (int e = take_pointers({tg.g}, {G_host}, NSIG_BASE_LEVELS, "hg_levels_scatter", "%s: table %u has a null pointer")) return e;
     hipStream_t st = as_stream(stream);
     if (M == 0) {
         for (int l = 0; l < NSIG_BASE_LEVELS; ++l)
@@ -1742,22 +1344,17 @@ NSIG_EXPORT int hg_levels_scatter_adam(const float *xyzs, uint32_t M, const uint
     NSIG_REQUIRE(xyzs && d_planes && plan, "hg_levels_scatter_adam: null pointer");
     NSIG_REQUIRE((reinterpret_cast<uintptr_t>(plan) & 15) == 0 && (reinterpret_cast<uintptr_t>(d_planes) & 7) == 0 && M < (1u << 27) && bound > 0.0f && stride >= M,
                  "hg_levels_scatter_adam: plan must be 16-byte and d_planes 8-byte aligned, M < 2^27, bound > 0, stride >= M");      // (before the step counts are touched)
-    static_assert(kOwnerAdamMax == kDenseMax, "k_adam_dense_prepare's scratch layout");
+    static_assert(NSIG_BASE_LEVELS <= kAdamGroup, "one group of the prepare launch");
     OwnerAdam adam{};
-    DenseAdam all{};
-    for (int l = 0; l < NSIG_BASE_LEVELS; ++l) {
-        NSIG_REQUIRE(params_host[l] && exp_avg_host[l] && exp_avg_sq_host[l] && steps_host[l], "hg_levels_scatter_adam: table %d has a null pointer", l);
-        NSIG_REQUIRE(aligned16(params_host[l]) && aligned16(exp_avg_host[l]) && aligned16(exp_avg_sq_host[l]), "hg_levels_scatter_adam: table %d must be 16-byte aligned", l);
-        adam.p[l] = params_host[l]; adam.m[l] = exp_avg_host[l]; adam.v[l] = exp_avg_sq_host[l];
-        all.step[l] = steps_host[l];
-    }
+    float *steps[NSIG_BASE_LEVELS];
+    if (int e = take_pointers({adam.p, adam.m, adam.v, steps}, {params_host, exp_avg_host, exp_avg_sq_host, steps_host}, NSIG_BASE_LEVELS, "hg_levels_scatter_adam",
+                              "%s: table %u has a null pointer", "%s: table %u must be 16-byte aligned", 3)) return e;
     adam.scratch = scratch;
     adam.beta1 = beta1; adam.beta2 = beta2; adam.eps = eps; adam.grad_scale = grad_scale;
     adam.on = 1u;
     hipStream_t st = as_stream(stream);
-    return levels_scatter_launch("hg_levels_scatter_adam", xyzs, M, rows_dev, bound, d_planes, stride, plan, ScatterTargets{}, adam, st, [&]() {
-        k_adam_dense_prepare<<<1, kDenseMax, 0, st>>>(all, NSIG_BASE_LEVELS, lr, beta1, beta2, scratch);      // step counts + 1, the two scalars per table
-        return check_launch("hg_levels_scatter_adam (prepare)");
+    return levels_scatter_launch("hg_levels_scatter_adam", xyzs, M, rows_dev, bound, d_planes, stride, plan, ScatterTargets{}, adam, st, [&]() {      // step counts + 1, the two scalars per table
+        return adam_prepare_launch(steps, NSIG_BASE_LEVELS, lr, beta1, beta2, scratch, st, "hg_levels_scatter_adam (prepare)");
     });
 }
 

@@ -1,0 +1,379 @@
+// The optimiser passes for gfx950, every opt_* entry point of include/nerfsig.h: torch.optim.Adam's update (adam.h) of the D selected codebook tables from their one
+// shared gradient (opt_codebook_adam[_sel[_next]]) and of any list of dense tensors in launch groups of kAdamGroup (opt_adam_dense[_host]); torch_ema's moving average
+// of the parameters (opt_ema_update).  The scatter owners' fused form of the update, hg_levels_scatter_adam, stays in hashgrid.hip and borrows adam_prepare_launch.
+#include "adam.h"
+
+namespace nsig {
+
+// ----------------------------------------------------------------------------- the codebook tables (shared gradient)
+
+// Fused Adam over the D selected tables (shared gradient): float4 per lane, D x (param, exp_avg, exp_avg_sq) streams.
+struct AdamPtrs {
+    float *p[NSIG_MAX_MESSAGE_DIM];
+    float *m[NSIG_MAX_MESSAGE_DIM];
+    float *v[NSIG_MAX_MESSAGE_DIM];
+    float step_size[NSIG_MAX_MESSAGE_DIM];
+    float inv_bc2_sqrt[NSIG_MAX_MESSAGE_DIM];
+};
+
+__global__ void __launch_bounds__(256) k_codebook_adam(const float4 *__restrict__ G, AdamPtrs a, uint32_t D, float beta1, float beta2, float eps,
+                                                       float grad_scale) {
+    const uint32_t e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= NSIG_TABLE_ROWS / 2) return;
+    float4 g = G[e];
+    g.x *= grad_scale; g.y *= grad_scale; g.z *= grad_scale; g.w *= grad_scale;
+    for (uint32_t i = 0; i < D; ++i) {
+        float4 *pp = reinterpret_cast<float4 *>(a.p[i]) + e, *pm = reinterpret_cast<float4 *>(a.m[i]) + e, *pv = reinterpret_cast<float4 *>(a.v[i]) + e;
+        float4 p = *pp, m = *pm, v = *pv;
+        adam_update4(g, p, m, v, beta1, beta2, eps, a.step_size[i], a.inv_bc2_sqrt[i]);
+        *pp = p; *pm = m; *pv = v;
+    }
+}
+
+// device-side table selection (every launch argument independent of the message: the enclosing step can be captured in a hipGraph)
+struct AdamPairPtrs {
+    float *p[2 * NSIG_MAX_MESSAGE_DIM];
+    float *m[2 * NSIG_MAX_MESSAGE_DIM];
+    float *v[2 * NSIG_MAX_MESSAGE_DIM];
+};
+struct StepPtrs {
+    float *s[2 * NSIG_MAX_MESSAGE_DIM];
+};
+
+// one thread per bit: advance the selected table's step count and derive its bias-correction scalars
+__global__ void k_adam_prepare(StepPtrs steps, const float *__restrict__ message, uint32_t D, const float *__restrict__ lr, float beta1, float beta2,
+                               float *__restrict__ scratch) {
+    const uint32_t i = threadIdx.x;
+    if (i >= D) return;
+    float *sp = steps.s[2 * i + (message[i] != 0.0f)];
+    const float step = *sp + 1.0f;
+    *sp = step;
+    adam_step_scalars(step, lr, beta1, beta2, scratch, i, D);
+}
+
+// NEXT: the same pass also produces the pre-summed codebook of the NEXT step's message, S_next = sum_i table[2i + next_i]: where the
+// next bit equals the current one the freshly updated row is already in registers, otherwise the partner table's row is read
+// (about D/2 extra 4 MiB streams: +9 % traffic) -- instead of a separate 128 MiB pre-sum pass at the head of the next step.
+// The sum keeps the table order, so S_next is bit-identical to k_codebook_presum_sel's.
+template <bool NEXT, bool NT>
+__global__ void __launch_bounds__(256) k_codebook_adam_sel(const float4 *__restrict__ G, AdamPairPtrs a, const float *__restrict__ message,
+                                                           const float *__restrict__ scratch, uint32_t D, float beta1, float beta2, float eps,
+                                                           float grad_scale, const float *__restrict__ next_message, float4 *__restrict__ S_next) {
+    const uint32_t e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= NSIG_TABLE_ROWS / 2) return;
+    float4 g = ld4<NT>(G + e);
+    g.x *= grad_scale; g.y *= grad_scale; g.z *= grad_scale; g.w *= grad_scale;
+    float4 acc = {0.f, 0.f, 0.f, 0.f};
+    const float4 zero = {0.f, 0.f, 0.f, 0.f};
+    // two tables per trip: six 16-byte loads in flight per thread before the first dependent store
+    uint32_t i = 0;
+    for (; i + 2 <= D; i += 2) {
+        const uint32_t j0 = 2 * i + (message[i] != 0.0f), j1 = 2 * i + 2 + (message[i + 1] != 0.0f);
+        float4 *pp0 = reinterpret_cast<float4 *>(a.p[j0]) + e, *pm0 = reinterpret_cast<float4 *>(a.m[j0]) + e, *pv0 = reinterpret_cast<float4 *>(a.v[j0]) + e;
+        float4 *pp1 = reinterpret_cast<float4 *>(a.p[j1]) + e, *pm1 = reinterpret_cast<float4 *>(a.m[j1]) + e, *pv1 = reinterpret_cast<float4 *>(a.v[j1]) + e;
+        bool other0 = false, other1 = false;      // wave-uniform
+        float4 o0 = zero, o1 = zero;
+        if (NEXT) {
+            other0 = (next_message[i] != 0.0f) != (message[i] != 0.0f);
+            other1 = (next_message[i + 1] != 0.0f) != (message[i + 1] != 0.0f);
+            if (other0) o0 = ld4<NT>(reinterpret_cast<const float4 *>(a.p[j0 ^ 1u]) + e);
+            if (other1) o1 = ld4<NT>(reinterpret_cast<const float4 *>(a.p[j1 ^ 1u]) + e);
+        }
+        float4 p0 = ld4<NT>(pp0), m0 = ld4<NT>(pm0), v0 = ld4<NT>(pv0), p1 = ld4<NT>(pp1), m1 = ld4<NT>(pm1), v1 = ld4<NT>(pv1);
+        const float ss0 = scratch[i], ib0 = scratch[D + i], ss1 = scratch[i + 1], ib1 = scratch[D + i + 1];
+        adam_update4(g, p0, m0, v0, beta1, beta2, eps, ss0, ib0);
+        adam_update4(g, p1, m1, v1, beta1, beta2, eps, ss1, ib1);
+        st4<NT>(pp0, p0); st4<NT>(pm0, m0); st4<NT>(pv0, v0); st4<NT>(pp1, p1); st4<NT>(pm1, m1); st4<NT>(pv1, v1);
+        if (NEXT) {
+            const float4 c0 = other0 ? o0 : p0, c1 = other1 ? o1 : p1;
+            acc.x += c0.x; acc.y += c0.y; acc.z += c0.z; acc.w += c0.w;
+            acc.x += c1.x; acc.y += c1.y; acc.z += c1.z; acc.w += c1.w;
+        }
+    }
+    for (; i < D; ++i) {
+        const uint32_t j = 2 * i + (message[i] != 0.0f);
+        float4 *pp = reinterpret_cast<float4 *>(a.p[j]) + e, *pm = reinterpret_cast<float4 *>(a.m[j]) + e, *pv = reinterpret_cast<float4 *>(a.v[j]) + e;
+        bool other = false;
+        float4 o = zero;
+        if (NEXT) {
+            other = (next_message[i] != 0.0f) != (message[i] != 0.0f);
+            if (other) o = ld4<NT>(reinterpret_cast<const float4 *>(a.p[j ^ 1u]) + e);
+        }
+        float4 p = ld4<NT>(pp), m = ld4<NT>(pm), v = ld4<NT>(pv);
+        adam_update4(g, p, m, v, beta1, beta2, eps, scratch[i], scratch[D + i]);
+        st4<NT>(pp, p); st4<NT>(pm, m); st4<NT>(pv, v);
+        if (NEXT) {
+            const float4 c = other ? o : p;
+            acc.x += c.x; acc.y += c.y; acc.z += c.z; acc.w += c.w;
+        }
+    }
+    if (NEXT) S_next[e] = acc;
+}
+
+// ----------------------------------------------------------------------------- EMA of the parameters
+// The stage-1 trainer keeps an exponential moving average of every parameter (main_nerf.py:130 `ema_decay=0.95`; utils.py:389-390 torch_ema's
+// ExponentialMovingAverage, updated after every optimiser step, :761-762/:892-893) and evaluates / checkpoints with it (:801-811).  torch_ema 0.3's update(), with
+// its default warm-up (use_num_updates): num_updates += 1; decay = min(decay, (1 + num_updates) / (10 + num_updates)); then for every parameter
+//     tmp = shadow - param;  tmp *= (1 - decay);  shadow -= tmp
+// -- here one launch over all tensors, the update count read from the captured loop's device step counter (which the step's loss kernel has already advanced).
+constexpr int kEmaMax = 32;
+constexpr uint32_t kEmaChunk = 4096;      // elements per workgroup
+struct DenseEma {
+    const float *p[kEmaMax];
+    float *s[kEmaMax];
+    uint32_t numel[kEmaMax], chunk0[kEmaMax + 1];
+};
+__global__ void __launch_bounds__(256) k_ema_dense(DenseEma a, uint32_t n, const uint32_t *__restrict__ num_updates, double decay) {
+    const uint32_t t = chunk_owner(a.chunk0, n);
+    const double nu = (double)*num_updates;
+    const float w = (float)(1.0 - fmin(decay, (1.0 + nu) / (10.0 + nu)));      // (python: a double, handed to mul_ as a float32 scalar)
+    const uint32_t first = (blockIdx.x - a.chunk0[t]) * kEmaChunk, numel = a.numel[t];
+    const float *__restrict__ p = a.p[t];
+    float *__restrict__ s = a.s[t];
+    if (numel % 4u == 0 && ((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(s)) & 15) == 0) {      // (uniform)
+        for (uint32_t i = first + 4u * threadIdx.x; i < min(numel, first + kEmaChunk); i += 1024u) {
+            const float4 pv = *reinterpret_cast<const float4 *>(p + i);
+            float4 sv = *reinterpret_cast<const float4 *>(s + i);
+            sv.x = sv.x - (sv.x - pv.x) * w; sv.y = sv.y - (sv.y - pv.y) * w; sv.z = sv.z - (sv.z - pv.z) * w; sv.w = sv.w - (sv.w - pv.w) * w;
+            *reinterpret_cast<float4 *>(s + i) = sv;
+        }
+    } else {
+        for (uint32_t i = first + threadIdx.x; i < min(numel, first + kEmaChunk); i += 256u) s[i] = s[i] - (s[i] - p[i]) * w;
+    }
+}
+
+}  // namespace nsig
+
+using namespace nsig;
+
+// ----------------------------------------------------------------------------- dense multi-tensor Adam (the decoder's parameters, stage 1's tables and MLPs)
+
+// torch's fused multi-tensor Adam walks 64K-element chunks, one workgroup each: the decoder's 29 tensors (262k parameters) become
+// ~30 workgroups that each stream 64K elements serially (28 us).  Here a chunk is 1024 elements, so the same update is ~260
+// workgroups of one pass (~3 us).
+constexpr uint32_t kDenseChunk = 1024;
+struct DenseAdam {
+    float *p[kAdamGroup], *m[kAdamGroup], *v[kAdamGroup], *step[kAdamGroup];
+    const float *g[kAdamGroup];
+    uint32_t numel[kAdamGroup], chunk0[kAdamGroup + 1];   // chunk0: first chunk of tensor i (chunk_owner)
+    uint8_t slot[kAdamGroup];                             // where the tensor's two step scalars sit in the scratch (k_adam_dense_prepare's index)
+};
+
+__global__ void k_adam_dense_prepare(DenseAdam a, uint32_t n, const float *__restrict__ lr, float beta1, float beta2, float *__restrict__ scratch) {
+    const uint32_t i = threadIdx.x;
+    if (i >= n) return;
+    const float step = *a.step[i] + 1.0f;
+    *a.step[i] = step;
+    adam_step_scalars(step, lr, beta1, beta2, scratch, i, kAdamGroup);
+}
+
+// one 1024-element chunk, element by element; scalars(i, ss, ib): the two step scalars of tensor i, wherever the launch keeps them
+template <typename Scalars>
+__device__ __forceinline__ void adam_dense_chunk(const DenseAdam &a, uint32_t n, Scalars scalars, float beta1, float beta2, float eps, float grad_scale) {
+    const uint32_t i = chunk_owner(a.chunk0, n);
+    const uint32_t base = (blockIdx.x - a.chunk0[i]) * kDenseChunk;
+    float ss, ib;
+    scalars(i, ss, ib);
+    float *__restrict__ pp = a.p[i], *__restrict__ pm = a.m[i], *__restrict__ pv = a.v[i];
+    const float *__restrict__ pg = a.g[i];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+        const uint32_t e = base + u * 256 + threadIdx.x;
+        if (e < a.numel[i]) {
+            float p = pp[e], m = pm[e], v = pv[e];
+            adam_update(pg[e] * grad_scale, p, m, v, beta1, beta2, eps, ss, ib);
+            pp[e] = p; pm[e] = m; pv[e] = v;
+        }
+    }
+}
+
+__global__ void __launch_bounds__(256) k_adam_dense(DenseAdam a, uint32_t n, const float *__restrict__ scratch, float beta1, float beta2, float eps,
+                                                    float grad_scale) {
+    adam_dense_chunk(a, n, [&](uint32_t i, float &ss, float &ib) { ss = scratch[a.slot[i]], ib = scratch[kAdamGroup + a.slot[i]]; }, beta1, beta2, eps, grad_scale);
+}
+
+// The same update with the per-tensor step size lr / (1 - beta1^t) and 1 / sqrt(1 - beta2^t) computed by the HOST (torch.optim.Adam's non-capturable state
+// keeps its step counts in host tensors: opt_adam_dense_host, the drop-in model's optimiser hook).
+struct DenseScalars {
+    float ss[kAdamGroup], ib[kAdamGroup];
+};
+__global__ void __launch_bounds__(256) k_adam_dense_host(DenseAdam a, uint32_t n, DenseScalars sc, float beta1, float beta2, float eps, float grad_scale) {
+    adam_dense_chunk(a, n, [&](uint32_t i, float &ss, float &ib) { ss = sc.ss[i], ib = sc.ib[i]; }, beta1, beta2, eps, grad_scale);
+}
+
+// Large tensors (stage 1: sixteen 4 MiB base tables with their own gradients): 4096-element chunks, float4 per lane, sixteen 16-byte loads in
+// flight per lane before the first dependent store, non-temporal loads and moment stores (a 448 MiB stream that nothing re-reads before it is evicted anyway).
+constexpr uint32_t kDenseChunk4 = 4096, kDenseBigNumel = 1u << 16, kDenseRideAlong = 1024;
+__global__ void __launch_bounds__(256) k_adam_dense_v4(DenseAdam a, uint32_t n, const float *__restrict__ scratch, float beta1, float beta2, float eps,
+                                                       float grad_scale) {
+    const uint32_t i = chunk_owner(a.chunk0, n);
+    const uint32_t base = (blockIdx.x - a.chunk0[i]) * (kDenseChunk4 / 4), n4 = a.numel[i] / 4;
+    const float ss = scratch[a.slot[i]], ib = scratch[kAdamGroup + a.slot[i]];
+    float4 *__restrict__ pp = reinterpret_cast<float4 *>(a.p[i]), *__restrict__ pm = reinterpret_cast<float4 *>(a.m[i]), *__restrict__ pv = reinterpret_cast<float4 *>(a.v[i]);
+    const float4 *__restrict__ pg = reinterpret_cast<const float4 *>(a.g[i]);
+    float4 p[4], m[4], v[4], g[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+        const uint32_t e = min(base + u * 256u + threadIdx.x, n4 - 1u);      // clamped: the duplicate is not stored
+        p[u] = ld4<true>(pp + e); m[u] = ld4<true>(pm + e); v[u] = ld4<true>(pv + e); g[u] = ld4<true>(pg + e);
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+        const uint32_t e = base + u * 256u + threadIdx.x;
+        if (e >= n4) break;
+        adam_update4(g[u], p[u], m[u], v[u], beta1, beta2, eps, ss, ib, grad_scale);
+        // the moments stream out; the PARAMETERS go through the caches: the next step's encoder gathers from these 64 MiB (same box, two rounds: encoder 139-141 -> 129-131 us,
+        // this pass 95 -> 91, step -0.6 %, on the sparse grid -1.8 %)
+        st4<false>(pp + e, p[u]); st4<true>(pm + e, m[u]); st4<true>(pv + e, v[u]);
+    }
+}
+
+// Tensor k (numel elements, `chunk` per workgroup) joins a launch's chunk table: chunk0[k] its first workgroup, chunk0[k + 1] the grid so far (the structs start zeroed)
+static void chunk_table_append(uint32_t *numel_tab, uint32_t *chunk0, uint32_t k, uint32_t numel, uint32_t chunk) {
+    numel_tab[k] = numel;
+    chunk0[k + 1] = chunk0[k] + ceil_div(numel, chunk);
+}
+
+static const char *const kNullTable = "%s: table %u has a null pointer", *const kMisalignedTable = "%s: table %u is not 16-byte aligned";
+
+NSIG_EXPORT int opt_codebook_adam(const float *G, float *const *params_host, float *const *exp_avg_host, float *const *exp_avg_sq_host,
+                                  uint32_t D, float beta1, float beta2, float eps, const float *step_size_host,
+                                  const float *inv_bc2_sqrt_host, float grad_scale, nsig_stream_t stream) {
+    NSIG_REQUIRE(G && params_host && exp_avg_host && exp_avg_sq_host && step_size_host && inv_bc2_sqrt_host, "opt_codebook_adam: null pointer");
+    NSIG_REQUIRE(D >= 1 && D <= NSIG_MAX_MESSAGE_DIM, "opt_codebook_adam: D=%u out of range", D);
+    NSIG_REQUIRE(aligned16(G), "opt_codebook_adam: G must be 16-byte aligned");
+    AdamPtrs a{};
+    if (int e = take_pointers({a.p, a.m, a.v}, {params_host, exp_avg_host, exp_avg_sq_host}, D, "opt_codebook_adam", kNullTable, kMisalignedTable)) return e;
+    for (uint32_t i = 0; i < D; ++i) {
+        a.step_size[i] = step_size_host[i];
+        a.inv_bc2_sqrt[i] = inv_bc2_sqrt_host[i];
+    }
+    k_codebook_adam<<<NSIG_TABLE_ROWS / 2 / 256, 256, 0, as_stream(stream)>>>(reinterpret_cast<const float4 *>(G), a, D, beta1, beta2, eps, grad_scale);
+    return check_launch("opt_codebook_adam");
+}
+
+static int codebook_adam_sel(const char *who, const float *G, float *const *params_host, float *const *exp_avg_host, float *const *exp_avg_sq_host,
+                             float *const *steps_host, const float *message, uint32_t D, const float *lr, float beta1, float beta2,
+                             float eps, float grad_scale, float *scratch, const float *next_message, float *S_next, nsig_stream_t stream) {
+    NSIG_REQUIRE(G && params_host && exp_avg_host && exp_avg_sq_host && steps_host && message && lr && scratch, "%s: null pointer", who);
+    NSIG_REQUIRE(D >= 1 && D <= NSIG_MAX_MESSAGE_DIM, "%s: D=%u out of range", who, D);
+    NSIG_REQUIRE(aligned16(G), "%s: G must be 16-byte aligned", who);
+    AdamPairPtrs a{};
+    StepPtrs s{};
+    if (int e = take_pointers({a.p, a.m, a.v, s.s}, {params_host, exp_avg_host, exp_avg_sq_host, steps_host}, 2 * D, who, kNullTable, kMisalignedTable, 3)) return e;
+    hipStream_t st = as_stream(stream);
+    k_adam_prepare<<<1, NSIG_MAX_MESSAGE_DIM, 0, st>>>(s, message, D, lr, beta1, beta2, scratch);
+    if (int e = check_launch(who)) return e;
+    // non-temporal accesses (same-box A/B of the bench step, three pairs: 1.124-1.138 ms against 1.151-1.157 with plain accesses; the kernel alone takes
+    // the same 160-164 us either way, the next step's gather gains)
+    if (next_message)
+        k_codebook_adam_sel<true, true><<<NSIG_TABLE_ROWS / 2 / 256, 256, 0, st>>>(reinterpret_cast<const float4 *>(G), a, message, scratch, D, beta1, beta2, eps,
+                                                                                 grad_scale, next_message, reinterpret_cast<float4 *>(S_next));
+    else
+        k_codebook_adam_sel<false, false><<<NSIG_TABLE_ROWS / 2 / 256, 256, 0, st>>>(reinterpret_cast<const float4 *>(G), a, message, scratch, D, beta1, beta2, eps,
+                                                                               grad_scale, nullptr, nullptr);
+    return check_launch(who);
+}
+
+NSIG_EXPORT int opt_codebook_adam_sel(const float *G, float *const *params_host, float *const *exp_avg_host, float *const *exp_avg_sq_host,
+                                      float *const *steps_host, const float *message, uint32_t D, const float *lr, float beta1, float beta2,
+                                      float eps, float grad_scale, float *scratch, nsig_stream_t stream) {
+    return codebook_adam_sel("opt_codebook_adam_sel", G, params_host, exp_avg_host, exp_avg_sq_host, steps_host, message, D, lr, beta1, beta2, eps,
+                             grad_scale, scratch, nullptr, nullptr, stream);
+}
+
+NSIG_EXPORT int opt_codebook_adam_sel_next(const float *G, float *const *params_host, float *const *exp_avg_host, float *const *exp_avg_sq_host,
+                                           float *const *steps_host, const float *message, uint32_t D, const float *lr, float beta1, float beta2,
+                                           float eps, float grad_scale, float *scratch, const float *next_message, float *S_next,
+                                           nsig_stream_t stream) {
+    NSIG_REQUIRE(next_message && S_next && aligned16(S_next), "opt_codebook_adam_sel_next: next_message / S_next null or S_next not 16-byte aligned");
+    return codebook_adam_sel("opt_codebook_adam_sel_next", G, params_host, exp_avg_host, exp_avg_sq_host, steps_host, message, D, lr, beta1, beta2, eps,
+                             grad_scale, scratch, next_message, S_next, stream);
+}
+
+int nsig::adam_prepare_launch(float *const *steps_host, uint32_t n, const float *lr, float beta1, float beta2, float *scratch, hipStream_t st, const char *who) {
+    DenseAdam all{};
+    for (uint32_t i = 0; i < n; ++i) all.step[i] = steps_host[i];
+    k_adam_dense_prepare<<<1, kAdamGroup, 0, st>>>(all, n, lr, beta1, beta2, scratch);
+    return check_launch(who);
+}
+
+NSIG_EXPORT int opt_adam_dense_host(uint32_t n, float *const *params_host, const float *const *grads_host, float *const *exp_avg_host,
+                                    float *const *exp_avg_sq_host, const uint32_t *numel_host, const float *step_sizes_host, const float *inv_bc2_host,
+                                    float beta1, float beta2, float eps, float grad_scale, nsig_stream_t stream) {
+    NSIG_REQUIRE(params_host && grads_host && exp_avg_host && exp_avg_sq_host && numel_host && step_sizes_host && inv_bc2_host, "opt_adam_dense_host: null pointer");
+    hipStream_t st = as_stream(stream);
+    for (uint32_t first = 0; first < n; first += kAdamGroup) {
+        const uint32_t cnt = n - first < (uint32_t)kAdamGroup ? n - first : (uint32_t)kAdamGroup;
+        DenseAdam a{};
+        DenseScalars sc{};
+        for (uint32_t i = 0; i < cnt; ++i) {
+            const uint32_t j = first + i;
+            NSIG_REQUIRE(params_host[j] && grads_host[j] && exp_avg_host[j] && exp_avg_sq_host[j] && numel_host[j] > 0,
+                         "opt_adam_dense_host: tensor %u has a null pointer or no elements", j);
+            a.p[i] = params_host[j]; a.g[i] = grads_host[j]; a.m[i] = exp_avg_host[j]; a.v[i] = exp_avg_sq_host[j];
+            chunk_table_append(a.numel, a.chunk0, i, numel_host[j], kDenseChunk);
+            sc.ss[i] = step_sizes_host[j];
+            sc.ib[i] = inv_bc2_host[j];
+        }
+        k_adam_dense_host<<<a.chunk0[cnt], 256, 0, st>>>(a, cnt, sc, beta1, beta2, eps, grad_scale);
+        if (int e = check_launch("opt_adam_dense_host")) return e;
+    }
+    return NSIG_OK;
+}
+
+NSIG_EXPORT int opt_adam_dense(uint32_t n, float *const *params_host, const float *const *grads_host, float *const *exp_avg_host,
+                               float *const *exp_avg_sq_host, float *const *steps_host, const uint32_t *numel_host, const float *lr, float beta1,
+                               float beta2, float eps, float grad_scale, float *scratch, nsig_stream_t stream) {
+    NSIG_REQUIRE(params_host && grads_host && exp_avg_host && exp_avg_sq_host && steps_host && numel_host && lr && scratch, "opt_adam_dense: null pointer");
+    hipStream_t st = as_stream(stream);
+    for (uint32_t first = 0; first < n; first += kAdamGroup) {   // 32 tensors per group of launches
+        const uint32_t cnt = n - first < (uint32_t)kAdamGroup ? n - first : (uint32_t)kAdamGroup;
+        DenseAdam small{}, big{};
+        uint32_t n_small = 0, n_big = 0;
+        auto vectorisable = [&](uint32_t j) {
+            return numel_host[j] % 4 == 0 && aligned16(params_host[j]) && aligned16(grads_host[j]) && aligned16(exp_avg_host[j]) && aligned16(exp_avg_sq_host[j]);
+        };
+        // a group with a large tensor launches the wide kernel anyway: its medium-sized tensors (stage 1: the two MLPs' 3072 + 7168 parameters beside sixteen 4 MiB
+        // tables) ride along as a few more workgroups instead of a launch of their own on the step's serial tail (the same update, element by element)
+        bool any_big = false;
+        for (uint32_t i = 0; i < cnt; ++i) any_big = any_big || (numel_host[first + i] >= kDenseBigNumel && vectorisable(first + i));
+        for (uint32_t i = 0; i < cnt; ++i) {
+            const uint32_t j = first + i;
+            NSIG_REQUIRE(params_host[j] && grads_host[j] && exp_avg_host[j] && exp_avg_sq_host[j] && steps_host[j] && numel_host[j] > 0,
+                         "opt_adam_dense: tensor %u has a null pointer or no elements", j);
+            const bool wide = numel_host[j] >= (any_big ? kDenseRideAlong : kDenseBigNumel) && vectorisable(j);
+            DenseAdam &d = wide ? big : small;
+            uint32_t &k = wide ? n_big : n_small;
+            d.p[k] = params_host[j]; d.g[k] = grads_host[j]; d.m[k] = exp_avg_host[j]; d.v[k] = exp_avg_sq_host[j];
+            d.slot[k] = (uint8_t)i;
+            chunk_table_append(d.numel, d.chunk0, k, numel_host[j], wide ? kDenseChunk4 : kDenseChunk);
+            ++k;
+        }
+        float *sc = scratch + (size_t)first * 2;
+        if (int e = adam_prepare_launch(steps_host + first, cnt, lr, beta1, beta2, sc, st, "opt_adam_dense (prepare)")) return e;
+        if (n_big) {
+            k_adam_dense_v4<<<big.chunk0[n_big], 256, 0, st>>>(big, n_big, sc, beta1, beta2, eps, grad_scale);
+            if (int e = check_launch("opt_adam_dense (wide)")) return e;
+        }
+        if (n_small) {
+            k_adam_dense<<<small.chunk0[n_small], 256, 0, st>>>(small, n_small, sc, beta1, beta2, eps, grad_scale);
+            if (int e = check_launch("opt_adam_dense")) return e;
+        }
+    }
+    return NSIG_OK;
+}
+
+NSIG_EXPORT int opt_ema_update(uint32_t n, const float *const *params_host, float *const *shadow_host, const uint32_t *numel_host, const uint32_t *num_updates,
+                               double decay, nsig_stream_t stream) {
+    NSIG_REQUIRE(params_host && shadow_host && numel_host && num_updates, "opt_ema_update: null pointer");
+    NSIG_REQUIRE(n >= 1 && n <= (uint32_t)kEmaMax && decay >= 0.0 && decay <= 1.0, "opt_ema_update: 1 .. %d tensors, decay in [0, 1]", kEmaMax);
+    DenseEma a{};
+    for (uint32_t i = 0; i < n; ++i) {
+        NSIG_REQUIRE(params_host[i] && shadow_host[i] && numel_host[i] > 0, "opt_ema_update: tensor %u has a null pointer or no elements", i);
+        a.p[i] = params_host[i]; a.s[i] = shadow_host[i];
+        chunk_table_append(a.numel, a.chunk0, i, numel_host[i], kEmaChunk);
+    }
+    k_ema_dense<<<a.chunk0[n], 256, 0, as_stream(stream)>>>(a, n, num_updates, decay);
+    return check_launch("opt_ema_update");
+}

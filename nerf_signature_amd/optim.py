@@ -1,19 +1,57 @@
 """CodebookAdam: torch.optim.Adam (the optimiser the reference builds, main_nerf_wtmk.py:110) whose update of the
 selected codebook tables is one native pass (opt_codebook_adam).
 
-Every selected table carries the same gradient G (csrc/hashgrid.hip), so instead of materialising D dense
+Every selected table carries the same gradient G (csrc/hashgrid.hip computes it), so instead of materialising D dense
 gradients and running the generic multi-tensor Adam over them (~10 passes over 128 MiB), one kernel reads G once
 and updates param / exp_avg / exp_avg_sq of the D tables in place.  Semantics are torch.optim.Adam's: per-table
 step counts (a table's step advances only when it is selected, exactly like a parameter whose grad is None is
 skipped), bias correction, eps outside the square root, no weight decay / amsgrad.  State lives in `self.state`
 in torch's own format, so `state_dict()` / `load_state_dict()` interoperate with a plain Adam checkpoint.
-Parameters that have an ordinary `.grad` (the decoder) are handled by the inherited `step()`."""
+Parameters that have an ordinary `.grad` (the decoder) are handled by the inherited `step()`.
+
+The native passes are the opt_* entry points of csrc/optim.hip (the arithmetic: csrc/adam.h); _adam_state, _adam_dense, _plain_group and _Handle are what they share here."""
 import ctypes
 import math
 
 import torch
 
 from . import _native as nv
+
+
+def _adam_state(optimizer, p, device_count):
+    """torch.optim.Adam's state of `p`, created on first use as Adam._init_group creates it: the step count a host tensor (the default format), or -- device_count --
+    a zero-dimensional tensor beside the parameter (the capturable format, which the passes that advance it on the device need); an existing host count moves there."""
+    st = optimizer.state[p]
+    if len(st) == 0:
+        st["step"] = torch.zeros((), dtype=torch.float32, device=p.device) if device_count else torch.tensor(0.0, dtype=torch.float32)
+        st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+        st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+    elif device_count and not st["step"].is_cuda:
+        st["step"] = st["step"].to(p.device)
+    return st
+
+
+def _plain_group(group):
+    """Adam as the reference configures it (main_nerf_wtmk.py:110, main_nerf.py:122), which is what the native passes compute: no weight decay / amsgrad / maximize."""
+    return not (group.get("weight_decay", 0) or group.get("amsgrad", False) or group.get("maximize", False))
+
+
+class _Handle:
+    """What a hook pass needs of one parameter at every step, looked up once: its host-count Adam state, the addresses, and the step count seen through numpy
+    (+= 1 without a dispatcher call; None for a count that the captured loop left on the device)."""
+    __slots__ = ("p", "state", "exp_avg", "exp_avg_sq", "step", "count", "p_ptr", "m_ptr", "v_ptr", "numel")
+
+    def __init__(self, optimizer, p):
+        st = _adam_state(optimizer, p, device_count=False)
+        self.p, self.state, self.exp_avg, self.exp_avg_sq, self.step = p, st, st["exp_avg"], st["exp_avg_sq"], st["step"]
+        self.count = None if self.step.is_cuda else self.step.numpy()
+        self.p_ptr, self.m_ptr, self.v_ptr, self.numel = p.data_ptr(), self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(), p.numel()
+
+    def fresh(self, optimizer, p):
+        """Against the LIVE state: optimizer.load_state_dict() replaces the inner dicts and their tensors (a cached dict would keep pointing at the orphaned moments)."""
+        st = self.state
+        return (self.p is p and optimizer.state.get(p) is st and st.get("exp_avg") is self.exp_avg and st.get("exp_avg_sq") is self.exp_avg_sq
+                and st.get("step") is self.step)
 
 
 def fused_shared_step(optimizer, group, selected, G, grad_scale=1.0):
@@ -24,27 +62,19 @@ def fused_shared_step(optimizer, group, selected, G, grad_scale=1.0):
     D = len(selected)
     vp = ctypes.c_void_p * D
     pp, pm, pv, step_sizes, inv_bc2 = vp(), vp(), vp(), (ctypes.c_float * D)(), (ctypes.c_float * D)()
-    handles = optimizer.__dict__.setdefault("_nsig_table_handles", {})      # id(table) -> (table, state dict, exp_avg, exp_avg_sq, their addresses, step count)
-    state = optimizer.state
+    handles = optimizer.__dict__.setdefault("_nsig_table_handles", {})      # id(table) -> _Handle
     for i, p in enumerate(selected):
         h = handles.get(id(p))
-        # validated against the LIVE state: optimizer.load_state_dict() replaces the inner dicts and their tensors (a cached dict would
-        # keep pointing at the orphaned moments)
-        if h is None or h[0] is not p or state.get(p) is not h[1] or h[1].get("exp_avg") is not h[2] or h[1].get("exp_avg_sq") is not h[3] or h[1].get("step") is not h[8]:
-            st = optimizer.state[p]
-            if len(st) == 0:   # torch.optim.Adam._init_group
-                st["step"] = torch.tensor(0.0, dtype=torch.float32)
-                st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
-                st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
-            for t in (p, st["exp_avg"], st["exp_avg_sq"]):
+        if h is None or not h.fresh(optimizer, p):
+            h = _Handle(optimizer, p)
+            for t in (p, h.exp_avg, h.exp_avg_sq):
                 if not (t.is_contiguous() and t.dtype == torch.float32):
                     raise ValueError("fused_shared_step: tables and their Adam moments must be contiguous float32 tensors")
-            h = handles[id(p)] = (p, st, st["exp_avg"], st["exp_avg_sq"], p.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(),
-                                  None if st["step"].is_cuda else st["step"].numpy(), st["step"])
-        pp[i], pm[i], pv[i] = h[4], h[5], h[6]
-        count = h[7]                     # the step count, torch's host tensor seen through numpy: += 1 without a dispatcher call (D of them per step)
+            handles[id(p)] = h
+        pp[i], pm[i], pv[i] = h.p_ptr, h.m_ptr, h.v_ptr
+        count = h.count                  # the step count, torch's host tensor seen through numpy: += 1 without a dispatcher call (D of them per step)
         if count is None:                # (a count left on the device by the captured loop: one synchronising read each)
-            count = h[8]
+            count = h.step
         count += 1
         step = float(count)
         step_sizes[i] = lr / (1.0 - beta1 ** step)
@@ -86,9 +116,8 @@ def _shared_gradient_pre_step(optimizer, args, kwargs):
                 break
         if group is None:
             continue                                    # not this optimiser's parameter
-        plain = (isinstance(optimizer, torch.optim.Adam) and not group.get("weight_decay", 0) and not group.get("amsgrad", False) and not group.get("maximize", False)
-                 and not group.get("capturable", False) and not group.get("differentiable", False) and not torch.is_tensor(group["lr"])
-                 and all(id(t) in ids[1] for t in sink.live))
+        plain = (isinstance(optimizer, torch.optim.Adam) and _plain_group(group) and not group.get("capturable", False) and not group.get("differentiable", False)
+                 and not torch.is_tensor(group["lr"]) and all(id(t) in ids[1] for t in sink.live))
         if not plain:
             sink.dissolve()                             # the optimiser sees D ordinary dense gradients
             continue
@@ -106,8 +135,7 @@ def _dense_takeover(optimizer):
     Groups or tensors this does not cover (weight decay, amsgrad, capturable, CPU / non-fp32 / non-contiguous tensors) are left to the optimiser."""
     aside = []
     for group in optimizer.param_groups:
-        if (group.get("weight_decay", 0) or group.get("amsgrad", False) or group.get("maximize", False) or group.get("capturable", False)
-                or group.get("differentiable", False) or torch.is_tensor(group["lr"])):
+        if not _plain_group(group) or group.get("capturable", False) or group.get("differentiable", False) or torch.is_tensor(group["lr"]):
             continue
         ps = [p for p in group["params"] if p.grad is not None and p.is_cuda and p.dtype == torch.float32 and p.grad.dtype == torch.float32
               and not p.grad.is_sparse and p.is_contiguous() and p.grad.is_contiguous()]
@@ -115,30 +143,24 @@ def _dense_takeover(optimizer):
             continue
         beta1, beta2 = group["betas"]
         lr, eps = float(group["lr"]), float(group["eps"])
-        handles = optimizer.__dict__.setdefault("_nsig_dense_handles", {})      # id(p) -> (p, state dict, exp_avg, exp_avg_sq, step count as numpy, step tensor)
+        handles = optimizer.__dict__.setdefault("_nsig_dense_handles", {})      # id(p) -> _Handle, host counts only
         n = len(ps)
         vp, fl = ctypes.c_void_p * n, ctypes.c_float * n
         pp, pg, pm, pv, numel, ss, ib = vp(), vp(), vp(), vp(), (ctypes.c_uint32 * n)(), fl(), fl()
         skip = False
         for i, p in enumerate(ps):
             h = handles.get(id(p))
-            if (h is None or h[0] is not p or optimizer.state.get(p) is not h[1] or h[1].get("exp_avg") is not h[2] or h[1].get("exp_avg_sq") is not h[3]
-                    or h[1].get("step") is not h[5]):      # (live state, see fused_shared_step)
-                st = optimizer.state[p]
-                if len(st) == 0:   # torch.optim.Adam._init_group
-                    st["step"] = torch.tensor(0.0, dtype=torch.float32)
-                    st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
-                    st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
-                if st["step"].is_cuda or not (st["exp_avg"].is_contiguous() and st["exp_avg_sq"].is_contiguous()):
+            if h is None or not h.fresh(optimizer, p):
+                h = _Handle(optimizer, p)
+                if h.count is None or not (h.exp_avg.is_contiguous() and h.exp_avg_sq.is_contiguous()):
                     skip = True    # (a state format from elsewhere: the optimiser's own business)
                     break
-                h = handles[id(p)] = (p, st, st["exp_avg"], st["exp_avg_sq"], st["step"].numpy(), st["step"], p.data_ptr(), st["exp_avg"].data_ptr(),
-                                      st["exp_avg_sq"].data_ptr(), p.numel())
-            pp[i], pm[i], pv[i], numel[i], pg[i] = h[6], h[7], h[8], h[9], p.grad.data_ptr()
+                handles[id(p)] = h
+            pp[i], pm[i], pv[i], numel[i], pg[i] = h.p_ptr, h.m_ptr, h.v_ptr, h.numel, p.grad.data_ptr()
         if skip:
             continue
         for i, p in enumerate(ps):
-            count = handles[id(p)][4]
+            count = handles[id(p)].count
             count += 1
             k = float(count)
             ss[i] = lr / (1.0 - beta1 ** k)
@@ -162,7 +184,7 @@ def _dense_takeover_post_step(optimizer, args, kwargs):
 
 class CodebookAdam(torch.optim.Adam):
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, **kw):
-        if kw.get("weight_decay", 0) or kw.get("amsgrad", False) or kw.get("maximize", False):
+        if not _plain_group(kw):
             raise NotImplementedError("CodebookAdam implements plain Adam (the reference's configuration)")
         super().__init__(params, lr=lr, betas=betas, eps=eps, **kw)
 
@@ -181,15 +203,8 @@ class CodebookAdam(torch.optim.Adam):
 
 
 def _prepare_device_state(opt, tables):
-    """Allocate Adam state for every table up front (static addresses for graph replay); torch's capturable format."""
-    for t in tables:
-        st = opt.state[t]
-        if len(st) == 0:
-            st["step"] = torch.zeros((), dtype=torch.float32, device=t.device)
-            st["exp_avg"] = torch.zeros_like(t, memory_format=torch.preserve_format)
-            st["exp_avg_sq"] = torch.zeros_like(t, memory_format=torch.preserve_format)
-        elif not st["step"].is_cuda:
-            st["step"] = st["step"].to(t.device)
+    """Adam state of every table in torch's capturable format, allocated up front (static addresses for graph replay); returns the state dicts."""
+    return [_adam_state(opt, t, device_count=True) for t in tables]
 
 
 def _step_shared_sel(opt, tables, message_dev, G, lr_dev, grad_scale=1.0, next_message_dev=None, S_next=None):
@@ -201,12 +216,11 @@ def _step_shared_sel(opt, tables, message_dev, G, lr_dev, grad_scale=1.0, next_m
     cache = getattr(opt, "_sel_cache", None)
     if (cache is None or len(cache[0]) != len(tables) or any(a is not b for a, b in zip(cache[0], tables))
             or any(opt.state.get(t) is not st for t, st in zip(tables, cache[4]))):      # (load_state_dict replaces the state: new addresses)
-        _prepare_device_state(opt, tables)
+        states = _prepare_device_state(opt, tables)
         D = len(tables) // 2
-        arrays = (nv.ptr_array([t.data for t in tables]), nv.ptr_array([opt.state[t]["exp_avg"] for t in tables]),
-                  nv.ptr_array([opt.state[t]["exp_avg_sq"] for t in tables]), nv.ptr_array([opt.state[t]["step"] for t in tables]))
+        arrays = (nv.ptr_array([t.data for t in tables]), *(nv.ptr_array([st[key] for st in states]) for key in ("exp_avg", "exp_avg_sq", "step")))
         scratch = torch.empty(2 * D, dtype=torch.float32, device=tables[0].device)
-        cache = opt._sel_cache = (list(tables), arrays, scratch, D, [opt.state[t] for t in tables])
+        cache = opt._sel_cache = (list(tables), arrays, scratch, D, states)
     _, (pp, pm, pv, ps), scratch, D, _ = cache
     if next_message_dev is not None:
         if S_next is None or S_next.dtype != torch.float32 or not S_next.is_contiguous() or S_next.numel() != tables[0].numel():
@@ -222,6 +236,18 @@ def _step_shared_sel(opt, tables, message_dev, G, lr_dev, grad_scale=1.0, next_m
 CodebookAdam.step_shared_sel = torch.no_grad()(_step_shared_sel)
 
 
+def _adam_dense(optimizer, params, group, lr_dev, scratch, grad_scale=1.0):
+    """torch.optim.Adam's update of `params` from their `.grad` with `group`'s betas and eps, through opt_adam_dense: state in torch's capturable format (device step
+    counts), created on first use; scratch: 64 floats per 32 parameters."""
+    states = _prepare_device_state(optimizer, params)
+    n = len(params)
+    numel = (ctypes.c_uint32 * n)(*[p.numel() for p in params])
+    nv.call("opt_adam_dense", n, nv.ptr_array([p.data for p in params]), nv.ptr_array([p.grad for p in params]),
+            *(nv.ptr_array([st[key] for st in states]) for key in ("exp_avg", "exp_avg_sq", "step")), numel, nv.ptr(lr_dev), float(group["betas"][0]),
+            float(group["betas"][1]), float(group["eps"]), float(grad_scale), nv.ptr(scratch), nv.stream())
+    _bump_versions(params)
+
+
 def _step_dense(opt, lr_dev, grad_scale=1.0):
     """torch.optim.Adam's update of every parameter that carries a dense `.grad` (the decoder) through opt_adam_dense: one
     pass of 1024-element chunks instead of the generic multi-tensor kernel's 64K-element ones.  State in torch's capturable
@@ -233,13 +259,6 @@ def _step_dense(opt, lr_dev, grad_scale=1.0):
                 continue
             if not (p.is_cuda and p.dtype == torch.float32 and p.grad.dtype == torch.float32 and p.is_contiguous() and p.grad.is_contiguous()):
                 raise NotImplementedError("step_dense handles contiguous float32 CUDA parameters")
-            st = opt.state[p]
-            if len(st) == 0:
-                st["step"] = torch.zeros((), dtype=torch.float32, device=p.device)
-                st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
-                st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
-            elif not st["step"].is_cuda:
-                st["step"] = st["step"].to(p.device)
             todo.append((group, p))
     if not todo:
         return
@@ -251,12 +270,7 @@ def _step_dense(opt, lr_dev, grad_scale=1.0):
     scratch = getattr(opt, "_dense_scratch", None)
     if scratch is None or scratch.numel() < 64 * ((n + 31) // 32):
         scratch = opt._dense_scratch = torch.empty(64 * ((n + 31) // 32), dtype=torch.float32, device=ps[0].device)
-    numel = (ctypes.c_uint32 * n)(*[p.numel() for p in ps])
-    nv.call("opt_adam_dense", n, nv.ptr_array([p.data for p in ps]), nv.ptr_array([p.grad for p in ps]),
-            nv.ptr_array([opt.state[p]["exp_avg"] for p in ps]), nv.ptr_array([opt.state[p]["exp_avg_sq"] for p in ps]),
-            nv.ptr_array([opt.state[p]["step"] for p in ps]), numel, nv.ptr(lr_dev), float(group["betas"][0]), float(group["betas"][1]),
-            float(group["eps"]), float(grad_scale), nv.ptr(scratch), nv.stream())
-    _bump_versions(ps)
+    _adam_dense(opt, ps, group, lr_dev, scratch, grad_scale)
 
 
 CodebookAdam.step_dense = torch.no_grad()(_step_dense)

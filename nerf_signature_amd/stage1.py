@@ -31,7 +31,7 @@ from . import dp
 from . import fieldops as fo
 from . import tcnn_compat as tcnn
 from .capture import SegmentedCapture, warm_up
-from .optim import _bump_versions
+from .optim import _adam_dense, _bump_versions, _plain_group, _prepare_device_state
 from .hash_encoding import HashEmbedder
 from .raymarching import padded_point_count
 from .renderer import NeRFRenderer
@@ -365,8 +365,7 @@ class GraphedCleanLoop:
             raise ValueError("GraphedCleanLoop drives the occupancy-grid path (cuda_ray=True)")
         if model.density_scale != 1:
             raise NotImplementedError("GraphedCleanLoop: density_scale != 1")
-        if not isinstance(optimizer, torch.optim.Adam) or any(g.get("weight_decay", 0) or g.get("amsgrad", False) or g.get("maximize", False)
-                                                               for g in optimizer.param_groups):
+        if not isinstance(optimizer, torch.optim.Adam) or not all(_plain_group(g) for g in optimizer.param_groups):
             raise TypeError("GraphedCleanLoop steps a plain torch.optim.Adam (the reference's, main_nerf.py:122) through opt_adam_dense")
         self.model, self.optimizer = model, optimizer
         self.render_kwargs = dict(render_kwargs)
@@ -444,7 +443,7 @@ class GraphedCleanLoop:
         # False: NeRFRenderer.update_extra_state, the reference's form (three host synchronisations per refresh)
         self.device_refresh = bool(device_refresh)
         self._refresh = None
-        # the trainer's moving average of the parameters (main_nerf.py:130 ema_decay=0.95; torch_ema semantics, csrc/stage1.hip opt_ema_update): one launch at the
+        # the trainer's moving average of the parameters (main_nerf.py:130 ema_decay=0.95; torch_ema semantics, csrc/optim.hip opt_ema_update): one launch at the
         # step's tail, inside the graph; read it through ema_parameters() / the ema_weights() context (utils.py:801-811 evaluates and checkpoints with it)
         self.ema_decay = None if ema_decay is None else float(ema_decay)
         self.ema_shadow = None if ema_decay is None else [p.detach().clone() for p in self.params]
@@ -506,10 +505,9 @@ class GraphedCleanLoop:
         if self.fused_table_adam:
             opt, tabs = self.optimizer, self.params[:16]
             group = opt.param_groups[0]
-            self._ensure_state(tabs)
+            states = _prepare_device_state(opt, tabs)
             nv.call("hg_levels_scatter_adam", nv.ptr(xyzs), M, nv.ptr(rows), float(m.bound), nv.ptr(tr.d_planes), tr.stride, nv.ptr(self.plan),
-                    nv.ptr_array([p.data for p in tabs]), nv.ptr_array([opt.state[p]["exp_avg"] for p in tabs]),
-                    nv.ptr_array([opt.state[p]["exp_avg_sq"] for p in tabs]), nv.ptr_array([opt.state[p]["step"] for p in tabs]), nv.ptr(self.lr_dev),
+                    nv.ptr_array([p.data for p in tabs]), *(nv.ptr_array([st[key] for st in states]) for key in ("exp_avg", "exp_avg_sq", "step")), nv.ptr(self.lr_dev),
                     float(group["betas"][0]), float(group["betas"][1]), float(group["eps"]), 1.0, nv.ptr(self._adam_scratch[0]), s)
             _bump_versions(tabs)
         else:
@@ -562,30 +560,10 @@ class GraphedCleanLoop:
         if self.sparse_exchange:
             coarse.index_copy_(0, self._live_index, self.g_packed)
 
-    def _ensure_state(self, params):
-        """torch.optim.Adam's state of `params` in its capturable format (device step counts), created on first use."""
-        opt = self.optimizer
-        for p in params:
-            st = opt.state[p]
-            if len(st) == 0:
-                st["step"] = torch.zeros((), dtype=torch.float32, device=p.device)
-                st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
-                st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
-            elif not st["step"].is_cuda:
-                st["step"] = st["step"].to(p.device)
-
     def _adam(self, params):
-        """torch.optim.Adam's update of `params` from their `.grad` views through opt_adam_dense (state in torch's capturable format: device step counts)."""
-        opt = self.optimizer
-        group = opt.param_groups[0]
-        self._ensure_state(params)
-        n = len(params)
-        numel = (ctypes.c_uint32 * n)(*[p.numel() for p in params])
-        nv.call("opt_adam_dense", n, nv.ptr_array([p.data for p in params]), nv.ptr_array([p.grad for p in params]),
-                nv.ptr_array([opt.state[p]["exp_avg"] for p in params]), nv.ptr_array([opt.state[p]["exp_avg_sq"] for p in params]),
-                nv.ptr_array([opt.state[p]["step"] for p in params]), numel, nv.ptr(self.lr_dev), float(group["betas"][0]), float(group["betas"][1]),
-                float(group["eps"]), 1.0, nv.ptr(self._adam_scratch[0 if params[0] is self.params[0] else 1]), nv.stream())
-        _bump_versions(params)
+        """torch.optim.Adam's update of `params` from their `.grad` views (optim._adam_dense; one (betas, eps) for all groups); the tables' pass and the MLPs' may be in
+        flight together, each with a scratch of its own."""
+        _adam_dense(self.optimizer, params, self.optimizer.param_groups[0], self.lr_dev, self._adam_scratch[0 if params[0] is self.params[0] else 1])
 
     def _optimise(self):
         if self.fused_backward:                     # every gradient is there when the scatter is: one call (one prepare launch) over the 18 tensors

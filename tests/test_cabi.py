@@ -69,6 +69,87 @@ def test_argument_validation_needs_no_gpu(native):
     assert native.fn("field_bwd_wgrad_scratch_bytes")(1) == 12 * 1024 * 4 and native.fn("field_bwd_wgrad_scratch_bytes")(10 ** 6) == 256 * 12 * 1024 * 4
 
 
+def test_optimiser_and_codebook_refusals_word_for_word(native):
+    """Every refusal of the opt_* entry points and of hg_codebook_presum / hg_codebook_presum_sel / hg_fanout_grad that comes before any launch, by its whole message:
+    null list, D / n out of range, a null or a misaligned element, misaligned G / S / S_next, opt_ema_update's tensor count and decay range."""
+    vp, fl, u32 = native._vp, native._fl, native._u32
+    d, off = vp(256), vp(264)                                # an aligned and a misaligned address (nothing is dereferenced on the device side of a refusal)
+    arr = lambda *a: (vp * len(a))(*a)
+    ok2, ok4 = arr(256, 512), arr(256, 512, 768, 1024)
+    hp = (0.9, 0.99, 1e-15)
+
+    def refused(name, message, *args):
+        with pytest.raises(ValueError) as e:
+            native.call(name, *args)
+        assert str(e.value) == f"{name} failed (code 1): {name}: {message}"
+
+    # opt_codebook_adam(G, params, exp_avg, exp_avg_sq, D, beta1, beta2, eps, step_sizes, inv_bc2, grad_scale, stream)
+    ss = (fl * 4)(1, 1, 1, 1)
+    adam = lambda G=d, p=ok2, m=ok2, v=ok2, D=2, s=ss: ("opt_codebook_adam", G, p, m, v, D, *hp, s, ss, 1.0, None)
+    for a, msg in ((adam(p=None), "null pointer"), (adam(G=None), "null pointer"), (adam(s=None), "null pointer"), (adam(D=0), "D=0 out of range"), (adam(D=65), "D=65 out of range"),
+                   (adam(G=off), "G must be 16-byte aligned"), (adam(m=arr(256, None)), "table 1 has a null pointer"), (adam(v=arr(264, 256)), "table 0 is not 16-byte aligned")):
+        refused(a[0], msg, *a[1:])
+
+    # opt_codebook_adam_sel(G, params, exp_avg, exp_avg_sq, steps, message, D, lr, beta1, beta2, eps, grad_scale, scratch, stream) and its _next form (+ next_message, S_next)
+    for name, tail in (("opt_codebook_adam_sel", ()), ("opt_codebook_adam_sel_next", (d, d))):
+        sel = lambda G=d, p=ok4, m=ok4, v=ok4, st=ok4, msg=d, D=2, lr=d, sc=d: (G, p, m, v, st, msg, D, lr, *hp, 1.0, sc, *tail, None)
+        refused(name, "null pointer", *sel(st=None))
+        refused(name, "null pointer", *sel(msg=None))
+        refused(name, "null pointer", *sel(sc=None))
+        refused(name, "D=0 out of range", *sel(D=0))
+        refused(name, "D=65 out of range", *sel(D=65))
+        refused(name, "G must be 16-byte aligned", *sel(G=off))
+        refused(name, "table 2 has a null pointer", *sel(st=arr(256, 512, None, 1024)))
+        refused(name, "table 3 has a null pointer", *sel(p=arr(256, 512, 768, None)))
+        refused(name, "table 1 is not 16-byte aligned", *sel(m=arr(256, 520, 768, 1024)))
+    nxt = lambda nm, S: (d, ok4, ok4, ok4, ok4, d, 2, d, *hp, 1.0, d, nm, S, None)
+    for nm, S in ((None, d), (d, None), (d, off)):
+        refused("opt_codebook_adam_sel_next", "next_message / S_next null or S_next not 16-byte aligned", *nxt(nm, S))
+
+    # the dense entry points launch group by group: a null element at index 0 is refused before the first launch
+    one, none1, n1, n0 = arr(256), arr(None), (u32 * 1)(8), (u32 * 1)(0)
+    host = lambda p=one, g=one, m=one, v=one, numel=n1, s=ss: ("opt_adam_dense_host", 1, p, g, m, v, numel, s, ss, *hp, 1.0, None)
+    dense = lambda p=one, g=one, m=one, v=one, st=one, numel=n1, lr=d, sc=d: ("opt_adam_dense", 1, p, g, m, v, st, numel, lr, *hp, 1.0, sc, None)
+    for a, msg in ((host(p=None), "null pointer"), (host(numel=None), "null pointer"), (host(s=None), "null pointer"), (host(g=none1), "tensor 0 has a null pointer or no elements"),
+                   (host(v=none1), "tensor 0 has a null pointer or no elements"), (host(numel=n0), "tensor 0 has a null pointer or no elements"),
+                   (dense(m=None), "null pointer"), (dense(st=None), "null pointer"), (dense(lr=None), "null pointer"), (dense(sc=None), "null pointer"),
+                   (dense(p=none1), "tensor 0 has a null pointer or no elements"), (dense(st=none1), "tensor 0 has a null pointer or no elements"),
+                   (dense(numel=n0), "tensor 0 has a null pointer or no elements")):
+        refused(a[0], msg, *a[1:])
+
+    # opt_ema_update(n, params, shadow, numel, num_updates, decay, stream): one launch behind every check
+    n2 = (u32 * 2)(8, 8)
+    ema = lambda n=2, p=ok2, s=ok2, numel=n2, nu=d, decay=0.95: ("opt_ema_update", n, p, s, numel, nu, decay, None)
+    for a, msg in ((ema(p=None), "null pointer"), (ema(nu=None), "null pointer"), (ema(n=0), "1 .. 32 tensors, decay in [0, 1]"), (ema(n=33), "1 .. 32 tensors, decay in [0, 1]"),
+                   (ema(decay=-0.01), "1 .. 32 tensors, decay in [0, 1]"), (ema(decay=1.01), "1 .. 32 tensors, decay in [0, 1]"),
+                   (ema(s=arr(256, None)), "tensor 1 has a null pointer or no elements"), (ema(p=arr(None, 256)), "tensor 0 has a null pointer or no elements"),
+                   (ema(numel=(u32 * 2)(8, 0)), "tensor 1 has a null pointer or no elements")):
+        refused(a[0], msg, *a[1:])
+
+    # hg_codebook_presum(tables, D, S, stream), hg_codebook_presum_sel(all_tables, message, D, S, stream), hg_fanout_grad(G, grads, D, accumulate, stream)
+    refused("hg_codebook_presum", "null pointer", None, 2, d, None)
+    refused("hg_codebook_presum", "null pointer", ok2, 2, None, None)
+    refused("hg_codebook_presum", "D=0 out of range [1,64]", ok2, 0, d, None)
+    refused("hg_codebook_presum", "D=65 out of range [1,64]", ok2, 65, d, None)
+    refused("hg_codebook_presum", "table 1 is null or not 16-byte aligned", arr(256, None), 2, d, None)
+    refused("hg_codebook_presum", "table 0 is null or not 16-byte aligned", arr(264, 256), 2, d, None)
+    refused("hg_codebook_presum", "S must be 16-byte aligned", ok2, 2, off, None)
+    refused("hg_codebook_presum_sel", "null pointer", None, d, 2, d, None)
+    refused("hg_codebook_presum_sel", "null pointer", ok4, None, 2, d, None)
+    refused("hg_codebook_presum_sel", "D=0 out of range [1,64]", ok4, d, 0, d, None)
+    refused("hg_codebook_presum_sel", "D=65 out of range [1,64]", ok4, d, 65, d, None)
+    refused("hg_codebook_presum_sel", "table 3 is null or not 16-byte aligned", arr(256, 512, 768, None), d, 2, d, None)
+    refused("hg_codebook_presum_sel", "table 2 is null or not 16-byte aligned", arr(256, 512, 776, 1024), d, 2, d, None)
+    refused("hg_codebook_presum_sel", "S must be 16-byte aligned", ok4, d, 2, off, None)
+    refused("hg_fanout_grad", "null pointer", None, ok2, 2, 0, None)
+    refused("hg_fanout_grad", "null pointer", d, None, 2, 0, None)
+    refused("hg_fanout_grad", "D=0 out of range", d, ok2, 0, 0, None)
+    refused("hg_fanout_grad", "D=65 out of range", d, ok2, 65, 1, None)
+    refused("hg_fanout_grad", "gradient 1 is null or not 16-byte aligned", d, arr(256, None), 2, 0, None)
+    refused("hg_fanout_grad", "gradient 0 is null or not 16-byte aligned", d, arr(264, 256), 2, 1, None)
+    refused("hg_fanout_grad", "G must be 16-byte aligned", off, ok2, 2, 0, None)
+
+
 def test_missing_library_fails_loudly(native, monkeypatch):
     monkeypatch.setattr(native, "_lib", None)
     monkeypatch.setattr(native, "_bound", {})

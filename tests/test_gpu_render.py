@@ -899,6 +899,44 @@ def test_dense_adam_with_a_large_tensor_in_the_group_matches_torch_adam():
         np.testing.assert_allclose(oa.state[p]["exp_avg_sq"].cpu().numpy(), ob.state[q]["exp_avg_sq"].cpu().numpy(), rtol=2e-6, atol=0, err_msg=str(i))
 
 
+def test_dense_adam_routes_agree_bit_for_bit():
+    """opt_adam_dense's routes run one element arithmetic: the wide launch (float4 per lane; here a 65 540-element tensor whose last 4096-element chunk holds exactly one
+    float4 -- the clamped duplicate load -- and a 1028-element tensor riding along with a partial chunk) and the element-wise launch (1030 elements: no multiple of 4,
+    a partial 1024-chunk) against the SAME values sent down the element-wise launch alone -- parameters and gradients as contiguous views one float into a larger
+    buffer, 4 bytes off the 16-byte alignment the wide launch needs.  Three steps, grad_scale 0.5, gradients from 1e-4 to 1e4 by index with every third element exactly
+    zero, one tensor without a gradient at step 1: parameters, both moments and the step counts are equal bit for bit."""
+    from nerf_signature_amd.optim import CodebookAdam
+    torch.manual_seed(3)
+    sizes = [65540, 1028, 1030]
+
+    def off_by_one_float(t):
+        buf = torch.empty(t.numel() + 1, device="cuda")
+        buf[1:].copy_(t)
+        return buf[1:]
+
+    a = [torch.nn.Parameter(torch.randn(n, device="cuda")) for n in sizes]
+    b = [torch.nn.Parameter(off_by_one_float(p.detach())) for p in a]
+    assert all(p.data_ptr() % 16 == 0 and q.data_ptr() % 16 == 4 and q.is_contiguous() for p, q in zip(a, b))
+    oa = CodebookAdam(a, lr=1e-2, betas=(0.9, 0.99), eps=1e-15, capturable=True)
+    ob = CodebookAdam(b, lr=1e-2, betas=(0.9, 0.99), eps=1e-15, capturable=True)
+    lr_dev = torch.tensor(1e-2, device="cuda")
+    for step in range(3):
+        for i, (p, q) in enumerate(zip(a, b)):
+            g = torch.randn_like(p) * 10.0 ** torch.linspace(-4.0, 4.0, p.numel(), device="cuda")
+            g[::3] = 0.0
+            skip = step == 1 and i == 1
+            p.grad, q.grad = (None, None) if skip else (g, off_by_one_float(g))
+            assert skip or (p.grad.data_ptr() % 16 == 0 and q.grad.data_ptr() % 16 == 4 and torch.equal(p.grad, q.grad))
+        oa.step_dense(lr_dev, grad_scale=0.5)
+        ob.step_dense(lr_dev, grad_scale=0.5)
+    for i, (p, q) in enumerate(zip(a, b)):
+        assert torch.equal(p, q), i
+        for key in ("exp_avg", "exp_avg_sq", "step"):
+            assert torch.equal(oa.state[p][key], ob.state[q][key]), (i, key)
+        assert float(oa.state[p]["step"]) == (2.0 if i == 1 else 3.0)
+        assert bool(torch.isfinite(p).all()) and not torch.equal(p, torch.zeros_like(p))
+
+
 def test_fused_decoder_gradients_are_views_of_one_flat_buffer():
     """What dp.GradExchange relies on for its single in-place all-reduce: after backward() every decoder parameter's .grad is a
     view of one contiguous buffer that they tile exactly (conv biases, whose gradient is identically zero, have none)."""

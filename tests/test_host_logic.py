@@ -932,3 +932,58 @@ def test_gpu_suite_runs_sharpest_first():
     keys = [rank(*t) for t in order]
     assert keys == sorted(keys), keys
     assert rank("test_gpu_amp_ckpt.py", "test_dense_takeover_is_torch_adam_arithmetic")[0] < rank("test_gpu_convergence.py", "test_anything")[0] == 3
+
+
+def test_adam_state_of_the_native_passes_is_torch_adams_own(monkeypatch):
+    """The state the native Adam passes create on first use is torch.optim.Adam's own, in both of its formats, on a CPU parameter (the launch itself stubbed out):
+    the host-count form (optim.fused_shared_step, the hooks) against what Adam creates on its first step(); the device-count form (optim._prepare_device_state, the
+    captured loops) against Adam(capturable=True)'s; the move of an existing host count to the device form; and either one's state_dict() in a plain Adam."""
+    import types
+    from nerf_signature_amd import optim
+    launched = []
+    monkeypatch.setattr(optim, "nv", types.SimpleNamespace(ptr=lambda t: None if t is None else t.data_ptr(), stream=lambda: None,
+                                                           ptr_array=lambda ts: [t.data_ptr() for t in ts], call=lambda name, *a: launched.append(name)))
+    torch.manual_seed(0)
+    kw = dict(lr=1e-2, betas=(0.9, 0.99), eps=1e-15)
+    layout = lambda st: {k: (v.dtype, tuple(v.shape), v.device) for k, v in st.items()}
+
+    # host counts: torch.optim.Adam after its first step()
+    p, q = torch.nn.Parameter(torch.randn(7, 2)), torch.nn.Parameter(torch.randn(7, 2))
+    q.grad = torch.ones_like(q)
+    ref = torch.optim.Adam([q], **kw)
+    ref.step()
+    opt = torch.optim.Adam([p], **kw)
+    optim.fused_shared_step(opt, opt.param_groups[0], [p], torch.zeros(7, 2))
+    assert launched == ["opt_codebook_adam"]
+    host = opt.state[p]
+    assert list(host) == list(ref.state[q]) == ["step", "exp_avg", "exp_avg_sq"] and layout(host) == layout(ref.state[q])
+    assert float(host["step"]) == float(ref.state[q]["step"]) == 1.0 and not host["exp_avg"].any() and not host["exp_avg_sq"].any()
+
+    # device counts: what Adam(capturable=True) creates (its _init_group; its step() itself refuses a CPU parameter)
+    cap = torch.optim.Adam([q], capturable=True, **kw)
+    cap._init_group(cap.param_groups[0], [], [], [], [], [], [])
+    p2 = torch.nn.Parameter(torch.randn(3, 5))
+    opt2 = torch.optim.Adam([p2], **kw)
+    optim._prepare_device_state(opt2, [p2])
+    dev = opt2.state[p2]
+    assert list(dev) == list(cap.state[q]) and {k: v[:1] + v[2:] for k, v in layout(dev).items()} == {k: v[:1] + v[2:] for k, v in layout(cap.state[q]).items()}
+    assert dev["step"].dim() == 0 and dev["step"].dtype == torch.float32 and dev["step"].device == p2.device and float(dev["step"]) == 0.0
+    assert dev["exp_avg"].shape == dev["exp_avg_sq"].shape == p2.shape and not dev["exp_avg"].any() and not dev["exp_avg_sq"].any()
+
+    # an existing host-count state taken to the device form: only `step` is touched, its value kept
+    m, v = host["exp_avg"], host["exp_avg_sq"]
+    optim._prepare_device_state(opt, [p])
+    moved = opt.state[p]
+    assert moved is host and moved["exp_avg"] is m and moved["exp_avg_sq"] is v and list(moved) == ["step", "exp_avg", "exp_avg_sq"]
+    assert moved["step"].dim() == 0 and moved["step"].dtype == torch.float32 and moved["step"].device == p.device and float(moved["step"]) == 1.0
+
+    # either format's state_dict() is a plain torch.optim.Adam's
+    for o, t in ((opt, p), (opt2, p2)):
+        fresh_p = torch.nn.Parameter(t.detach().clone())
+        fresh = torch.optim.Adam([fresh_p], **kw)
+        fresh.load_state_dict(o.state_dict())
+        count = float(o.state[t]["step"])      # (a host count travels through state_dict() as the tensor itself)
+        assert layout(fresh.state[fresh_p]) == layout(o.state[t]) and float(fresh.state[fresh_p]["step"]) == float(o.state[t]["step"])
+        fresh_p.grad = torch.ones_like(fresh_p)
+        fresh.step()
+        assert float(fresh.state[fresh_p]["step"]) == count + 1.0 and fresh.state[fresh_p]["exp_avg"].any()
