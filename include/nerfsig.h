@@ -743,6 +743,30 @@ int mc_count(const float *u, uint32_t nx, uint32_t ny, uint32_t nz, float thresh
 int mc_emit(const float *u, uint32_t nx, uint32_t ny, uint32_t nz, float threshold, void *scratch, uint32_t n_vertices, uint32_t n_triangles,
             float *vertices, int32_t *triangles, nsig_stream_t stream);
 
+/*
+ * Vertex normals of the mesh mc_emit wrote: called after it with the same lattice, threshold and scratch (whose node codes and vertex bases say
+ * which node and axis own each vertex), it writes normals [V, 3] in mc_emit's vertex order.  Every operation is fp32 and rounded on its own.
+ * Node gradient per axis of extent n: (u[i+1] - u[i-1]) * 0.5f inside, u[1] - u[0] at i = 0, u[n-1] - u[n-2] at i = n-1.  The vertex lies on the
+ * edge from node A to node B = A + 1 along the edge's axis at mc_emit's own t (the same expression, clamp and NaN -> 0.5 included); per component
+ * g = gA + t * (gB - gA), times scale_x / scale_y / scale_z (lattice steps per world unit along each axis; 1, 1, 1 for lattice space);
+ * len = sqrtf((gx*gx + gy*gy) + gz*gz); normal = -g / len (density grows inwards, so it points out), or (0, 0, 0) when len is zero or not
+ * finite.  gradients: NULL or [V, 3], the scaled g before the division.  V = 0 launches nothing.  One launch; mc_emit's outputs are not touched.
+ */
+int mc_vertex_normals(const float *u, uint32_t nx, uint32_t ny, uint32_t nz, float threshold, const void *scratch, uint32_t n_vertices,
+                      float scale_x, float scale_y, float scale_z, float *normals, float *gradients, nsig_stream_t stream);
+
+/*
+ * Connected components of any triangle list: triangles [T, 3] int32 ids in [0, V), the graph of the V vertices with the three sides of every
+ * triangle as edges.  labels [V] int32: the smallest vertex id of the vertex's component (a vertex in no triangle labels itself).  The answer
+ * is unique: the same bits on every run.  V, T < 2^31.  Three launches (init, hook: one thread per triangle, flatten), no host read, no
+ * barrier between workgroups and no thread that waits for another; every loop ends on its own (csrc/mesh.hip).  scratch:
+ * mesh_components_scratch_bytes(V, T) bytes, 16-byte aligned, need not be initialised (0 = out of range).  Its first 32-bit word is the
+ * status the caller reads after the stream has finished: 0xffffffff, or the index of the first triangle with an id outside [0, V) -- such
+ * triangles are skipped, never dereferenced, and the labels are then those of the remaining triangles.
+ */
+size_t mesh_components_scratch_bytes(uint32_t V, uint32_t T);
+int mesh_components(const int32_t *triangles, uint32_t T, uint32_t V, int32_t *labels, void *scratch, nsig_stream_t stream);
+
 /* ------------------------------------------------------------------ image metrics */
 
 /*

@@ -135,12 +135,15 @@ SIGNATURES = {
     "mc_scratch_bytes": [_u32, _u32, _u32],
     "mc_count": [_vp, _u32, _u32, _u32, _fl, _vp, _vp, _vp],
     "mc_emit": [_vp, _u32, _u32, _u32, _fl, _vp, _u32, _u32, _vp, _vp, _vp],
+    "mc_vertex_normals": [_vp, _u32, _u32, _u32, _fl, _vp, _u32, _fl, _fl, _fl, _vp, _vp, _vp],
+    "mesh_components_scratch_bytes": [_u32, _u32],
+    "mesh_components": [_vp, _u32, _u32, _vp, _vp, _vp],
     "im_range_scratch_bytes": [_u32, _c.c_uint64],
     "im_range_sse": [_vp, _vp, _u32, _c.c_uint64, _vp, _vp, _vp, _vp],
     "im_ssim_scratch_bytes": [_u32, _u32, _u32, _u32],
     "im_ssim": [_vp, _vp, _u32, _u32, _u32, _u32, _vp, _fl, _vp, _vp, _vp, _vp],
 }
-_RESTYPES = {"nsig_last_error": _c.c_char_p, "nsig_host_device_pointer": _c.c_void_p, "rm_march_train_scratch_bytes": _sz, "mlp_packed_bytes": _sz, "hg_planes_bytes": _sz, "dec_workspace_bytes": _sz, "hg_scatter_levels_scratch_bytes": _sz, "hg_scatter_binned_scratch_bytes": _sz, "hg_scatter_plan_bytes": _sz, "field_wgrad_scratch_bytes": _sz, "field_bwd_wgrad_scratch_bytes": _sz, "hg_levels_plan_bytes": _sz, "rg_refresh_partials_bytes": _sz, "rg_refresh_draw_scratch_bytes": _sz, "mc_scratch_bytes": _sz, "im_range_scratch_bytes": _sz, "im_ssim_scratch_bytes": _sz}
+_RESTYPES = {"nsig_last_error": _c.c_char_p, "nsig_host_device_pointer": _c.c_void_p, "rm_march_train_scratch_bytes": _sz, "mlp_packed_bytes": _sz, "hg_planes_bytes": _sz, "dec_workspace_bytes": _sz, "hg_scatter_levels_scratch_bytes": _sz, "hg_scatter_binned_scratch_bytes": _sz, "hg_scatter_plan_bytes": _sz, "field_wgrad_scratch_bytes": _sz, "field_bwd_wgrad_scratch_bytes": _sz, "hg_levels_plan_bytes": _sz, "rg_refresh_partials_bytes": _sz, "rg_refresh_draw_scratch_bytes": _sz, "mc_scratch_bytes": _sz, "mesh_components_scratch_bytes": _sz, "im_range_scratch_bytes": _sz, "im_ssim_scratch_bytes": _sz}
 
 _lib = None
 

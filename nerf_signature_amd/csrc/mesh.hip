@@ -216,6 +216,139 @@ __global__ void __launch_bounds__(kMcThreads) k_mc_tris(McDims d, const uint16_t
     }
 }
 
+// ---- vertex normals -------------------------------------------------------------------------------------------------------------------------------------
+// Finite-difference gradient of u at a node along one axis of extent ext (>= 2): central inside, one-sided at the two ends.
+__device__ inline float mc_diff(const float *__restrict__ u, uint32_t n, uint32_t i, uint32_t ext, uint32_t stride) {
+    if (i == 0) return u[n + stride] - u[n];
+    if (i == ext - 1) return u[n] - u[n - stride];
+    return (u[n + stride] - u[n - stride]) * 0.5f;
+}
+
+__device__ inline void mc_node_grad(const float *__restrict__ u, const McDims &d, uint32_t n, uint32_t i, uint32_t j, uint32_t k, float g[3]) {
+    g[0] = mc_diff(u, n, i, d.nx, d.sx);
+    g[1] = mc_diff(u, n, j, d.ny, d.sy);
+    g[2] = mc_diff(u, n, k, d.nz, 1u);
+}
+
+// One thread per node, after mc_emit: for every crossing edge the node owns, the normal of the vertex k_mc_verts wrote for it, to the same index
+// (vbase[n] + the node's crossing edges of lower axis).  The gradient is interpolated between the edge's two nodes at k_mc_verts' own t, scaled per
+// axis, and the normal is its negated unit vector (density grows inwards); a zero or non-finite length gives (0, 0, 0).  grads (optional) receives
+// the scaled gradient before the division.
+__global__ void __launch_bounds__(kMcThreads) k_mc_normals(const float *__restrict__ u, McDims d, float thr, const uint16_t *__restrict__ code,
+                                                           const uint32_t *__restrict__ vbase, uint32_t n_vertices, float sx, float sy, float sz,
+                                                           float *__restrict__ normals, float *__restrict__ grads) {
+    const uint32_t n = blockIdx.x * kMcThreads + threadIdx.x;
+    if (n >= d.N) return;
+    const uint32_t bits = (uint32_t)(code[n] >> 8);
+    if (!bits) return;
+    const uint32_t k = n % d.nz, jk = n / d.nz, j = jk % d.ny, i = jk / d.ny;
+    const float a = u[n];
+    float ga[3];
+    mc_node_grad(u, d, n, i, j, k, ga);
+    const uint32_t step[3] = {d.sx, d.sy, 1u};
+    const float scale[3] = {sx, sy, sz};
+    uint32_t off = vbase[n];
+#pragma unroll
+    for (uint32_t ax = 0; ax < 3; ++ax) {
+        if (!((bits >> ax) & 1u)) continue;
+        if (!(ax == 0 ? i + 1 < d.nx : ax == 1 ? j + 1 < d.ny : k + 1 < d.nz)) continue;      // (never, with mc_count's codes: a crossing edge has its far node)
+        const uint32_t m = n + step[ax];
+        const float b = u[m];
+        float t = (thr - a) / (b - a);
+        t = isnan(t) ? 0.5f : fminf(fmaxf(t, 0.0f), 1.0f);
+        float gb[3];
+        mc_node_grad(u, d, m, i + (ax == 0), j + (ax == 1), k + (ax == 2), gb);
+        float g[3];
+#pragma unroll
+        for (uint32_t c = 0; c < 3; ++c) g[c] = (ga[c] + t * (gb[c] - ga[c])) * scale[c];
+        const float len = sqrtf((g[0] * g[0] + g[1] * g[1]) + g[2] * g[2]);
+        const bool ok = len > 0.0f && len < INFINITY;      // false for NaN too
+        if (off < n_vertices) {                             // (always, with the scratch mc_emit left for these very arguments)
+            float *o = normals + 3 * (size_t)off;
+#pragma unroll
+            for (uint32_t c = 0; c < 3; ++c) o[c] = ok ? -g[c] / len : 0.0f;
+            if (grads) {
+                float *q = grads + 3 * (size_t)off;
+#pragma unroll
+                for (uint32_t c = 0; c < 3; ++c) q[c] = g[c];
+            }
+        }
+        ++off;
+    }
+}
+
+// ---- connected components of a triangle mesh ----------------------------------------------------------------------------------------------------------
+// A union-find forest in labels[] itself: labels[v] is v's parent.  Invariant, from the first store to the last: labels[v] <= v, and a
+// vertex whose parent is not itself never becomes a root again.  Hence every pointer walk strictly descends and ends within v steps whatever other
+// threads do, no cycle can form, and a tree's root is its smallest id.  Roots are hooked by compare-and-swap (larger root under the smaller); path
+// halving only ever lowers a parent to one of its own ancestors.  No thread waits for another: a failed compare-and-swap means another thread hooked
+// that root, and the retry goes on from a strictly smaller pair of ids.  Every shared word is read and written with agent-scope atomics.
+constexpr uint32_t kCcThreads = 256;
+constexpr uint32_t kCcNoError = 0xffffffffu;
+constexpr size_t kCcScratchBytes = 256;      // word 0: kCcNoError, or the index of the first triangle with an id outside [0, V)
+
+__device__ inline int32_t cc_load(const int32_t *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+
+// Root of x's tree, halving the path on the way (each parent lowered to the grandparent read just before: an ancestor, smaller than the parent).
+__device__ inline int32_t cc_find(int32_t *parent, int32_t x) {
+    int32_t px = cc_load(parent + x);
+    while (px != x) {                      // px < x
+        const int32_t g = cc_load(parent + px);
+        if (g != px) atomicMin(parent + x, g);
+        x = px;
+        px = g;
+    }
+    return x;
+}
+
+// The same walk without a store (the flatten pass: every root is final).
+__device__ inline int32_t cc_root(const int32_t *parent, int32_t x) {
+    int32_t px = cc_load(parent + x);
+    while (px != x) {
+        x = px;
+        px = cc_load(parent + x);
+    }
+    return x;
+}
+
+// Join the trees of a and b.  a + b falls with every failed compare-and-swap, so the loop ends on its own.
+__device__ inline void cc_hook(int32_t *parent, int32_t a, int32_t b) {
+    a = cc_find(parent, a);
+    b = cc_find(parent, b);
+    while (a != b) {
+        const int32_t hi = max(a, b), lo = min(a, b);
+        const int32_t old = atomicCAS(parent + hi, hi, lo);
+        if (old == hi) break;              // hi was a root and now hangs under lo < hi
+        a = cc_find(parent, old);          // another thread hooked hi under old < hi: go on from there
+        b = lo;
+    }
+}
+
+__global__ void __launch_bounds__(kCcThreads) k_cc_init(int32_t *__restrict__ labels, uint32_t V, uint32_t *__restrict__ err) {
+    const uint32_t v = blockIdx.x * kCcThreads + threadIdx.x;
+    if (v == 0) *err = kCcNoError;
+    if (v < V) labels[v] = (int32_t)v;
+}
+
+__global__ void __launch_bounds__(kCcThreads) k_cc_hook(const int32_t *__restrict__ tris, uint32_t T, uint32_t V, int32_t *labels, uint32_t *err) {
+    const uint32_t t = blockIdx.x * kCcThreads + threadIdx.x;
+    if (t >= T) return;
+    const int32_t a = tris[3 * (size_t)t], b = tris[3 * (size_t)t + 1], c = tris[3 * (size_t)t + 2];
+    if ((uint32_t)a >= V || (uint32_t)b >= V || (uint32_t)c >= V) {      // (negative ids wrap above 2^31 > V)
+        atomicMin(err, t);
+        return;
+    }
+    cc_hook(labels, a, b);                 // two sides connect the three corners; the third adds nothing
+    cc_hook(labels, b, c);
+}
+
+__global__ void __launch_bounds__(kCcThreads) k_cc_flatten(int32_t *labels, uint32_t V) {
+    const uint32_t v = blockIdx.x * kCcThreads + threadIdx.x;
+    if (v >= V) return;
+    const int32_t r = cc_root(labels, (int32_t)v);
+    __hip_atomic_store(labels + v, r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);      // r <= every value labels[v] has held: walks through v stay valid
+}
+
 static int check_dims(const char *what, uint32_t nx, uint32_t ny, uint32_t nz) {
     NSIG_REQUIRE(nx >= 2 && ny >= 2 && nz >= 2, "%s: every lattice dimension must be at least 2 (got %u x %u x %u)", what, nx, ny, nz);
     NSIG_REQUIRE((uint64_t)nx * ny * nz <= kMcMaxNodes, "%s: lattice of %u x %u x %u nodes is out of range (at most 2^28 nodes)", what, nx, ny, nz);
@@ -257,4 +390,35 @@ NSIG_EXPORT int mc_emit(const float *u, uint32_t nx, uint32_t ny, uint32_t nz, f
     k_mc_verts<<<s.nb, kMcThreads, 0, as_stream(stream)>>>(u, d, threshold, s.code, s.sums, s.vbase, vertices);
     k_mc_tris<<<s.nb, kMcThreads, 0, as_stream(stream)>>>(d, s.code, s.sums + s.nb, s.vbase, triangles);
     return check_launch("mc_emit");
+}
+
+NSIG_EXPORT int mc_vertex_normals(const float *u, uint32_t nx, uint32_t ny, uint32_t nz, float threshold, const void *scratch, uint32_t n_vertices,
+                                  float scale_x, float scale_y, float scale_z, float *normals, float *gradients, nsig_stream_t stream) {
+    NSIG_REQUIRE(u && scratch, "mc_vertex_normals: null pointer");
+    if (int e = check_dims("mc_vertex_normals", nx, ny, nz)) return e;
+    NSIG_REQUIRE(reinterpret_cast<uintptr_t>(scratch) % 16 == 0, "mc_vertex_normals: scratch must be 16-byte aligned");
+    NSIG_REQUIRE((uint64_t)n_vertices <= 3ull * nx * ny * nz, "mc_vertex_normals: %u vertices is out of range for %u x %u x %u nodes", n_vertices, nx, ny, nz);
+    if (n_vertices == 0) return NSIG_OK;
+    NSIG_REQUIRE(normals, "mc_vertex_normals: null pointer");
+    const McDims d = make_dims(nx, ny, nz);
+    const McScratch s = mc_split(const_cast<void *>(scratch), d.N);
+    k_mc_normals<<<ceil_div(d.N, kMcThreads), kMcThreads, 0, as_stream(stream)>>>(u, d, threshold, s.code, s.vbase, n_vertices, scale_x, scale_y, scale_z, normals,
+                                                                                  gradients);
+    return check_launch("mc_vertex_normals");
+}
+
+NSIG_EXPORT size_t mesh_components_scratch_bytes(uint32_t V, uint32_t T) {
+    if (V >= (1u << 31) || T >= (1u << 31)) return 0;
+    return kCcScratchBytes;
+}
+
+NSIG_EXPORT int mesh_components(const int32_t *triangles, uint32_t T, uint32_t V, int32_t *labels, void *scratch, nsig_stream_t stream) {
+    NSIG_REQUIRE(V < (1u << 31) && T < (1u << 31), "mesh_components: V=%u, T=%u out of range (each below 2^31)", V, T);
+    NSIG_REQUIRE(scratch && (triangles || T == 0) && (labels || V == 0), "mesh_components: null pointer");
+    NSIG_REQUIRE(reinterpret_cast<uintptr_t>(scratch) % 16 == 0, "mesh_components: scratch must be 16-byte aligned");
+    uint32_t *err = static_cast<uint32_t *>(scratch);
+    k_cc_init<<<max(1u, ceil_div(V, kCcThreads)), kCcThreads, 0, as_stream(stream)>>>(labels, V, err);
+    if (T) k_cc_hook<<<ceil_div(T, kCcThreads), kCcThreads, 0, as_stream(stream)>>>(triangles, T, V, labels, err);
+    if (T && V) k_cc_flatten<<<ceil_div(V, kCcThreads), kCcThreads, 0, as_stream(stream)>>>(labels, V);
+    return check_launch("mesh_components");
 }

@@ -4,10 +4,17 @@ The reference evaluates `model.density` on a 256^3 lattice in 128^3 chunks, copi
 on the CPU and exports a PLY through trimesh.  Here the lattice stays on the device and the marching cubes are HIP kernels
 (csrc/mesh.hip, table csrc/mc_tables.h from mc_table.py); only the finished mesh is copied back.
 
-    marching_cubes(u, threshold)                              -> vertices [V,3] fp32, triangles [T,3] int32 (device, lattice space)
+    marching_cubes(u, threshold, normals=False)               -> vertices [V,3] fp32, triangles [T,3] int32 (device, lattice space)[, normals [V,3]]
     lattice(model, bound_min, bound_max, resolution, message) -> the fp32 [R,R,R] density lattice, bit-identical to extract_fields
     extract_geometry(bound_min, bound_max, resolution, threshold, query_func)   the reference's signature and return types
-    save_mesh(model, path, resolution=256, threshold=10, message=None)          binary PLY over aabb_infer; returns (V, T)
+    save_mesh(model, path, resolution=256, threshold=10, message=None, ...)     binary PLY over aabb_infer; returns (V, T)
+
+Opt-in mesh attributes and cleaning, all on the device ("Mesh attributes"):
+
+    vertex_normals(u, threshold, scratch=None, scale=(1, 1, 1))   the normals of marching_cubes' vertices (mc_vertex_normals)
+    vertex_colors(model, vertices_world, normals, message=None)   the colour head seen against the normal, rgb [V,3] fp32
+    components(triangles, n_vertices)                             labels [V] int32: the smallest vertex id of each component (mesh_components)
+    clean(vertices, triangles, min_triangles=0, keep_largest=None, attributes=())   drop small components, stable compaction
 
 The triangulation is this project's table ("Mesh extraction"), not mcubes': the same surface, closed and consistently
 oriented, with its own choice in the ambiguous cases and its own triangle order.
@@ -26,20 +33,30 @@ LATTICE_CHUNK = 1 << 21      # points per field evaluation: the planes workspace
 REFERENCE_CHUNK = 128        # extract_fields' S
 
 
-def marching_cubes(u, threshold):
-    """Marching cubes of the device lattice u[nx, ny, nz] (fp32, z fastest) at `threshold` (inside: u > threshold) -> (vertices float32 [V,3],
-    triangles int32 [T,3]) on u's device, vertices in lattice space (the counterpart of mcubes.marching_cubes).  Output order: include/nerfsig.h."""
+def _check_lattice(u, who):
     if not isinstance(u, torch.Tensor) or not u.is_cuda:
-        raise ValueError("marching_cubes: the lattice must be a tensor on the GPU (there is no CPU path)")
+        raise ValueError(f"{who}: the lattice must be a tensor on the GPU (there is no CPU path)")
     if u.dtype != torch.float32:
-        raise ValueError(f"marching_cubes: the lattice must be float32, got {u.dtype}")
+        raise ValueError(f"{who}: the lattice must be float32, got {u.dtype}")
     if u.dim() != 3:
-        raise ValueError(f"marching_cubes: the lattice must be 3-D, got shape {tuple(u.shape)}")
+        raise ValueError(f"{who}: the lattice must be 3-D, got shape {tuple(u.shape)}")
     nx, ny, nz = (int(s) for s in u.shape)
     if min(nx, ny, nz) < 2:
-        raise ValueError(f"marching_cubes: every lattice dimension must be at least 2, got {tuple(u.shape)}")
+        raise ValueError(f"{who}: every lattice dimension must be at least 2, got {tuple(u.shape)}")
     if nx * ny * nz > MAX_NODES:
-        raise ValueError(f"marching_cubes: {nx} x {ny} x {nz} nodes is above the limit of 2^28")
+        raise ValueError(f"{who}: {nx} x {ny} x {nz} nodes is above the limit of 2^28")
+    return nx, ny, nz
+
+
+class McScratch:
+    """What mc_emit leaves behind for vertex_normals: the (contiguous) lattice, the threshold, the scratch with the node codes and vertex bases, and V."""
+
+    def __init__(self, u, threshold, buf, n_vertices):
+        self.u, self.threshold, self.buf, self.n_vertices = u, threshold, buf, n_vertices
+
+
+def _march(u, threshold, who="marching_cubes"):
+    nx, ny, nz = _check_lattice(u, who)
     thr = float(threshold)
     dev = u.device
     with torch.cuda.device(dev):
@@ -52,7 +69,45 @@ def marching_cubes(u, threshold):
         triangles = torch.empty(T, 3, dtype=torch.int32, device=dev)
         if V:
             nv.call("mc_emit", nv.ptr(u), nx, ny, nz, thr, nv.ptr(scratch), V, T, nv.ptr(vertices), nv.ptr(triangles), nv.stream())
+    return vertices, triangles, McScratch(u, thr, scratch, V)
+
+
+def marching_cubes(u, threshold, normals=False, scale=(1.0, 1.0, 1.0)):
+    """Marching cubes of the device lattice u[nx, ny, nz] (fp32, z fastest) at `threshold` (inside: u > threshold) -> (vertices float32 [V,3],
+    triangles int32 [T,3]) on u's device, vertices in lattice space (the counterpart of mcubes.marching_cubes).  Output order: include/nerfsig.h.
+    normals=True: -> (vertices, triangles, normals float32 [V,3]), the vertex normals of vertex_normals(u, threshold, scale=scale) from the same scratch."""
+    vertices, triangles, scratch = _march(u, threshold)
+    if normals:
+        return vertices, triangles, vertex_normals(scratch.u, threshold, scratch, scale)
     return vertices, triangles
+
+
+def vertex_normals(u, threshold, scratch=None, scale=(1.0, 1.0, 1.0), gradients=False):
+    """Unit normals float32 [V,3] of the vertices marching_cubes(u, threshold) returns, in their order: minus the lattice's finite-difference gradient,
+    interpolated along the vertex's edge, scaled per axis and normalised, all in fp32 (include/nerfsig.h, mc_vertex_normals); (0, 0, 0) where the
+    gradient is zero or not finite.  scratch: the McScratch of the marching-cubes call on this very lattice and threshold, or None to recompute it.
+    scale: lattice steps per world unit along x, y, z -- (R - 1) / (bound_max - bound_min) for world-space normals (lattice_scale), ones for lattice
+    space.  gradients=True: -> (normals, the scaled gradients before the division)."""
+    nx, ny, nz = _check_lattice(u, "vertex_normals")
+    thr = float(threshold)
+    if scratch is None:
+        scratch = _march(u, thr, "vertex_normals")[2]
+    elif scratch.threshold != thr or tuple(scratch.u.shape) != (nx, ny, nz) or scratch.u.device != u.device:
+        raise ValueError("vertex_normals: the scratch belongs to another lattice or threshold")
+    sx, sy, sz = (float(x) for x in scale)
+    dev, V = u.device, scratch.n_vertices
+    with torch.cuda.device(dev):
+        normals = torch.empty(V, 3, dtype=torch.float32, device=dev)
+        grads = torch.empty(V, 3, dtype=torch.float32, device=dev) if gradients else None
+        nv.call("mc_vertex_normals", nv.ptr(scratch.u), nx, ny, nz, thr, nv.ptr(scratch.buf), V, sx, sy, sz, nv.ptr(normals) if V else None,
+                nv.ptr(grads) if V else None, nv.stream())
+    return (normals, grads) if gradients else normals
+
+
+def lattice_scale(bound_min, bound_max, resolution):
+    """vertex_normals' scale for world-space normals of an R^3 lattice over [bound_min, bound_max]: (R - 1) / (bound_max - bound_min) per axis."""
+    lo, hi = _host(bound_min), _host(bound_max)
+    return tuple((resolution - 1.0) / (float(hi[a]) - float(lo[a])) for a in range(3))
 
 
 def _axes(bound_min, bound_max, resolution):
@@ -140,30 +195,183 @@ def extract_geometry(bound_min, bound_max, resolution, threshold, query_func):
     return to_world(v, t, bound_min, bound_max, resolution)
 
 
-def write_ply(path, vertices, triangles):
-    """Binary little-endian PLY: double x, y, z per vertex; list uchar int vertex_indices per face."""
+def world_vertices(vertices, bound_min, bound_max, resolution):
+    """to_world's mapping on the device: float64 [V,3] world positions of lattice-space vertices (the same operations in the same order)."""
+    dev = vertices.device
+    lo = torch.as_tensor(_host(bound_min)).to(dev)
+    hi = torch.as_tensor(_host(bound_max)).to(dev)
+    steps = torch.full((1, 1), resolution - 1.0, dtype=torch.float64, device=dev)      # a tensor: a Python scalar divisor becomes a multiplication by its reciprocal
+    return vertices.double() / steps * (hi - lo).double()[None, :] + lo.double()[None, :]
+
+
+@torch.no_grad()
+def vertex_colors(model, vertices_world, normals, message=None):
+    """rgb float32 [V,3] on the device: the model's colour head at every vertex, seen against the normal -- position float32(vertices_world), view
+    direction -normal, (0, 0, 1) where the normal is zero.  Queried through field_forward as lattice() queries the density (NeRFNetwork with or without a
+    message, CleanNeRFNetwork), in chunks of about 2 M vertices: up to one chunk the result is bit-equal to one model(x, d, message) call on these rows."""
+    bound, tables, S, packed = _field_of(model, message)
+    dev = packed.device
+    x = torch.as_tensor(vertices_world).to(dev, torch.float32).reshape(-1, 3).contiguous()
+    n = torch.as_tensor(normals).to(dev, torch.float32).reshape(-1, 3)
+    if n.shape != x.shape:
+        raise ValueError(f"vertex_colors: {x.shape[0]} vertices with {n.shape[0]} normals")
+    zero = (n == 0).all(dim=-1, keepdim=True)
+    d = torch.where(zero, torch.tensor([0.0, 0.0, 1.0], device=dev), -n).contiguous()
+    V = x.shape[0]
+    rgb = torch.empty(V, 3, dtype=torch.float32, device=dev)
+    n_chunks = max(1, math.ceil(V / LATTICE_CHUNK))
+    step = max(1, math.ceil(V / n_chunks))
+    for s in range(0, V, step):
+        _, c, _, _ = fo.field_forward(x[s:s + step], d[s:s + step], bound, tables, S, packed)
+        rgb[s:s + step] = c
+    return rgb
+
+
+def quantize_colors(rgb):
+    """The PLY's bytes of float colours: uint8(floor(clamp(c, 0, 1) * 255 + 0.5)) (numpy array or tensor, same kind back)."""
+    if isinstance(rgb, torch.Tensor):
+        return torch.floor(rgb.float().clamp(0.0, 1.0) * 255.0 + 0.5).to(torch.uint8)
+    c = np.clip(np.asarray(rgb, np.float32), np.float32(0), np.float32(1))
+    return np.floor(c * np.float32(255) + np.float32(0.5)).astype(np.uint8)
+
+
+# ---- components and cleaning ------------------------------------------------------------------------------------------------------------------------------
+
+CC_OK = 0xFFFFFFFF           # mesh_components' status word when every id was in range
+MAX_ELEMENTS = 1 << 31       # mesh_components: V, T below 2^31
+
+
+def _check_triangles(triangles, who):
+    if not isinstance(triangles, torch.Tensor) or not triangles.is_cuda:
+        raise ValueError(f"{who}: the triangles must be a tensor on the GPU (there is no CPU path)")
+    if triangles.dtype != torch.int32 or triangles.dim() != 2 or triangles.shape[1] != 3:
+        raise ValueError(f"{who}: the triangles must be int32 [T,3], got {triangles.dtype} {tuple(triangles.shape)}")
+    return triangles.contiguous()
+
+
+def _components(triangles, V):
+    """(labels [V] int32, status [1] int64 on the device: CC_OK or the first triangle with an id outside [0, V)); nothing is read back."""
+    T = int(triangles.shape[0])
+    if not 0 <= V < MAX_ELEMENTS or T >= MAX_ELEMENTS:
+        raise ValueError(f"components: V={V}, T={T} out of range (each below 2^31)")
+    dev = triangles.device
+    with torch.cuda.device(dev):
+        labels = torch.empty(V, dtype=torch.int32, device=dev)
+        scratch = torch.empty(int(nv.fn("mesh_components_scratch_bytes")(V, T)), dtype=torch.uint8, device=dev)
+        nv.call("mesh_components", nv.ptr(triangles) if T else None, T, V, nv.ptr(labels) if V else None, nv.ptr(scratch), nv.stream())
+    return labels, scratch[:4].view(torch.int32).to(torch.int64) & CC_OK
+
+
+def _refuse_bad_ids(status, V):
+    if status != CC_OK:
+        raise ValueError(f"components: triangle {status} has a vertex id outside [0, {V})")
+
+
+def components(triangles, n_vertices):
+    """Connected components of the mesh graph (vertices; the sides of every triangle): labels int32 [V] on the device, labels[v] = the smallest vertex id
+    of v's component; a vertex in no triangle labels itself.  Any int32 [T,3] triangle list with ids in [0, V); an id outside raises ValueError."""
+    triangles = _check_triangles(triangles, "components")
+    labels, status = _components(triangles, int(n_vertices))
+    _refuse_bad_ids(int(status.item()), int(n_vertices))
+    return labels
+
+
+def _kept(mask):
+    """(running count of a bool mask, int64; a function n -> the indices of its n true entries in order, without a host read)."""
+    run = torch.cumsum(mask, 0)
+    return run, lambda n: torch.searchsorted(run, torch.arange(1, n + 1, dtype=run.dtype, device=run.device))
+
+
+def clean(vertices, triangles, min_triangles=0, keep_largest=None, attributes=()):
+    """Remove small components ("floaters") on the device -> (vertices, triangles, *attributes) compacted.  A component survives if it has at least
+    min_triangles triangles and, with keep_largest=k, is among the k components of most triangles (ties: the smaller label first).  Surviving vertices
+    and triangles keep their relative order, triangle ids are remapped, every tensor of `attributes` ([V, ...]) is compacted with the vertices, and
+    vertices no surviving triangle uses are dropped.  One host read (the new sizes); the mesh is not copied to the host."""
+    triangles = _check_triangles(triangles, "clean")
+    V, T = int(vertices.shape[0]), int(triangles.shape[0])
+    if keep_largest is not None and int(keep_largest) < 0 or int(min_triangles) < 0:
+        raise ValueError("clean: min_triangles and keep_largest must not be negative")
+    for a in attributes:
+        if a.shape[0] != V or a.device != vertices.device:
+            raise ValueError("clean: every attribute must have one row per vertex, on the vertices' device")
+    dev = triangles.device
+    labels, status = _components(triangles, V)
+    with torch.cuda.device(dev):
+        tri = triangles.long().clamp(0, max(V - 1, 0))                    # (ids out of range are refused below, before anything is returned)
+        lab = labels.long()
+        tlabel = lab[tri[:, 0]] if V else tri[:, 0]
+        count = torch.zeros(V, dtype=torch.int64, device=dev).scatter_add_(0, tlabel, torch.ones_like(tlabel))       # triangles per component, at its label
+        keep = count >= max(int(min_triangles), 1)
+        if keep_largest is not None:
+            order = torch.sort(count, descending=True, stable=True).indices[:int(keep_largest)]       # stable: equal counts stay in label order
+            top = torch.zeros(V, dtype=torch.bool, device=dev)
+            top[order] = True
+            keep &= top
+        used = torch.zeros(V, dtype=torch.bool, device=dev)
+        used[tri.reshape(-1)] = True
+        vkeep = keep[lab] & used
+        tkeep = keep[tlabel]
+        vrun, vidx = _kept(vkeep)
+        trun, tidx = _kept(tkeep)
+        zero = torch.zeros(1, dtype=torch.int64, device=dev)
+        Vn, Tn, st = torch.cat([vrun[-1:] if V else zero, trun[-1:] if T else zero, status]).tolist()        # the one host read
+        _refuse_bad_ids(st, V)
+        vi, ti = vidx(Vn), tidx(Tn)
+        new_id = (vrun - 1).to(torch.int32)
+        out_t = new_id[triangles.index_select(0, ti).long()]
+        return (vertices.index_select(0, vi), out_t) + tuple(a.index_select(0, vi) for a in attributes)
+
+
+# ---- PLY ----------------------------------------------------------------------------------------------------------------------------------------------
+
+def write_ply(path, vertices, triangles, normals=None, colors=None):
+    """Binary little-endian PLY: double x, y, z per vertex, then float nx, ny, nz when normals [V,3] are given, then uchar red, green, blue when
+    colors are given (uint8 as they are, floats through quantize_colors); list uchar int vertex_indices per face."""
     vertices = np.ascontiguousarray(vertices, dtype="<f8").reshape(-1, 3)
     triangles = np.asarray(triangles).reshape(-1, 3)
     faces = np.empty(triangles.shape[0], dtype=[("n", "u1"), ("v", "<i4", (3,))])
     faces["n"] = 3
     faces["v"] = triangles
-    header = (f"ply\nformat binary_little_endian 1.0\nelement vertex {vertices.shape[0]}\nproperty double x\nproperty double y\nproperty double z\n"
+    fields, props = [("p", "<f8", (3,))], "property double x\nproperty double y\nproperty double z\n"
+    if normals is not None:
+        fields.append(("n", "<f4", (3,)))
+        props += "property float nx\nproperty float ny\nproperty float nz\n"
+    if colors is not None:
+        fields.append(("c", "u1", (3,)))
+        props += "property uchar red\nproperty uchar green\nproperty uchar blue\n"
+    if len(fields) == 1:
+        record = vertices
+    else:
+        record = np.empty(vertices.shape[0], dtype=fields)
+        record["p"] = vertices
+        if normals is not None:
+            record["n"] = np.asarray(normals, dtype="<f4").reshape(vertices.shape[0], 3)
+        if colors is not None:
+            colors = np.asarray(colors)
+            record["c"] = (colors if colors.dtype == np.uint8 else quantize_colors(colors)).reshape(vertices.shape[0], 3)
+    header = (f"ply\nformat binary_little_endian 1.0\nelement vertex {vertices.shape[0]}\n{props}"
               f"element face {triangles.shape[0]}\nproperty list uchar int vertex_indices\nend_header\n")
     with open(path, "wb") as f:
         f.write(header.encode("ascii"))
-        f.write(vertices.tobytes())
+        f.write(record.tobytes())
         f.write(faces.tobytes())
 
 
-def save_mesh(model, path, resolution=256, threshold=10, message=None):
+def save_mesh(model, path, resolution=256, threshold=10, message=None, normals=False, colors=False, min_triangles=0, keep_largest=None):
     """Trainer.save_mesh (nerf/utils.py:611): the mesh of `model`'s density over aabb_infer, written to `path` as a binary PLY.
-    Returns (vertex count, triangle count)."""
+    Returns (vertex count, triangle count).  Opt-in, all computed on the device before the one copy of the finished mesh: normals=True writes world-space
+    vertex normals; colors=True writes the colour head seen against the normal (normals are computed for it, written only with normals=True);
+    min_triangles / keep_largest remove small components first (clean), and the counts returned are those after cleaning."""
     bmin, bmax = model.aabb_infer[:3], model.aabb_infer[3:]
     u = lattice(model, bmin, bmax, resolution, message)
-    v, t = marching_cubes(u, threshold)
+    want_n = bool(normals or colors)
+    v, t, *n = marching_cubes(u, threshold, normals=want_n, scale=lattice_scale(bmin, bmax, resolution))
+    if min_triangles or keep_largest is not None:
+        v, t, *n = clean(v, t, min_triangles, keep_largest, attributes=n)
+    rgb = quantize_colors(vertex_colors(model, world_vertices(v, bmin, bmax, resolution), n[0], message)).cpu().numpy() if colors else None
     vertices, triangles = to_world(v, t, bmin, bmax, resolution)
     d = os.path.dirname(path)
     if d:
         os.makedirs(d, exist_ok=True)
-    write_ply(path, vertices, triangles)
+    write_ply(path, vertices, triangles, normals=n[0].cpu().numpy() if normals else None, colors=rgb)
     return vertices.shape[0], triangles.shape[0]

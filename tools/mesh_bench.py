@@ -4,6 +4,7 @@
     python tools/mesh_bench.py [--out profiles/mesh_bench.json]            # timings (device events + a synchronise), V and T
     rocprofv3 --kernel-trace --stats -d DIR -- python tools/mesh_bench.py --kernels-only
     python tools/mesh_bench.py --stats DIR [--out ...]                     # add the MC kernels' bytes / kernel time from DIR's *_kernel_stats.csv
+    python tools/mesh_bench.py --attributes [--out ...]                    # add the attribute and cleaning stages to the runs already in --out
 
 Per R it reports the lattice evaluation (mesh.lattice), the marching-cubes call (mc_count, the one totals read, mc_emit) and the
 device-to-host copy of the mesh separately, and the reference-shaped route: extract_fields' 128^3 chunks through model.density with a
@@ -11,6 +12,11 @@ device-to-host copy of the mesh separately, and the reference-shaped route: extr
 a lower bound on a CPU marching cubes' time).  Bytes of the MC kernels, per call, from shapes: count reads u (4 N) and writes the node
 codes (2 N); vertex emit reads them (2 N), writes the vertex bases (4 N) and the vertices (12 V); triangle emit reads codes and bases
 (6 N) and writes the triangles (12 T): 18 N + 12 V + 12 T, neighbour re-reads counted once (they hit the caches).
+
+--attributes times, per R, the stages behind save_mesh's options on the device -- vertex normals (mc_vertex_normals from mc_emit's scratch), vertex
+colours (the field forward at every vertex), components (mesh_components, no host read) and clean (components, filter at 8 triangles, compaction of the
+vertices, the triangles and the normals, one host read) -- and beside them the host route they replace: copying the mesh to the host, scipy's
+connected_components, and the numpy filter and compaction (tests/mesh_attr_ref.py's, on scipy's labels).
 """
 import argparse
 import csv
@@ -100,6 +106,55 @@ def run(resolutions, reps, threads):
     return rec
 
 
+def host_route(v, t, n, min_triangles):
+    """(copy ms, scipy components ms, numpy filter + compaction ms, components) of the same cleaning through the host."""
+    from scipy.sparse import coo_matrix
+    from scipy.sparse.csgraph import connected_components
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    hv, ht, hn = v.cpu().numpy(), t.cpu().numpy(), n.cpu().numpy()
+    t1 = time.perf_counter()
+    V = len(hv)
+    r, c = ht[:, [0, 1, 2]].reshape(-1), ht[:, [1, 2, 0]].reshape(-1)
+    ncomp, lab = connected_components(coo_matrix((np.ones(r.size, np.int8), (r, c)), shape=(V, V)), directed=False)
+    t2 = time.perf_counter()
+    count = np.bincount(lab[ht[:, 0]], minlength=ncomp)
+    keep = count >= max(min_triangles, 1)
+    vkeep, tkeep = keep[lab], keep[lab[ht[:, 0]]]
+    new_id = np.cumsum(vkeep) - 1
+    out = hv[vkeep], new_id[ht[tkeep]].astype(np.int32), hn[vkeep]
+    t3 = time.perf_counter()
+    return (t1 - t0) * 1e3, (t2 - t1) * 1e3, (t3 - t2) * 1e3, int(ncomp), len(out[0]), len(out[1])
+
+
+def attributes(resolutions, reps, min_triangles=8):
+    """Per R: device times of normals, colours, components and clean, and the host route of the cleaning."""
+    from nerf_signature_amd import mesh
+    m = model()
+    lo, hi = m.aabb_infer[:3], m.aabb_infer[3:]
+    out = {}
+    for R in resolutions:
+        u = mesh.lattice(m, lo, hi, R)
+        scale = mesh.lattice_scale(lo, hi, R)
+        v, t, scratch = mesh._march(u, THRESHOLD)
+        n = mesh.vertex_normals(u, THRESHOLD, scratch, scale)                 # warm-ups: code objects, allocator
+        x = mesh.world_vertices(v, lo, hi, R).float()
+        mesh.vertex_colors(m, x, n)
+        mesh.clean(v, t, min_triangles, attributes=(n,))
+        normals_ms, _ = timed(lambda: mesh.vertex_normals(u, THRESHOLD, scratch, scale), reps)
+        colours_ms, _ = timed(lambda: mesh.vertex_colors(m, x, n), reps)
+        comp_ms, (labels, _) = timed(lambda: mesh._components(t, v.shape[0]), reps)
+        clean_ms, (cv, ct, cn) = timed(lambda: mesh.clean(v, t, min_triangles, attributes=(n,)), reps)
+        host = sorted(host_route(v, t, n, min_triangles) for _ in range(3))[1]
+        rec = {"V": v.shape[0], "T": t.shape[0], "components": int(torch.unique(labels[t[:, 0].long()]).numel()), "min_triangles": min_triangles,
+               "V_clean": cv.shape[0], "T_clean": ct.shape[0], "normals_ms": normals_ms, "colours_ms": colours_ms, "components_ms": comp_ms,
+               "clean_ms": clean_ms, "host_route": {"d2h_ms": host[0], "scipy_components_ms": host[1], "numpy_filter_ms": host[2],
+                                                      "components": host[3], "V_clean": host[4], "T_clean": host[5]}}
+        out[R] = rec
+        print(json.dumps(dict(rec, R=R)), flush=True)
+    return out
+
+
 def kernels_only(resolutions, reps):
     """What the profiled run executes: the lattice and the marching cubes, reps times per R."""
     from nerf_signature_amd import mesh
@@ -127,6 +182,7 @@ def main():
     ap.add_argument("--threads", type=int, default=16)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "mesh_bench.json"))
     ap.add_argument("--kernels-only", action="store_true")
+    ap.add_argument("--attributes", action="store_true", help="add the attribute and cleaning stages to the runs already in --out")
     ap.add_argument("--stats", help="directory of a rocprofv3 --kernel-trace --stats run of --kernels-only, one R per run: --resolutions R")
     a = ap.parse_args()
     if not torch.cuda.is_available():
@@ -134,7 +190,11 @@ def main():
     if a.kernels_only:
         kernels_only(a.resolutions, a.reps)
         return
-    if a.stats:
+    if a.attributes:
+        rec = json.load(open(a.out))
+        for R, r in attributes(a.resolutions, a.reps).items():
+            next(x for x in rec["runs"] if x["R"] == R)["attributes"] = r
+    elif a.stats:
         rec = json.load(open(a.out))
         if len(a.resolutions) != 1:
             sys.exit("--stats: give the one resolution the profiled run used")
