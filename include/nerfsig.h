@@ -391,6 +391,31 @@ int field_fwd_twin(const float *xyzs, const float *dirs, uint32_t M, float bound
                    const float *S, const void *packed, float *sigmas, float *rgbs, float *geo_feat, uint32_t *masks,
                    const void *planes, int planes_layout, float *sigmas_clean, float *rgbs_clean, nsig_stream_t stream);
 
+/* One set of points under K messages in a single field pass (inference: forward only).  Nothing but the codebook depends on the message, so the march, the
+ * 16 base planes and the directions are shared and only the codebook level exists K times:
+ *   hg_codebook_presum_multi         S_k[t] = sum_i table[2i + bit_{k,i}][t] for K messages [K, D] (device floats 0. / 1., as hg_codebook_presum_sel; no launch argument
+ *                                    depends on a message's value) in ONE pass over the 2 D tables, each read once; per message the serial sum in table order, so S_k
+ *                                    has the bits of hg_codebook_presum_sel with message k.  S_multi, hg_multi_presum_bytes(K) bytes, 16-byte aligned, is
+ *                                    ROW-INTERLEAVED: float2 S_multi[NSIG_TABLE_ROWS][K], element [t][k] = S_k[t] -- the K values of a row are 8 K contiguous
+ *                                    bytes.  The layout is private to these three entry points.
+ *   hg_encode_codebook_planes_multi  the codebook level of M points under all K messages: cplanes, hg_multi_planes_bytes(M, K) bytes, is K planes of float2,
+ *                                    message-major, float2 cplanes[K][stride] with the point stride of a plane set of M points (hg_planes_bytes(M) / 17 / 8); plane k
+ *                                    has the bits of plane 16 written by hg_encode_codebook_plane from S_k.
+ *   field_fwd_multi                  sigmas [K, M] and rgbs [K, M, 3] (no masks, no geo features): each 32-point tile loads the 16 base planes of `planes` (a plane
+ *                                    set in `planes_layout`; its plane 16 is neither read nor written) once and evaluates the MLP chain K times (the direction is read by the chain),
+ *                                    level 15's operand formed from f15 + cplanes[k] as field_fwd forms it from plane 16.  Slice k has the bits of field_fwd with S_k
+ *                                    over a plane set encoded with S_k.  fp16 MLP with either layout, split-bf16 MLP with NSIG_PLANES_F32.
+ * NSIG_MULTI_MAX_MESSAGES is the largest K of one launch, sized by registers: the pre-sum keeps one float4 accumulator per message (64 VGPRs at 16). */
+#define NSIG_MULTI_MAX_MESSAGES 16
+size_t hg_multi_presum_bytes(uint32_t K);
+int hg_codebook_presum_multi(const float *const *all_tables_host, const float *messages, uint32_t K, uint32_t D, void *S_multi,
+                             nsig_stream_t stream);
+size_t hg_multi_planes_bytes(uint32_t M, uint32_t K);
+int hg_encode_codebook_planes_multi(const float *xyzs, uint32_t M, float bound, const void *S_multi, uint32_t K, void *cplanes,
+                                    nsig_stream_t stream);
+int field_fwd_multi(const float *dirs, uint32_t M, const void *packed, const void *planes, int planes_layout, const void *cplanes,
+                    uint32_t K, float *sigmas, float *rgbs, nsig_stream_t stream);
+
 /* The encoder of field_fwd as its own pass: planes[level][point] (float2; 16 base levels + the pre-summed codebook as
  * plane 16), hg_planes_bytes(M) bytes.  Workgroup (tile, slot = blockIdx % 8) encodes only the levels assigned to
  * its slot, so each XCD's L2 serves the gathers of one fine table (see csrc/field.hip). */

@@ -83,6 +83,11 @@ SIGNATURES = {
     "hg_encode_codebook_plane": [_vp, _u32, _fl, _vp, _vp, _int, _vp, _vp],
     "field_fwd": [_vp, _vp, _u32, _fl, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _int, _vp],
     "field_fwd_twin": [_vp, _vp, _u32, _fl, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _int, _vp, _vp, _vp],
+    "hg_multi_presum_bytes": [_u32],
+    "hg_codebook_presum_multi": [_vp, _vp, _u32, _u32, _vp, _vp],
+    "hg_multi_planes_bytes": [_u32, _u32],
+    "hg_encode_codebook_planes_multi": [_vp, _u32, _fl, _vp, _u32, _vp, _vp],
+    "field_fwd_multi": [_vp, _u32, _vp, _vp, _int, _vp, _u32, _vp, _vp, _vp],
     "field_color_fwd": [_vp, _vp, _u32, _vp, _vp, _vp],
     "opt_adam_dense_host": [_u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _fl, _fl, _fl, _fl, _vp],
     "opt_adam_dense": [_u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _fl, _fl, _fl, _fl, _vp, _vp],
@@ -143,7 +148,7 @@ SIGNATURES = {
     "im_ssim_scratch_bytes": [_u32, _u32, _u32, _u32],
     "im_ssim": [_vp, _vp, _u32, _u32, _u32, _u32, _vp, _fl, _vp, _vp, _vp, _vp],
 }
-_RESTYPES = {"nsig_last_error": _c.c_char_p, "nsig_host_device_pointer": _c.c_void_p, "rm_march_train_scratch_bytes": _sz, "mlp_packed_bytes": _sz, "hg_planes_bytes": _sz, "dec_workspace_bytes": _sz, "hg_scatter_levels_scratch_bytes": _sz, "hg_scatter_binned_scratch_bytes": _sz, "hg_scatter_plan_bytes": _sz, "field_wgrad_scratch_bytes": _sz, "field_bwd_wgrad_scratch_bytes": _sz, "hg_levels_plan_bytes": _sz, "rg_refresh_partials_bytes": _sz, "rg_refresh_draw_scratch_bytes": _sz, "mc_scratch_bytes": _sz, "mesh_components_scratch_bytes": _sz, "im_range_scratch_bytes": _sz, "im_ssim_scratch_bytes": _sz}
+_RESTYPES = {"nsig_last_error": _c.c_char_p, "nsig_host_device_pointer": _c.c_void_p, "rm_march_train_scratch_bytes": _sz, "mlp_packed_bytes": _sz, "hg_planes_bytes": _sz, "hg_multi_presum_bytes": _sz, "hg_multi_planes_bytes": _sz, "dec_workspace_bytes": _sz, "hg_scatter_levels_scratch_bytes": _sz, "hg_scatter_binned_scratch_bytes": _sz, "hg_scatter_plan_bytes": _sz, "field_wgrad_scratch_bytes": _sz, "field_bwd_wgrad_scratch_bytes": _sz, "hg_levels_plan_bytes": _sz, "rg_refresh_partials_bytes": _sz, "rg_refresh_draw_scratch_bytes": _sz, "mc_scratch_bytes": _sz, "mesh_components_scratch_bytes": _sz, "im_range_scratch_bytes": _sz, "im_ssim_scratch_bytes": _sz}
 
 _lib = None
 

@@ -247,6 +247,42 @@ __global__ void __launch_bounds__(256) k_encode_codebook_plane(const float *__re
     encode_tile_level(reinterpret_cast<const float2 *>(S), cell, threadIdx.x & 1u, x, y, z, plane + m);
 }
 
+// The codebook level of M points under K messages at once (hg_encode_codebook_planes_multi): S is K pre-sums row-interleaved, S[row][k] (float2), so one corner
+// of one point is ONE contiguous read of 8 K bytes for all messages.  A group of G consecutive lanes shares a point: lane j of the group reads, of each of the
+// point's eight rows, messages 2 j and 2 j + 1 as one 16-byte load (kPair: K even, G = K / 2) or message j as one 8-byte load (K odd, G = K) -- a group's loads
+// of a row are adjacent, a wave's instruction touches 64 / G rows instead of 64.  Every lane derives its point's rows and weights itself (corner_rows; no lane
+// exchange, so groups may straddle waves), interpolates with trilerp as encode_tile_level does -- plane k has the bits of hg_encode_codebook_plane from S_k -- and
+// writes cplanes[k][point].  Rows in [M, stride) replicate the last point, as there.
+template <bool kPair>
+__global__ void __launch_bounds__(256) k_encode_codebook_planes_multi(const float *__restrict__ xyzs, uint32_t M, float bound, float cell, const float2 *__restrict__ S,
+                                                                      uint32_t K, uint32_t G, float2 *__restrict__ cplanes, uint32_t stride) {
+    const uint64_t gid = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    const uint32_t m = (uint32_t)(gid / G), j = (uint32_t)(gid - (uint64_t)m * G);
+    if (m >= stride) return;
+    const uint32_t ml = min(m, M - 1);
+    const float two_b = 2.0f * bound;
+    const float3 pt = *reinterpret_cast<const float3 *>(xyzs + 3 * (size_t)ml);
+    const float x = (pt.x + bound) / two_b, y = (pt.y + bound) / two_b, z = (pt.z + bound) / two_b;
+    Corner8 c;
+    corner_rows(x, y, z, cell, c);
+    float2 e[8];
+    if constexpr (kPair) {
+        float4 v[8];
+#pragma unroll
+        for (int q = 0; q < 8; ++q) v[q] = *reinterpret_cast<const float4 *>(S + (size_t)c.row[q] * K + 2 * j);
+#pragma unroll
+        for (int q = 0; q < 8; ++q) e[q] = make_float2(v[q].x, v[q].y);
+        cplanes[(size_t)(2 * j) * stride + m] = trilerp(e, c.wx, c.wy, c.wz);
+#pragma unroll
+        for (int q = 0; q < 8; ++q) e[q] = make_float2(v[q].z, v[q].w);
+        cplanes[(size_t)(2 * j + 1) * stride + m] = trilerp(e, c.wx, c.wy, c.wz);
+    } else {
+#pragma unroll
+        for (int q = 0; q < 8; ++q) e[q] = S[(size_t)c.row[q] * K + j];
+        cplanes[(size_t)j * stride + m] = trilerp(e, c.wx, c.wy, c.wz);
+    }
+}
+
 // (k_field_fwd's kPlanes = 0: gather the features in-kernel (fused); 1: read all 17 from the level-major planes.)
 // The training render's forward launch (all 17 feature planes in memory, sigma + rgb + ReLU masks out), software-pipelined over a wave's tiles.
 // The plain loop -- load, evaluate, store, next tile -- spends most of a tile's ~4.9 us waiting, three times: for the planes at its head, for the
@@ -513,6 +549,51 @@ __global__ void __launch_bounds__(256) k_field_fwd_twin(const float *__restrict_
             uint32_t *const no_masks = nullptr;
 #define CHAIN_SIGMAS sigmas_clean
 #define CHAIN_RGBS rgbs_clean
+#define CHAIN_GEO no_geo
+#define CHAIN_MASKS no_masks
+#include "field_chain_plain.h"
+#undef CHAIN_SIGMAS
+#undef CHAIN_RGBS
+#undef CHAIN_GEO
+#undef CHAIN_MASKS
+        }
+    }
+}
+
+// field_fwd_multi: the twin's structure under K codebook planes.  A tile's 16 base planes are loaded once (its direction is read inside the chain fragment, so that
+// load is written inside the message loop: dirs is const __restrict__ and hoisting it is the compiler's to do; the values are the same either way); per message k level 15's operand word is formed from
+// f15 + cplanes[k] exactly as k_field_fwd forms it from plane 16 (the sum in fp32, then the operand's rounding) and the chain is evaluated on it: slice k of the
+// outputs (sigmas [K, M], rgbs [K, M, 3]) has the bits of k_field_fwd<P, 1> with S_k.  Plane 16 of `planes` is neither read nor written; no masks, no geo features.
+template <typename P>
+__global__ void __launch_bounds__(256) k_field_fwd_multi(const float *__restrict__ dirs, uint32_t M, const float2 *__restrict__ planes, uint32_t stride,
+                                                         const char *__restrict__ packed, bool mixed, const float2 *__restrict__ cplanes, uint32_t K,
+                                                         float *__restrict__ sigmas, float *__restrict__ rgbs) {
+    extern __shared__ __attribute__((aligned(16))) char lds[];
+    stage_weights(lds, packed + P::kFwdOffset, (int)P::kFwdLds);
+    constexpr size_t kHalf = kFwdBytes;
+    constexpr bool kTrace = false;
+    const ActTrace trace{};
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    const int p = lane & 31, h = lane >> 5;
+    const uint32_t n_tiles = ceil_div(M, 32u);
+    for (uint32_t tile = blockIdx.x * 4 + wid; tile < n_tiles; tile += gridDim.x * 4) {
+        const uint32_t s = tile * 32 + p;
+        const uint32_t sl = min(s, M - 1);
+        float2 f[8];
+#pragma unroll
+        for (int q = 0; q < 8; ++q) f[q] = load_plane(planes, stride, 8 * (q >> 2) + (q & 3) + 4 * h, s, mixed);
+        typename P::Op feat[2];
+#pragma unroll
+        for (int q = 0; q < 8; ++q) P::put2(feat[q >> 2], q & 3, f[q].x, f[q].y);
+        for (uint32_t k = 0; k < K; ++k) {
+            if (h) {  // codebook added into channels 30:32 (network_wtmk_tcnn.py:106)
+                const float2 c = cplanes[(size_t)k * stride + s];
+                P::put2(feat[1], 3, f[7].x + c.x, f[7].y + c.y);
+            }
+            float *const sigmas_k = sigmas + (size_t)k * M, *const rgbs_k = rgbs + (size_t)k * M * 3, *const no_geo = nullptr;
+            uint32_t *const no_masks = nullptr;
+#define CHAIN_SIGMAS sigmas_k
+#define CHAIN_RGBS rgbs_k
 #define CHAIN_GEO no_geo
 #define CHAIN_MASKS no_masks
 #include "field_chain_plain.h"
@@ -1143,6 +1224,53 @@ NSIG_EXPORT int field_fwd_twin(const float *xyzs, const float *dirs, uint32_t M,
     NSIG_REQUIRE(planes != nullptr, "field_fwd_twin: needs a plane set (hg_encode_planes / _mixed with S): the fused no-planes route has no plane 16 to leave out");
     NSIG_REQUIRE(S != nullptr, "field_fwd_twin: S is NULL -- without a codebook both results are field_fwd's");
     return field_fwd_impl(xyzs, dirs, M, bound, base_tables_host, S, packed, sigmas, rgbs, geo_feat, masks, planes, planes_layout, nullptr, stream, sigmas_clean, rgbs_clean);
+}
+
+// ---- K messages over one set of points (hg_codebook_presum_multi in hashgrid.hip makes S_multi)
+static int check_multi_k(uint32_t K, const char *who) {
+    NSIG_REQUIRE(K >= 1 && K <= NSIG_MULTI_MAX_MESSAGES, "%s: K=%u out of range [1,%d]", who, K, NSIG_MULTI_MAX_MESSAGES);
+    return NSIG_OK;
+}
+
+NSIG_EXPORT size_t hg_multi_planes_bytes(uint32_t M, uint32_t K) { return (size_t)K * ceil_div(M, 32u) * 32u * sizeof(float2); }
+
+NSIG_EXPORT int hg_encode_codebook_planes_multi(const float *xyzs, uint32_t M, float bound, const void *S_multi, uint32_t K, void *cplanes, nsig_stream_t stream) {
+    NSIG_REQUIRE(xyzs && S_multi && cplanes, "hg_encode_codebook_planes_multi: null pointer");
+    if (int e = check_multi_k(K, "hg_encode_codebook_planes_multi")) return e;
+    NSIG_REQUIRE(bound > 0.0f, "hg_encode_codebook_planes_multi: bound must be positive");
+    NSIG_REQUIRE((reinterpret_cast<uintptr_t>(S_multi) & 15) == 0, "hg_encode_codebook_planes_multi: S_multi must be 16-byte aligned");
+    NSIG_REQUIRE((reinterpret_cast<uintptr_t>(cplanes) & 7) == 0, "hg_encode_codebook_planes_multi: cplanes must be 8-byte aligned");
+    NSIG_REQUIRE(M <= (1u << 27), "hg_encode_codebook_planes_multi: M=%u too large", M);
+    if (M == 0) return NSIG_OK;
+    const uint32_t stride = ceil_div(M, 32u) * 32u;
+    const bool pair = (K & 1u) == 0u;
+    const uint32_t G = pair ? K / 2 : K;
+    const uint32_t grid = (uint32_t)(((uint64_t)stride * G + 255) / 256);
+    const float cell = make_level_geom().cell[NSIG_BASE_LEVELS];
+    const float2 *S = reinterpret_cast<const float2 *>(S_multi);
+    if (pair) k_encode_codebook_planes_multi<true><<<grid, 256, 0, as_stream(stream)>>>(xyzs, M, bound, cell, S, K, G, reinterpret_cast<float2 *>(cplanes), stride);
+    else k_encode_codebook_planes_multi<false><<<grid, 256, 0, as_stream(stream)>>>(xyzs, M, bound, cell, S, K, G, reinterpret_cast<float2 *>(cplanes), stride);
+    return check_launch("hg_encode_codebook_planes_multi");
+}
+
+NSIG_EXPORT int field_fwd_multi(const float *dirs, uint32_t M, const void *packed, const void *planes, int planes_layout, const void *cplanes, uint32_t K,
+                                float *sigmas, float *rgbs, nsig_stream_t stream) {
+    NSIG_REQUIRE(dirs && packed && planes && cplanes && sigmas && rgbs, "field_fwd_multi: null pointer");
+    if (int e = check_multi_k(K, "field_fwd_multi")) return e;
+    if (int e = check_layout(planes_layout, "field_fwd_multi")) return e;
+    NSIG_REQUIRE((reinterpret_cast<uintptr_t>(packed) & 15) == 0, "field_fwd_multi: packed must be 16-byte aligned");
+    NSIG_REQUIRE((reinterpret_cast<uintptr_t>(planes) & 7) == 0 && (reinterpret_cast<uintptr_t>(cplanes) & 7) == 0, "field_fwd_multi: planes and cplanes must be 8-byte aligned");
+    const bool f16 = mlp_precision() == 1, mixed = planes_layout == NSIG_PLANES_MIXED;
+    NSIG_REQUIRE(!mixed || f16, "field_fwd_multi: this plane set was written in the mixed (fp16) layout; the split-bf16 MLP needs hg_encode_planes");
+    NSIG_REQUIRE(M <= (1u << 27), "field_fwd_multi: M=%u too large", M);      // (the same range as the gather that fills cplanes: row indices and the stride stay far from 2^32)
+    if (M == 0) return NSIG_OK;
+    const uint32_t stride = ceil_div(M, 32u) * 32u;
+    const float2 *pl = reinterpret_cast<const float2 *>(planes), *cp = reinterpret_cast<const float2 *>(cplanes);
+    const char *pk = reinterpret_cast<const char *>(packed);
+    hipStream_t st = as_stream(stream);
+    if (f16) k_field_fwd_multi<F16><<<field_grid(M, true), 256, F16::kFwdLds, st>>>(dirs, M, pl, stride, pk, mixed, cp, K, sigmas, rgbs);
+    else k_field_fwd_multi<Bf16x3><<<field_grid(M, true), 256, Bf16x3::kFwdLds, st>>>(dirs, M, pl, stride, pk, false, cp, K, sigmas, rgbs);
+    return check_launch("field_fwd_multi");
 }
 
 NSIG_EXPORT int field_fwd_rows(const float *xyzs, const float *dirs, uint32_t M_capacity, const uint32_t *rows_dev, float bound,

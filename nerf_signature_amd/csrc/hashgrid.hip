@@ -1047,6 +1047,66 @@ __global__ void __launch_bounds__(256) k_codebook_presum_sel(PairPtrs tabs, cons
     S[e] = acc;
 }
 
+// hg_codebook_presum_multi: K messages in ONE pass over the 2 D tables.  A thread owns the same float4 (two rows) of every table as above, reads BOTH tables of
+// a pair once and adds, per message, the one the message's bit names -- per message the serial sum in table order of k_codebook_presum_sel, so S_k has its bits.
+// bits[i] holds bit i of every message (message k in bit k).  KC >= K accumulators (a power of two; the ones past K follow message "all zero" and are dropped).
+// Output row-interleaved, S_multi[row][k] (float2): a thread's two rows are 2 K consecutive float2 -- 16-byte stores when K is even.
+static_assert(NSIG_MULTI_MAX_MESSAGES == 16, "hg_codebook_presum_multi instantiates 1, 2, 4, 8 and 16 accumulators");
+template <int KC>
+__device__ __forceinline__ void presum_multi_add(float4 (&acc)[KC], const float4 t0, const float4 t1, const uint32_t w) {
+#pragma unroll
+    for (int k = 0; k < KC; ++k) {
+        const bool one = ((w >> k) & 1u) != 0u;
+        acc[k].x += one ? t1.x : t0.x; acc[k].y += one ? t1.y : t0.y; acc[k].z += one ? t1.z : t0.z; acc[k].w += one ? t1.w : t0.w;
+    }
+}
+
+template <int KC>
+__global__ void __launch_bounds__(256) k_codebook_presum_multi(PairPtrs tabs, const float *__restrict__ messages, uint32_t K, uint32_t D, float2 *__restrict__ S_multi) {
+    __shared__ uint32_t bits[NSIG_MAX_MESSAGE_DIM];
+    __shared__ const float4 *tab[2 * NSIG_MAX_MESSAGE_DIM];      // (as k_codebook_presum_sel: the pointers once per workgroup, not a kernel-argument lookup per load)
+    if (threadIdx.x < D) {
+        uint32_t w = 0;
+        for (uint32_t k = 0; k < K; ++k) w |= (messages[(size_t)k * D + threadIdx.x] != 0.0f ? 1u : 0u) << k;
+        bits[threadIdx.x] = w;
+    }
+    if (threadIdx.x < 2 * D) tab[threadIdx.x] = reinterpret_cast<const float4 *>(tabs.p[threadIdx.x]);
+    __syncthreads();
+    const uint32_t e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= NSIG_TABLE_ROWS / 2) return;
+    float4 acc[KC];
+#pragma unroll
+    for (int k = 0; k < KC; ++k) acc[k] = make_float4(0.f, 0.f, 0.f, 0.f);
+    uint32_t i = 0;
+    for (; i + 4 <= D; i += 4) {      // eight loads in flight, as the single pass has; the sums keep the table order
+        const float4 a0 = tab[2 * i][e], a1 = tab[2 * i + 1][e], b0 = tab[2 * i + 2][e], b1 = tab[2 * i + 3][e];
+        const float4 c0 = tab[2 * i + 4][e], c1 = tab[2 * i + 5][e], d0 = tab[2 * i + 6][e], d1 = tab[2 * i + 7][e];
+        presum_multi_add<KC>(acc, a0, a1, bits[i]);
+        presum_multi_add<KC>(acc, b0, b1, bits[i + 1]);
+        presum_multi_add<KC>(acc, c0, c1, bits[i + 2]);
+        presum_multi_add<KC>(acc, d0, d1, bits[i + 3]);
+    }
+    for (; i < D; ++i) presum_multi_add<KC>(acc, tab[2 * i][e], tab[2 * i + 1][e], bits[i]);
+    float2 *out = S_multi + (size_t)2 * e * K;      // rows 2 e and 2 e + 1
+    if constexpr (KC >= 2) {
+        if ((K & 1u) == 0u) {
+#pragma unroll
+            for (int k = 0; k < KC; k += 2)
+                if ((uint32_t)k < K) {
+                    *reinterpret_cast<float4 *>(out + k) = make_float4(acc[k].x, acc[k].y, acc[k + 1].x, acc[k + 1].y);
+                    *reinterpret_cast<float4 *>(out + K + k) = make_float4(acc[k].z, acc[k].w, acc[k + 1].z, acc[k + 1].w);
+                }
+            return;
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < KC; ++k)
+        if ((uint32_t)k < K) {
+            out[k] = make_float2(acc[k].x, acc[k].y);
+            out[K + k] = make_float2(acc[k].z, acc[k].w);
+        }
+}
+
 }  // namespace nsig
 
 using namespace nsig;
@@ -1143,6 +1203,27 @@ NSIG_EXPORT int hg_codebook_presum_sel(const float *const *all_tables_host, cons
     NSIG_REQUIRE(aligned16(S), "hg_codebook_presum_sel: S must be 16-byte aligned");
     k_codebook_presum_sel<<<NSIG_TABLE_ROWS / 2 / 256, 256, 0, as_stream(stream)>>>(tabs, message, D, reinterpret_cast<float4 *>(S));
     return check_launch("hg_codebook_presum_sel");
+}
+
+NSIG_EXPORT size_t hg_multi_presum_bytes(uint32_t K) { return (size_t)K * NSIG_TABLE_ROWS * sizeof(float2); }
+
+NSIG_EXPORT int hg_codebook_presum_multi(const float *const *all_tables_host, const float *messages, uint32_t K, uint32_t D, void *S_multi, nsig_stream_t stream) {
+    NSIG_REQUIRE(all_tables_host && messages && S_multi, "hg_codebook_presum_multi: null pointer");
+    NSIG_REQUIRE(K >= 1 && K <= NSIG_MULTI_MAX_MESSAGES, "hg_codebook_presum_multi: K=%u out of range [1,%d]", K, NSIG_MULTI_MAX_MESSAGES);
+    NSIG_REQUIRE(D >= 1 && D <= NSIG_MAX_MESSAGE_DIM, "hg_codebook_presum_multi: D=%u out of range [1,%d]", D, NSIG_MAX_MESSAGE_DIM);
+    PairPtrs tabs{};
+    const char *bad = "%s: table %u is null or not 16-byte aligned";
+    if (int e = take_pointers({tabs.p}, {all_tables_host}, 2 * D, "hg_codebook_presum_multi", bad, bad)) return e;
+    NSIG_REQUIRE(aligned16(S_multi), "hg_codebook_presum_multi: S_multi must be 16-byte aligned");
+    float2 *out = reinterpret_cast<float2 *>(S_multi);
+    const dim3 grid(NSIG_TABLE_ROWS / 2 / 256);
+    hipStream_t st = as_stream(stream);
+    if (K == 1) k_codebook_presum_multi<1><<<grid, 256, 0, st>>>(tabs, messages, K, D, out);
+    else if (K == 2) k_codebook_presum_multi<2><<<grid, 256, 0, st>>>(tabs, messages, K, D, out);
+    else if (K <= 4) k_codebook_presum_multi<4><<<grid, 256, 0, st>>>(tabs, messages, K, D, out);
+    else if (K <= 8) k_codebook_presum_multi<8><<<grid, 256, 0, st>>>(tabs, messages, K, D, out);
+    else k_codebook_presum_multi<16><<<grid, 256, 0, st>>>(tabs, messages, K, D, out);
+    return check_launch("hg_codebook_presum_multi");
 }
 
 static size_t binned_scratch_bytes(uint32_t M, uint32_t sets) { return (size_t)sets * (sizeof(BinHeader) + (size_t)4 * M * sizeof(uint4)); }

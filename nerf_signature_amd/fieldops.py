@@ -186,6 +186,73 @@ def field_forward(xyzs, dirs, bound, base_tables, S, packed, want_rgb=True, want
     return sigmas, rgbs, geo, masks
 
 
+MULTI_MAX_MESSAGES = 16      # include/nerfsig.h NSIG_MULTI_MAX_MESSAGES: the largest K of one multi-message launch
+
+
+def message_chunks(n, batch):
+    """[(start, stop), ...] covering range(n) in order, `batch` at a time (the last one shorter): how K messages are dealt to multi-message launches."""
+    n, batch = int(n), int(batch)
+    if n < 0 or batch < 1:
+        raise ValueError(f"message_chunks: n={n} must be >= 0 and batch={batch} >= 1")
+    return [(a, min(a + batch, n)) for a in range(0, n, batch)]
+
+
+def codebook_presum_multi(all_tables, messages_dev, out=None):
+    """The pre-sums of K messages [K, D] in one pass over the 2 D tables (hg_codebook_presum_multi), row-interleaved [T_ROWS, K, 2]: S[:, k] has the bits of
+    codebook_presum_sel(all_tables, messages_dev[k]).  out: a buffer of at least K * T_ROWS * 2 floats to write into (a view of its head is returned)."""
+    D = len(all_tables) // 2
+    if messages_dev.dtype != torch.float32 or messages_dev.dim() != 2 or messages_dev.shape[1] != D or not messages_dev.is_cuda or not messages_dev.is_contiguous():
+        raise ValueError(f"messages must be a contiguous CUDA float32 tensor [K, {D}]")
+    K = int(messages_dev.shape[0])
+    if not 1 <= K <= MULTI_MAX_MESSAGES:
+        raise ValueError(f"codebook_presum_multi: K={K} messages, one launch takes 1..{MULTI_MAX_MESSAGES} (message_chunks)")
+    if out is not None:
+        if out.dtype != torch.float32 or out.numel() < K * T_ROWS * 2 or not out.is_contiguous():
+            raise ValueError(f"codebook_presum_multi: out must be a contiguous float32 buffer of at least {K * T_ROWS * 2} elements")
+        S = out.view(-1)[:K * T_ROWS * 2].view(T_ROWS, K, 2)
+    else:
+        S = torch.empty(T_ROWS, K, 2, dtype=torch.float32, device=messages_dev.device)
+    nv.call("hg_codebook_presum_multi", nv.ptr_array([_check_table(t.detach(), "codebook table") for t in all_tables]), nv.ptr(messages_dev), K, D, nv.ptr(S), nv.stream())
+    return S
+
+
+def field_forward_multi(xyzs, dirs, bound, base_tables, S_multi, K, packed, fixed=None, planes=None):
+    """sigmas [K, M], rgbs [K, M, 3]: the field at M points under K messages in one pass (inference only) -> hg_encode_codebook_planes_multi, field_fwd_multi.
+    S_multi: codebook_presum_multi's result for the K messages.  Always through a plane set: the 16 base planes are the kept ones of `fixed` (a FixedPoints built
+    from these very points; nothing of it is written, its plane 16 and its scatter plan stay as they are), or a (buffer, layout) pair `planes` whose base levels the
+    caller encoded for these points, or one encode_planes(..., S=None) here.  Slice k has the bits of field_forward(..., S_k, planes=True)."""
+    xyzs = xyzs.contiguous().float()
+    dirs = dirs.contiguous().float()
+    M, dev = xyzs.shape[0], xyzs.device
+    K = int(K)
+    if not 1 <= K <= MULTI_MAX_MESSAGES or S_multi.numel() < K * T_ROWS * 2:
+        raise ValueError(f"field_forward_multi: K={K} out of range 1..{MULTI_MAX_MESSAGES}, or S_multi holds fewer than K pre-sums")
+    sigmas = torch.empty(K, M, dtype=torch.float32, device=dev)
+    rgbs = torch.empty(K, M, 3, dtype=torch.float32, device=dev)
+    if M == 0:
+        return sigmas, rgbs
+    if fixed is not None:
+        fixed.check(xyzs, bound, base_tables)
+        ws, layout = fixed.planes, fixed.layout
+    elif planes is not None:
+        ws, layout = planes
+    else:
+        ws, layout = encode_base_planes(xyzs, bound, base_tables)
+    cplanes = torch.empty(int(nv.fn("hg_multi_planes_bytes")(M, K)), dtype=torch.uint8, device=dev)
+    nv.call("hg_encode_codebook_planes_multi", nv.ptr(xyzs), M, float(bound), nv.ptr(S_multi), K, nv.ptr(cplanes), nv.stream())
+    nv.call("field_fwd_multi", nv.ptr(dirs), M, nv.ptr(packed), nv.ptr(ws), layout, nv.ptr(cplanes), K, nv.ptr(sigmas), nv.ptr(rgbs), nv.stream())
+    return sigmas, rgbs
+
+
+def encode_base_planes(xyzs, bound, base_tables):
+    """(plane set, layout) with the 16 base levels of `xyzs` (encode_planes with S = None): what field_forward_multi shares among chunks of messages."""
+    xyzs = xyzs.contiguous().float()
+    M = xyzs.shape[0]
+    ws = torch.empty(int(nv.fn("hg_planes_bytes")(M)), dtype=torch.uint8, device=xyzs.device)
+    base_ptrs = nv.ptr_array([_check_table(t.detach(), "base table") for t in base_tables])
+    return ws, encode_planes(xyzs, M, bound, base_ptrs, None, ws)
+
+
 def field_color(dirs, geo_feat, packed):
     dirs = dirs.contiguous().float()
     geo_feat = geo_feat.contiguous().float()

@@ -57,6 +57,7 @@ class NeRFNetwork(NeRFRenderer):
 
         self._packed_cache = None   # (key, packed weight image)
         self._presum_cache = None   # (key, S)
+        self._multi_presum = None   # forward_multi's own buffer of up to NSIG_MULTI_MAX_MESSAGES row-interleaved pre-sums (never the cache above)
         self.grad_sink = None       # optional fieldops.GradSink: backward accumulates the shared gradient there
         # shared_gradient_step (the drop-in modules switch it on): under a foreign training loop -- zero_grad / backward / GradScaler / torch.optim.Adam.step,
         # the reference Trainer's -- the D identical dense gradients are never materialised: fieldops.SharedGradient + optim.install_shared_gradient_hook
@@ -190,6 +191,46 @@ class NeRFNetwork(NeRFRenderer):
                 install_shared_gradient_hook(self._shared_sink)
             sink = self._shared_sink
         return fo.field_apply(x, d, self.bound, self._packed(), self.encoder.tables(), selected, S, sink, fixed, twin)
+
+    # ------------------------------------------------------------------ one set of points under K messages (inference)
+
+    def _check_multi_messages(self, messages, clean_twin=False):
+        super()._check_multi_messages(messages, clean_twin)
+        self._refuse_multi_when_sharded()
+
+    def _refuse_multi_when_sharded(self):
+        if _data_parallel() or self.codebook_shard is not None or getattr(self, "_codebook_stale", False):
+            raise NotImplementedError("K messages under data-parallel table sharding: this rank holds current values only for the tables of its own bits, and the "
+                                      "multi-message pre-sum reads all of them in one pass (gather the codebook and render on one rank)")
+
+    def forward_multi_chunks(self, x, d, messages, fixed=None):
+        """The field at points x under K messages [K, D] (host or device; a host tensor is copied once, nothing is read back), at most
+        fieldops.MULTI_MAX_MESSAGES per launch: yields (sigma [k, N], color [k, N, 3]) chunk by chunk, in message order.  The 16 base planes are encoded once for
+        all chunks (or are the kept ones of `fixed`, which is left untouched); per chunk one pass over the 2 D codebook tables (into a buffer of this model's own:
+        `_presum_cache` is neither used nor invalidated), one K-plane gather and one MLP launch.  Inference only."""
+        if torch.is_grad_enabled():
+            raise RuntimeError("forward_multi is inference only (forward, no gradients): call it under torch.no_grad()")
+        if not torch.is_tensor(messages) or messages.dim() != 2 or messages.shape[0] < 1 or messages.shape[1] != self.message_dim:
+            raise ValueError(f"messages must be a [K, {self.message_dim}] tensor with K >= 1")
+        self._refuse_multi_when_sharded()
+        messages = messages.detach().to(device=x.device, dtype=torch.float32).contiguous()
+        tables, base = self.msg_encoder.tables(), self.encoder.tables()
+        packed = self._packed()
+        x, d = x.contiguous().float(), d.contiguous().float()
+        planes = fo.encode_base_planes(x, self.bound, base) if fixed is None and x.shape[0] else None
+        for a, b in fo.message_chunks(messages.shape[0], fo.MULTI_MAX_MESSAGES):
+            need = (b - a) * fo.T_ROWS * 2
+            if self._multi_presum is None or self._multi_presum.numel() < need or self._multi_presum.device != x.device:
+                self._multi_presum = torch.empty(need, dtype=torch.float32, device=x.device)
+            S = fo.codebook_presum_multi(tables, messages[a:b], out=self._multi_presum)
+            yield fo.field_forward_multi(x, d, self.bound, base, S, b - a, packed, fixed=fixed, planes=planes)
+
+    def forward_multi(self, x, d, messages, fixed=None):
+        """(sigma [K, N], color [K, N, 3]) for K messages [K, D]: slice k has the bits of forward(x, d, messages[k]) through a plane set.  See forward_multi_chunks."""
+        chunks = list(self.forward_multi_chunks(x, d, messages, fixed=fixed))
+        if len(chunks) == 1:
+            return chunks[0]
+        return torch.cat([c[0] for c in chunks]), torch.cat([c[1] for c in chunks])
 
     @torch.no_grad()
     def _eval_field_rows(self, capacity, message):

@@ -19,6 +19,7 @@ import torch
 
 from . import blocks, rays, synthetic, trainer
 from .distortion import DistortionLayer
+from .fieldops import message_chunks
 from .metrics import ImageMetrics
 from .trainer import BIT_ACC, PSNRMeter
 
@@ -185,9 +186,11 @@ def trained_tensors(stage):
 
 
 @torch.no_grad()
-def test_bitacc(stage, n_messages=200, seed=4321, distortion="none"):
+def test_bitacc(stage, n_messages=200, seed=4321, distortion="none", message_batch=None):
     """Trainer.test_bitacc (utils_wtmk_disen.py:935-1030): per item a random message, eval_step(render_whole=False) on the watermark blocks
     (the model stays in whatever mode it is in -- the reference never calls model.eval() here, :951), BIT_ACC over the items.
+    message_batch: None -- one render per message, as the reference; an integer -- the same messages (same generator, same order) rendered that many at a
+    time by trainer.eval_blocks_multi (one march and base encode per batch; distortion and decoder per message in the same order): the same numbers.
     Returns (mean bit accuracy, mean wrong bits per message, worst message's wrong bits)."""
     model, D, dev = stage["model"], stage["D"], stage["device"]
     acc = BIT_ACC()
@@ -195,6 +198,14 @@ def test_bitacc(stage, n_messages=200, seed=4321, distortion="none"):
     wm = {"rays_o_block": stage["block_o"], "rays_d_block": stage["block_d"]}
     wrong = []
     layer = None if distortion in (None, "none") else DistortionLayer(distortion, seed)
+    if message_batch is not None:
+        for a, b in message_chunks(n_messages, message_batch):
+            messages = torch.stack([torch.randint(0, 2, (D,), generator=gen).float() for _ in range(a, b)]).to(dev)
+            _, decoded = trainer.eval_blocks_multi(model, wm, messages, stage["render_kwargs"], distortion=layer)
+            for k in range(b - a):
+                acc.update(decoded[k].permute(1, 0), messages[k].unsqueeze(0))
+                wrong.append(round((1.0 - acc.instant_V) * D))
+        return float(acc.measure()), float(np.mean(wrong)), int(np.max(wrong))
     for _ in range(n_messages):
         message = torch.randint(0, 2, (D,), generator=gen).float().to(dev)
         _, _, _, decoded, _, _, _ = trainer.eval_step(model, wm, message, stage["render_kwargs"], render_whole=False, distortion=layer)

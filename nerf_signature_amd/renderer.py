@@ -16,6 +16,11 @@ from . import _native as nv
 from . import raymarching
 
 
+def is_multi_message(message):
+    """A [K, D] tensor of K messages (render's multi-message form) as opposed to one message [D] or None."""
+    return torch.is_tensor(message) and message.dim() == 2
+
+
 def custom_meshgrid(*args):
     return torch.meshgrid(*args, indexing="ij")
 
@@ -388,6 +393,9 @@ class NeRFRenderer(nn.Module):
                                       "so a watermarked and a clean image would not share samples; the twin exists on the training path (model.train())")
         if clean_twin and message is None:
             raise ValueError("clean_twin needs a message: without one \"image\" is the clean image")
+        multi = is_multi_message(message)
+        if multi:
+            self._check_multi_messages(message, clean_twin)
         bg_color = self._background(bg_color)
         prefix, o, d = self._flatten_rays(rays_o, rays_d)
         plain = self.training and force_all_rays and not perturb      # (the render that march_ahead and premarch march for)
@@ -410,6 +418,12 @@ class NeRFRenderer(nn.Module):
             out = self._march_and_composite_train(o, d, message, nears, fars, dt_gamma, perturb, force_all_rays, max_steps, T_thresh, finish=bg,
                                                   marched=marched, limits=(self.aabb_train, self.min_near) if march_limits else None, clean_twin=clean_twin)
             weights_sum, depth, image = out[:3]
+            if multi:      # [K, N], [K, N], [K, N, 3]: one march, K composited images
+                K = message.shape[0]
+                if bg is None:
+                    tails = [self._finish((o.shape[0],), image[k], depth[k], weights_sum[k], bg_color, nears, fars) for k in range(K)]
+                    image, depth = torch.stack([t[0] for t in tails]), torch.stack([t[1] for t in tails])
+                return {"depth": depth.view(K, *prefix), "image": image.view(K, *prefix, 3), "weights_sum": weights_sum}
             clean = None
             if clean_twin:
                 clean = out[3][2] if bg is not None else self._finish(prefix, out[3][2], out[3][1], out[3][0], bg_color, nears, fars)[0]
@@ -451,6 +465,18 @@ class NeRFRenderer(nn.Module):
     def _field_and_composite(self, xyzs, dirs, deltas, rays, message, nears, fars, finish, T_thresh, fixed=None, clean_twin=False):
         # fixed: rays declared constant (NeRFNetwork.fix_rays) -- base planes and scatter plan are kept beside the samples
         # clean_twin: a fourth result, the (weights_sum, depth, image) of the clean field at the same samples -- the same compositing launch once more, no gradient
+        if is_multi_message(message):
+            # K messages: the field pass shares everything but the codebook level (forward_multi_chunks: base planes once, at most NSIG_MULTI_MAX_MESSAGES messages
+            # per launch); slice k then goes through the compositing launch and render tail of the single render -- stacked (weights_sum [K,N], depth [K,N], image [K,N,3])
+            outs = []
+            for sigmas, rgbs in self.forward_multi_chunks(xyzs, dirs, message, fixed=fixed):
+                for k in range(sigmas.shape[0]):
+                    s = sigmas[k] if self.density_scale == 1 else self.density_scale * sigmas[k]
+                    if finish is not None:
+                        outs.append(_CompositeFinish.apply(s, rgbs[k], deltas, rays, nears, fars, finish, T_thresh))
+                    else:
+                        outs.append(raymarching.composite_rays_train(s, rgbs[k], deltas, rays, T_thresh))
+            return tuple(torch.stack([o[i] for o in outs]) for i in range(3))
         if clean_twin:
             if fixed is not None:
                 raise NotImplementedError("clean_twin for rays declared constant (fix_rays): their kept plane set is not read by the twin launch")
@@ -668,8 +694,9 @@ class NeRFRenderer(nn.Module):
         ring of (points, rays) per call (renderer_wtmk.py:282-284) -- are reproduced from the per-ray counts."""
         B, N = rays_o.shape[:2]
         device = rays_o.device
-        depth = torch.empty((B, N), device=device)
-        image = torch.empty((B, N, 3), device=device)
+        lead = (message.shape[0],) if is_multi_message(message) else ()      # K messages: [K, B, N(, 3)], every super-chunk marched once for all of them
+        depth = torch.empty(lead + (B, N), device=device)
+        image = torch.empty(lead + (B, N, 3), device=device)
         self._keep_rays = True
         try:
             for b in range(B):
@@ -677,8 +704,8 @@ class NeRFRenderer(nn.Module):
                     tail = min(head + self.STAGED_SUPER_RAYS, N)
                     first_call = self.local_step
                     out = self.run_cuda(rays_o[b:b + 1, head:tail], rays_d[b:b + 1, head:tail], message, **kwargs)
-                    depth[b:b + 1, head:tail] = out["depth"]
-                    image[b:b + 1, head:tail] = out["image"]
+                    depth[..., b:b + 1, head:tail] = out["depth"]
+                    image[..., b:b + 1, head:tail, :] = out["image"]
                     counts = self._last_rays[:, 2].long()                                   # ray-id order
                     bounds = list(range(0, tail - head, max_ray_batch)) + [tail - head]
                     csum = torch.cat([counts.new_zeros(1), torch.cumsum(counts, 0)])
@@ -695,7 +722,33 @@ class NeRFRenderer(nn.Module):
             self._last_rays = None
         return {"depth": depth, "image": image}
 
+    def _check_multi_messages(self, messages, clean_twin=False):
+        """What a render under K messages [K, D] supports: the occupancy-grid training-mode path without gradients (what test_bitacc / test_image run)."""
+        D = getattr(self, "message_dim", None)
+        if D is not None and messages.shape[1] != D:
+            raise ValueError(f"messages are [K, {messages.shape[1]}], the network was built with message_dim={D}")
+        if not hasattr(self, "forward_multi_chunks"):
+            raise NotImplementedError("a render under K messages needs a field with forward_multi_chunks (NeRFNetwork)")
+        if not self.cuda_ray:
+            raise NotImplementedError("K messages on the uniform-sample `run` path: it re-samples depths from each field's own weights, so the messages would not "
+                                      "share samples; the multi-message render exists on the occupancy-grid path (cuda_ray=True)")
+        if not self.training:
+            raise NotImplementedError("K messages in model.eval(): the eval loop terminates rays per field (a ray leaves the alive list when ITS transmittance falls "
+                                      "under T_thresh), so the messages would not share samples; render in model.train() mode under torch.no_grad()")
+        if clean_twin:
+            raise NotImplementedError("clean_twin together with K messages: the twin launch evaluates one message and the clean field (render the clean image once, "
+                                      "with message=None)")
+        if torch.is_grad_enabled():
+            raise RuntimeError("a render under K messages is inference only (forward, no gradients): call it under torch.no_grad()")
+
     def render(self, rays_o, rays_d, message=None, staged=False, max_ray_batch=4096, **kwargs):
+        """message: None, one message [D], or K messages [K, D] (K >= 1; training-mode kernels under torch.no_grad()): one march and one base-level encode for all K,
+        the codebook level and the MLP chain per message -> image [K, *prefix, 3], depth [K, *prefix] (unstaged also weights_sum [K, N]); image[k] has the bits of
+        render(..., message[k])."""
+        if is_multi_message(message):
+            if not self.cuda_ray or kwargs.get("clean_twin"):      # (what run_cuda -- which checks every call it gets -- would not see, or not see first)
+                self._check_multi_messages(message, kwargs.get("clean_twin", False))
+            message = message.detach().to(device=rays_o.device, dtype=torch.float32).contiguous()      # (a host tensor: copied once, here; nothing is read back)
         if kwargs.get("clean_twin") and (staged or not self.cuda_ray):
             raise NotImplementedError("clean_twin exists on the unstaged occupancy-grid training path only (cuda_ray=True, staged=False): the uniform-sample path "
                                       "re-samples depths from the field's own weights, so the two images would not share samples, and a staged render assembles "
@@ -708,15 +761,16 @@ class NeRFRenderer(nn.Module):
                 and os.environ.get("NERFSIG_STAGED_FUSED", "1") != "0"):
             return self._render_staged_fused(rays_o, rays_d, message, max_ray_batch, **kwargs)
         if staged:
-            depth = torch.empty((B, N), device=device)
-            image = torch.empty((B, N, 3), device=device)
+            lead = (message.shape[0],) if is_multi_message(message) else ()
+            depth = torch.empty(lead + (B, N), device=device)
+            image = torch.empty(lead + (B, N, 3), device=device)
             for b in range(B):
                 head = 0
                 while head < N:
                     tail = min(head + max_ray_batch, N)
                     results_ = _run(rays_o[b:b + 1, head:tail], rays_d[b:b + 1, head:tail], message, **kwargs)
-                    depth[b:b + 1, head:tail] = results_["depth"]
-                    image[b:b + 1, head:tail] = results_["image"]
+                    depth[..., b:b + 1, head:tail] = results_["depth"]
+                    image[..., b:b + 1, head:tail, :] = results_["image"]
                     head += max_ray_batch
             results = {"depth": depth, "image": image}
         else:

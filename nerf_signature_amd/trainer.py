@@ -373,6 +373,26 @@ def eval_step(model, data, message, render_kwargs, render_whole=True, lambda_w=1
     return pred_rgb, pred_depth, gt_rgb, decoded, lossi, lossw, loss
 
 
+@torch.no_grad()
+def eval_blocks_multi(model, data, messages, render_kwargs, distortion=None):
+    """eval_step(render_whole=False) under K messages [K, D] with ONE multi-message render of the watermark blocks (NeRFRenderer.render with a 2-D message: one
+    march and one base-level encode for all K); the distortion layer and the decoder then run per message, in message order -- the decoder's BatchNorm takes its
+    batch statistics over one message's D blocks, so messages never share a decoder batch, and the distortion layer draws once per message as eval_step does.
+    Returns (pred_rgb [K, D, bh, bw, 3], decoded [K, D, 1]): slice k is what eval_step returns for messages[k] when the K calls are made in this order."""
+    out = model.render(data["rays_o_block"], data["rays_d_block"], messages, staged=False, bg_color=1, perturb=False, force_all_rays=True, **dict(render_kwargs))
+    pred_rgb = torch.clamp(out["image"], min=0, max=1)
+    if isinstance(distortion, str):
+        distortion = DistortionLayer(distortion) if distortion != "none" else None
+    decoded = []
+    for k in range(pred_rgb.shape[0]):
+        rgb = pred_rgb[k]
+        if distortion is not None:
+            distortion.draw(tuple(rgb.shape), rgb.device)
+            rgb = distortion(rgb)
+        decoded.append(model.msg_decoder(model.normalization(rgb.permute(0, 3, 1, 2))))
+    return pred_rgb, torch.stack(decoded)
+
+
 def test_step(model, data, message, render_kwargs, bg_color=None, perturb=False):
     """Trainer.test_step (utils_wtmk_disen.py:704-722): a staged full-view render, clamped.  Returns (pred_rgb [B,H,W,3], pred_depth [B,H,W])."""
     H, W = data["H"], data["W"]
