@@ -5,6 +5,7 @@ how to build it, and every call checks its return code and raises with nsig_last
 """
 import ctypes
 import os
+import re
 
 import torch
 
@@ -14,147 +15,52 @@ LIB_PATH = os.path.join(_PKG, "lib", "libnerfsig.so")
 _c = ctypes
 _vp, _u32, _fl, _int, _sz = _c.c_void_p, _c.c_uint32, _c.c_float, _c.c_int, _c.c_size_t
 
-# name -> argtypes (restype is int unless listed in _RESTYPES); mirrors include/nerfsig.h one to one.
-SIGNATURES = {
-    "nsig_abi_version": [],
-    "nsig_last_error": [],
-    "nsig_host_device_pointer": [_vp],
-    "rg_sample_rays": [_vp, _u32, _vp, _fl, _fl, _fl, _fl, _u32, _u32, _u32, _vp, _u32, _u32, _c.c_uint64, _vp, _vp, _vp, _vp, _vp, _vp],
-    "rg_sample_rays_orbit": [_fl, _fl, _fl, _fl, _u32, _u32, _u32, _vp, _u32, _u32, _c.c_uint64, _fl, _fl, _fl, _fl, _fl, _vp, _vp, _vp, _vp, _vp],
-    "rg_sample_rays_weighted": [_vp, _u32, _vp, _fl, _fl, _fl, _fl, _u32, _u32, _u32, _vp, _u32, _u32, _c.c_uint64, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
-    "rg_blend_random_background": [_vp, _u32, _vp, _c.c_uint64, _vp, _vp, _vp],
-    "rg_sample_rays_rgba": [_vp, _u32, _vp, _fl, _fl, _fl, _fl, _u32, _u32, _u32, _vp, _u32, _u32, _c.c_uint64, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
-    "rg_sample_rays_weighted_rgba": [_vp, _u32, _vp, _fl, _fl, _fl, _fl, _u32, _u32, _u32, _vp, _u32, _u32, _c.c_uint64, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
-    "rg_error_map_update": [_vp, _u32, _u32, _vp, _vp, _vp, _vp, _u32, _vp],
-    "rg_get_rays": [_vp, _fl, _fl, _fl, _fl, _u32, _u32, _vp, _u32, _u32, _vp, _vp, _vp],
-    "rm_near_far_from_aabb": [_vp, _vp, _vp, _u32, _fl, _vp, _vp, _vp],
-    "rm_sph_from_ray": [_vp, _vp, _fl, _u32, _vp, _vp],
-    "rm_morton3D": [_vp, _u32, _vp, _vp],
-    "rm_morton3D_invert": [_vp, _u32, _vp, _vp],
-    "rm_packbits": [_vp, _u32, _fl, _vp, _vp],
-    "rg_refresh_draw_scratch_bytes": [_u32, _u32],
-    "rg_refresh_begin": [_vp, _u32, _vp],
-    "rg_refresh_draw": [_vp, _vp, _u32, _u32, _vp, _vp, _c.c_uint64, _vp, _u32, _vp],
-    "rg_refresh_points": [_vp, _vp, _u32, _u32, _fl, _fl, _c.c_uint64, _vp, _u32, _vp, _vp, _vp],
-    "rg_refresh_scatter": [_vp, _vp, _u32, _fl, _vp, _vp],
-    "rg_refresh_partials_bytes": [_u32],
-    "rg_refresh_finish": [_vp, _vp, _u32, _fl, _vp, _fl, _vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp],
-    "rm_march_train_scratch_bytes": [_u32, _u32],
-    "rm_march_train_count": [_vp, _vp, _vp, _fl, _fl, _u32, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _vp, _vp],
-    "rm_march_train_scan": [_vp, _u32, _vp, _vp, _vp],
-    "rm_march_train_scan_blocks": [_u32],
-    "rm_march_train_scan_wide": [_vp, _u32, _vp, _vp, _vp, _vp],
-    "rm_march_train_write": [_vp, _vp, _fl, _fl, _u32, _u32, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
-    "rm_march_train_count_nf": [_vp, _vp, _vp, _fl, _vp, _fl, _fl, _u32, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _vp, _vp],
-    "rm_march_train_scan_write_max_rays": [],
-    "rm_march_train_scan_write": [_vp, _vp, _fl, _fl, _u32, _u32, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
-    "rm_composite_train_fwd": [_vp, _vp, _vp, _vp, _u32, _u32, _fl, _vp, _vp, _vp, _vp],
-    "rm_composite_train_bwd": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _u32, _fl, _vp, _vp, _vp],
-    "rm_march": [_u32, _u32, _vp, _vp, _vp, _vp, _fl, _fl, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp],
-    "rm_composite": [_u32, _u32, _fl, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
-    "rm_compact_alive": [_vp, _u32, _vp, _vp, _vp],
-    "rm_eval_begin": [_u32, _vp, _vp, _vp],
-    "rm_eval_march": [_vp, _u32, _vp, _vp, _vp, _vp, _fl, _fl, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
-    "rm_eval_composite": [_vp, _u32, _fl, _fl, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
-    "rm_eval_compact": [_vp, _u32, _u32, _vp, _vp, _vp],
-    "hg_encode_planes_rows": [_vp, _u32, _vp, _fl, _vp, _vp, _vp, _vp],
-    "hg_encode_planes_mixed": [_vp, _u32, _vp, _fl, _vp, _vp, _vp, _vp],
-    "field_fwd_rows": [_vp, _vp, _u32, _vp, _fl, _vp, _vp, _vp, _vp, _vp, _vp, _int, _vp],
-    "hg_codebook_presum": [_vp, _u32, _vp, _vp],
-    "hg_codebook_presum_sel": [_vp, _vp, _u32, _vp, _vp],
-    "hg_encode_fwd": [_vp, _u32, _vp, _vp, _vp, _vp],
-    "hg_codebook_encode_fwd": [_vp, _u32, _vp, _u32, _vp, _vp],
-    "hg_codebook_bwd": [_vp, _u32, _vp, _vp, _vp],
-    "hg_scatter_sliced": [_vp, _u32, _vp, _vp],
-    "hg_fanout_grad": [_vp, _vp, _u32, _int, _vp],
-    "hg_level_lookup": [_vp, _u32, _fl, _vp, _vp, _vp],
-    "opt_codebook_adam": [_vp, _vp, _vp, _vp, _u32, _fl, _fl, _fl, _vp, _vp, _fl, _vp],
-    "opt_codebook_adam_sel": [_vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp, _fl, _fl, _fl, _fl, _vp, _vp],
-    "opt_codebook_adam_sel_next": [_vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp, _fl, _fl, _fl, _fl, _vp, _vp, _vp, _vp],
-    "mlp_packed_bytes": [],
-    "mlp_get_precision": [],
-    "mlp_set_precision": [_int],
-    "mlp_get_pipelined": [],
-    "mlp_set_pipelined": [_int],
-    "mlp_pack_weights": [_vp, _vp, _vp, _vp],
-    "hg_planes_bytes": [_u32],
-    "hg_encode_planes": [_vp, _u32, _fl, _vp, _vp, _vp, _vp],
-    "hg_warm_tables": [_vp, _vp, _vp, _vp],
-    "hg_encode_codebook_plane": [_vp, _u32, _fl, _vp, _vp, _int, _vp, _vp],
-    "field_fwd": [_vp, _vp, _u32, _fl, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _int, _vp],
-    "field_fwd_twin": [_vp, _vp, _u32, _fl, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _int, _vp, _vp, _vp],
-    "hg_multi_presum_bytes": [_u32],
-    "hg_codebook_presum_multi": [_vp, _vp, _u32, _u32, _vp, _vp],
-    "hg_multi_planes_bytes": [_u32, _u32],
-    "hg_encode_codebook_planes_multi": [_vp, _u32, _fl, _vp, _u32, _vp, _vp],
-    "field_fwd_multi": [_vp, _u32, _vp, _vp, _int, _vp, _u32, _vp, _vp, _vp],
-    "field_color_fwd": [_vp, _vp, _u32, _vp, _vp, _vp],
-    "opt_adam_dense_host": [_u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _fl, _fl, _fl, _fl, _vp],
-    "opt_adam_dense": [_u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _fl, _fl, _fl, _fl, _vp, _vp],
-    "rm_composite_train_finish_fwd": [_vp, _vp, _vp, _vp, _u32, _u32, _fl, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp],
-    "rm_composite_train_finish_bwd": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _u32, _u32, _fl, _u32, _vp, _vp, _vp],
-    "rm_finish_fwd": [_vp, _vp, _vp, _vp, _vp, _vp, _u32, _u32, _vp, _vp, _vp],
-    "rm_finish_bwd": [_vp, _vp, _vp, _vp, _vp, _vp, _u32, _u32, _vp, _vp, _vp],
-    "loop_step_begin": [_vp, _u32, _vp, _u32, _u32, _vp, _vp, _vp],
-    "wm_loss_fwd": [_vp, _vp, _u32, _vp, _vp, _u32, _fl, _fl, _fl, _vp, _vp, _vp, _vp],
-    "wm_loss_bwd": [_vp, _vp, _vp, _fl, _fl, _vp, _u32, _vp, _u32, _vp, _vp, _vp],
-    "dec_bn_gelu_fwd": [_vp, _vp, _vp, _u32, _u32, _u32, _fl, _vp, _vp, _vp],
-    "dec_bn_gelu_bwd": [_vp, _vp, _vp, _vp, _vp, _u32, _u32, _u32, _vp, _vp, _vp, _vp],
-    "dec_workspace_bytes": [_u32, _u32, _u32, _u32],
-    "dec_forward": [_vp, _u32, _vp, _vp, _vp, _u32, _u32, _u32, _u32, _fl, _vp, _vp, _vp, _vp],
-    "dec_backward": [_vp, _vp, _u32, _vp, _vp, _vp, _u32, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _vp],
-    "dec_forward_train": [_vp, _vp, _vp, _vp, _u32, _u32, _u32, _u32, _fl, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _fl, _fl, _vp, _vp],
-    "dec_backward_train": [_vp, _vp, _vp, _vp, _vp, _u32, _u32, _u32, _u32, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp],
-    "wm_distort_draw": [_u32, _c.c_uint64, _vp, _u32, _vp, _vp, _vp],
-    "wm_distort_fwd": [_vp, _u32, _u32, _u32, _u32, _u32, _vp, _vp, _vp, _vp],
-    "wm_distort_bwd": [_vp, _vp, _u32, _u32, _u32, _u32, _u32, _vp, _vp, _vp, _vp],
-    "wm_distort_geom_fwd": [_vp, _u32, _u32, _u32, _u32, _u32, _vp, _u32, _vp, _vp, _vp],
-    "wm_distort_geom_bwd": [_vp, _vp, _u32, _u32, _u32, _u32, _u32, _vp, _u32, _vp, _vp],
-    "field_fwd_trace": [_vp, _vp, _u32, _fl, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
-    "field_bwd_trace": [_u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
-    "hg_scatter_level": [_vp, _fl, _vp, _u32, _u32, _vp, _vp],
-    "hg_scatter_binned_scratch_bytes": [_u32],
-    "hg_scatter_binned": [_vp, _u32, _vp, _vp, _vp],
-    "hg_scatter_levels_scratch_bytes": [_u32],
-    "hg_scatter_levels": [_vp, _fl, _vp, _u32, _u32, _vp, _vp, _vp],
-    "field_bwd": [_vp, _u32, _fl, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
-    "field_bwd_planned": [_vp, _u32, _fl, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
-    "hg_scatter_plan_bytes": [_u32],
-    "hg_scatter_plan": [_vp, _u32, _fl, _vp, _vp],
-    "hg_scatter_planned": [_vp, _u32, _vp, _vp],
-    "field_fwd_trace_rows": [_vp, _vp, _u32, _vp, _fl, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
-    "field_fwd_trace_f16": [_vp, _vp, _u32, _vp, _fl, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
-    "field_bwd_trace_rows": [_u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
-    "field_wgrad_scratch_bytes": [_u32],
-    "field_wgrad": [_u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
-    "field_bwd_wgrad_scratch_bytes": [_u32],
-    "field_bwd_wgrad": [_u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
-    "field_bwd_wgrad_f16": [_u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
-    "rm_composite_train_mse": [_vp, _vp, _vp, _vp, _u32, _u32, _fl, _vp, _vp, _vp, _u32, _vp, _u32, _fl, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
-    "opt_ema_update": [_u32, _vp, _vp, _vp, _vp, _c.c_double, _vp],
-    "clean_loss": [_vp, _vp, _u32, _fl, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp, _u32, _c.c_uint64, _vp],
-    "hg_levels_plan_bytes": [_u32],
-    "hg_levels_plan": [_vp, _u32, _vp, _fl, _vp, _vp],
-    "hg_levels_scatter": [_vp, _u32, _vp, _fl, _vp, _u32, _vp, _vp, _vp],
-    "hg_levels_scatter_adam": [_vp, _u32, _vp, _fl, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _fl, _fl, _fl, _fl, _vp, _vp],
-    "mc_scratch_bytes": [_u32, _u32, _u32],
-    "mc_count": [_vp, _u32, _u32, _u32, _fl, _vp, _vp, _vp],
-    "mc_emit": [_vp, _u32, _u32, _u32, _fl, _vp, _u32, _u32, _vp, _vp, _vp],
-    "mc_vertex_normals": [_vp, _u32, _u32, _u32, _fl, _vp, _u32, _fl, _fl, _fl, _vp, _vp, _vp],
-    "mesh_components_scratch_bytes": [_u32, _u32],
-    "mesh_components": [_vp, _u32, _u32, _vp, _vp, _vp],
-    "im_range_scratch_bytes": [_u32, _c.c_uint64],
-    "im_range_sse": [_vp, _vp, _u32, _c.c_uint64, _vp, _vp, _vp, _vp],
-    "im_ssim_scratch_bytes": [_u32, _u32, _u32, _u32],
-    "im_ssim": [_vp, _vp, _u32, _u32, _u32, _u32, _vp, _fl, _vp, _vp, _vp, _vp],
-}
-_RESTYPES = {"nsig_last_error": _c.c_char_p, "nsig_host_device_pointer": _c.c_void_p, "rm_march_train_scratch_bytes": _sz, "mlp_packed_bytes": _sz, "hg_planes_bytes": _sz, "hg_multi_presum_bytes": _sz, "hg_multi_planes_bytes": _sz, "dec_workspace_bytes": _sz, "hg_scatter_levels_scratch_bytes": _sz, "hg_scatter_binned_scratch_bytes": _sz, "hg_scatter_plan_bytes": _sz, "field_wgrad_scratch_bytes": _sz, "field_bwd_wgrad_scratch_bytes": _sz, "hg_levels_plan_bytes": _sz, "rg_refresh_partials_bytes": _sz, "rg_refresh_draw_scratch_bytes": _sz, "mc_scratch_bytes": _sz, "mesh_components_scratch_bytes": _sz, "im_range_scratch_bytes": _sz, "im_ssim_scratch_bytes": _sz}
-
-_lib = None
-
 
 class NativeError(RuntimeError):
     pass
+
+
+# The header is the one written record of the ABI: argument and return types are read from its declarations, as the compiler reads them for csrc/*.hip.
+HEADER_PATH = os.path.join(_PKG, "..", "include", "nerfsig.h")
+_PARAM_TYPES = {"nsig_stream_t": _vp, "uint32_t": _u32, "int32_t": _c.c_int32, "uint64_t": _c.c_uint64, "int": _int, "float": _fl, "double": _c.c_double, "size_t": _sz}
+_RETURN_TYPES = {"int": _int, "size_t": _sz, "const char *": _c.c_char_p, "void *": _vp}
+_DECLARATION = re.compile(r"^(int|size_t|const char \*|void \*)\s*(\w+)\s*\(([^()]*)\)\s*;", re.M)
+
+
+def parse_header(text):
+    """{name: (restype, argtypes)} of every `<ret> name(<params>);` in a header's text.  A parameter with a `*` and nsig_stream_t are pointers, the scalar types map by
+    name, `(void)` is no arguments; anything else -- and any other text with a parenthesis in it -- raises NativeError naming the declaration: nothing is guessed."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", "", text, flags=re.S)
+    text = re.sub(r"^[ \t]*#.*$", "", text, flags=re.M)
+    found = {}
+    for ret, name, params in _DECLARATION.findall(text):
+        argtypes = []
+        for p in ([] if params.strip() == "void" else params.split(",")):
+            words = [w for w in p.split() if w != "const"]
+            t = _vp if "*" in p else _PARAM_TYPES.get(words[0] if words else "")
+            if t is None:
+                raise NativeError(f"{name}({' '.join(params.split())}): no ctypes type for the parameter '{p.strip()}'")
+            argtypes.append(t)
+        found[name] = (_RETURN_TYPES[ret], argtypes)
+    stray = [line.strip() for line in _DECLARATION.sub("", text).splitlines() if "(" in line]
+    if stray:
+        raise NativeError(f"cannot read the declaration '{stray[0]}'")
+    return found
+
+
+def _read_header(path):
+    try:
+        with open(path) as f:
+            return parse_header(f.read())
+    except (OSError, NativeError) as e:
+        raise NativeError(f"{path}: {e} (the ctypes signatures of libnerfsig.so are derived from this header; there is no second table)") from e
+
+
+_DECLARED = _read_header(HEADER_PATH)
+SIGNATURES = {name: argtypes for name, (_, argtypes) in _DECLARED.items()}      # name -> argtypes
+_RESTYPES = {name: restype for name, (restype, _) in _DECLARED.items()}
+
+_lib = None
 
 
 def load():
@@ -184,7 +90,7 @@ def fn(name):
         except AttributeError as e:
             raise NativeError(f"libnerfsig.so does not export {name}; rebuild with `python -m nerf_signature_amd.build --force`") from e
         f.argtypes = SIGNATURES[name]
-        f.restype = _RESTYPES.get(name, _int)
+        f.restype = _RESTYPES[name]
         _bound[name] = f
     return f
 

@@ -5,6 +5,9 @@
 #include <stdint.h>
 #include <stdio.h>
 
+#include <atomic>
+#include <mutex>
+
 #include "../../include/nerfsig.h"
 
 #define NSIG_EXPORT extern "C" __attribute__((visibility("default")))
@@ -28,7 +31,26 @@ inline hipStream_t as_stream(nsig_stream_t s) { return reinterpret_cast<hipStrea
         }                                 \
     } while (0)
 
-inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+__host__ __device__ inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+__host__ __device__ inline bool aligned8(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 7) == 0; }
+__host__ __device__ inline bool aligned4(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 3) == 0; }
+
+// A launch with more than 64 KB of dynamic LDS has to be allowed per kernel first.  `granted` is the call site's own record (a static std::atomic<size_t>, zero at
+// start) of what `kernel` has been allowed so far; the attribute is set only when `bytes` exceeds it.  The entry points are reached from more than one thread
+// (forward, autograd's backward): the record is read without a lock, and raised under one, so a kernel's limit never goes down.
+template <typename K>
+int reserve_lds(K kernel, size_t bytes, std::atomic<size_t> &granted, const char *who) {
+    if (bytes <= granted.load(std::memory_order_acquire)) return NSIG_OK;
+    static std::mutex raising;
+    std::lock_guard<std::mutex> lock(raising);
+    if (bytes <= granted.load(std::memory_order_relaxed)) return NSIG_OK;
+    if (hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) != hipSuccess) {
+        set_error("%s: cannot reserve %zu bytes of LDS", who, bytes);
+        return NSIG_ERR_LAUNCH;
+    }
+    granted.store(bytes, std::memory_order_release);
+    return NSIG_OK;
+}
 
 // Element i < n of K parallel host lists of device pointers into K arrays of a launch's argument struct, index by index: a null one is refused with null_fmt, one of
 // the first `aligned` lists that is not 16-byte aligned with align_fmt (printf formats taking who and i).

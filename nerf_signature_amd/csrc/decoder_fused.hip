@@ -1436,19 +1436,12 @@ static int load_params(const float *const *params, DecParams &p) {
     return !(p.lin_w && p.lin_b);
 }
 
-// Dynamic LDS above 64 KB has to be allowed per kernel; remembered per kernel so the attribute call happens once per size.
-template <typename K>
-static int allow_lds(K kernel, size_t bytes, size_t &allowed) {
-    if (bytes <= allowed) return 0;
-    if (hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) != hipSuccess) return 1;
-    allowed = bytes;
-    return 0;
-}
-static int allow_all_lds(const DecGeom &g) {
-    static size_t a[6] = {0, 0, 0, 0, 0, 0};
-    return allow_lds(k_dec_conv<kFwd, 512>, conv_lds(g), a[0]) | allow_lds(k_dec_conv<kDgrad, 512>, conv_lds(g), a[1]) |
-           allow_lds(k_dec_conv<kDgradImg, 512>, conv_lds(g), a[2]) | allow_lds(k_dec_l8_fwd, l8_lds(g), a[3]) |
-           allow_lds(k_dec_l8_bwd, l8b_lds(g), a[4]) | allow_lds(k_dec_wgrad, wgrad_lds(g), a[5]);
+// Every kernel's dynamic LDS for this geometry (the sizes grow with the image: remembered per kernel, so the attribute call happens once per size).
+static int allow_all_lds(const DecGeom &g, const char *who) {
+    static std::atomic<size_t> a[6];
+    return reserve_lds(k_dec_conv<kFwd, 512>, conv_lds(g), a[0], who) | reserve_lds(k_dec_conv<kDgrad, 512>, conv_lds(g), a[1], who) |
+           reserve_lds(k_dec_conv<kDgradImg, 512>, conv_lds(g), a[2], who) | reserve_lds(k_dec_l8_fwd, l8_lds(g), a[3], who) |
+           reserve_lds(k_dec_l8_bwd, l8b_lds(g), a[4], who) | reserve_lds(k_dec_wgrad, wgrad_lds(g), a[5], who);
 }
 
 // Threads per conv workgroup: 512 = four MFMA waves + four helper waves for the request / statistics / prologue phases.
@@ -1689,7 +1682,7 @@ static int dec_forward_impl(const float *img, uint32_t input_mode, const float *
                  "dec_forward: unsupported image shape %ux%ux%ux%u (see dec_workspace_bytes)", B, Cin, H, W);
     DecParams prm;
     NSIG_REQUIRE(load_params(params, prm) == 0, "dec_forward: params must hold 29 device pointers");
-    NSIG_REQUIRE(allow_all_lds(g) == 0, "dec_forward: could not raise the dynamic LDS limit");
+    NSIG_REQUIRE(allow_all_lds(g, "dec_forward") == 0, "dec_forward: could not raise the dynamic LDS limit");
     DecWs ws;
     carve(workspace, g, ws);
     hipStream_t s = as_stream(stream);
@@ -1744,7 +1737,7 @@ static int dec_backward_impl(const float *grad_decoded, const float *img, uint32
     gr.lin_w = grads[27];
     gr.lin_b = grads[28];
     NSIG_REQUIRE(gr.lin_w && gr.lin_b, "dec_backward: grads must hold 29 device pointers");
-    NSIG_REQUIRE(allow_all_lds(g) == 0, "dec_backward: could not raise the dynamic LDS limit");
+    NSIG_REQUIRE(allow_all_lds(g, "dec_backward") == 0, "dec_backward: could not raise the dynamic LDS limit");
     DecWs ws;
     carve(workspace, g, ws);
     hipStream_t s = as_stream(stream);

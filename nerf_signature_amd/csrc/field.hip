@@ -28,6 +28,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <mutex>
+#include <type_traits>
 #include <unordered_set>
 #include "fieldmlp.h"
 #include "wave.h"
@@ -1028,6 +1029,18 @@ static int mlp_precision() {
     return g_mlp_precision;
 }
 NSIG_EXPORT int mlp_get_precision(void) { return mlp_precision(); }
+// launch(F16{}) or launch(Bf16x3{}), as selected: a launch of a kernel template over the MLP arithmetic is written once, as a generic lambda (`using P = decltype(tag)`).
+template <typename Launch>
+static void with_mlp(Launch launch) {
+    if (mlp_precision() == 1) launch(F16{});
+    else launch(Bf16x3{});
+}
+// launch(std::true_type{}) or launch(std::false_type{}): the same for a launch that differs in one bool template argument (`decltype(flag)::value`).
+template <typename Launch>
+static void with_flag(bool flag, Launch launch) {
+    if (flag) launch(std::true_type{});
+    else launch(std::false_type{});
+}
 NSIG_EXPORT int mlp_set_precision(int mode) {
     NSIG_REQUIRE(mode == 0 || mode == 1, "mlp_set_precision: 0 (bf16x3) or 1 (f16)");
     g_mlp_precision = mode;
@@ -1036,7 +1049,7 @@ NSIG_EXPORT int mlp_set_precision(int mode) {
 
 NSIG_EXPORT int mlp_pack_weights(const float *sigma_params, const float *color_params, void *packed, nsig_stream_t stream) {
     NSIG_REQUIRE(sigma_params && color_params && packed, "mlp_pack_weights: null pointer");
-    NSIG_REQUIRE((reinterpret_cast<uintptr_t>(packed) & 15) == 0, "mlp_pack_weights: packed must be 16-byte aligned");
+    NSIG_REQUIRE(aligned16(packed), "mlp_pack_weights: packed must be 16-byte aligned");
     const int total = (kFwdFrags + kBwdFrags) * 512;
     k_pack_weights<<<ceil_div(total, 256), 256, 0, as_stream(stream)>>>(sigma_params, color_params, reinterpret_cast<__bf16 *>(packed));
     return check_launch("mlp_pack_weights");
@@ -1064,15 +1077,6 @@ static uint32_t field_grid(uint32_t M, bool forward = false, uint32_t per_cu = 0
     // the forward with 512 or 1024 (117-120 us against 124-125 with 768) and the step with 1024 (1.118-1.123 ms against 1.132-1.133).
     const uint32_t cap = (uint32_t)kCUs * (per_cu ? per_cu : (forward ? 4u : 3u));
     return blocks < cap ? blocks : cap;
-}
-
-static int fill_base_tables(const float *const *host, TablePtrs &base, const char *who) {
-    NSIG_REQUIRE(host, "%s: null base table list", who);
-    for (int l = 0; l < NSIG_BASE_LEVELS; ++l) {
-        NSIG_REQUIRE(host[l] != nullptr, "%s: base table %d is null", who, l);
-        base.p[l] = host[l];
-    }
-    return NSIG_OK;
 }
 
 // Level -> XCD-slot assignment of k_encode_planes: the six finest levels each get a slot of their own or share it only with coarse
@@ -1113,7 +1117,7 @@ static int encode_planes_impl(const float *xyzs, uint32_t M, float bound, const 
     if (M == 0) return NSIG_OK;
     NSIG_REQUIRE(xyzs && planes, "hg_encode_planes: null pointer");
     NSIG_REQUIRE(bound > 0.0f, "hg_encode_planes: bound must be positive");
-    NSIG_REQUIRE((reinterpret_cast<uintptr_t>(planes) & 7) == 0, "hg_encode_planes: planes must be 8-byte aligned");
+    NSIG_REQUIRE(aligned8(planes), "hg_encode_planes: planes must be 8-byte aligned");
     TablePtrs base{};
     if (int e = fill_base_tables(base_tables_host, base, "hg_encode_planes")) return e;
     const uint32_t stride = ceil_div(M, 32u) * 32u;
@@ -1128,8 +1132,9 @@ static int encode_planes_impl(const float *xyzs, uint32_t M, float bound, const 
     // tiles per XCD slot handled by distinct workgroups before they start looping: with one tile per workgroup (cap >= tiles) the block
     // render's launch takes 244-247 us against 258-261 us with 1024 looping workgroups per slot (same-box sweep, profiles/r01_k_encoder_grid_sweep.txt)
     const uint32_t per_slot = tiles < 8192u ? tiles : 8192u;
-    if (mixed) k_encode_planes<true><<<per_slot * 8, 256, 0, as_stream(stream)>>>(xyzs, M, bound, base, make_level_geom(), S, reinterpret_cast<float2 *>(planes), stride, tab, rows_dev);
-    else k_encode_planes<false><<<per_slot * 8, 256, 0, as_stream(stream)>>>(xyzs, M, bound, base, make_level_geom(), S, reinterpret_cast<float2 *>(planes), stride, tab, rows_dev);
+    with_flag(mixed, [&](auto kMixed) {
+        k_encode_planes<decltype(kMixed)::value><<<per_slot * 8, 256, 0, as_stream(stream)>>>(xyzs, M, bound, base, make_level_geom(), S, reinterpret_cast<float2 *>(planes), stride, tab, rows_dev);
+    });
     return check_launch("hg_encode_planes");
 }
 
@@ -1156,8 +1161,8 @@ NSIG_EXPORT int hg_encode_codebook_plane(const float *xyzs, uint32_t M, float bo
     if (int e = check_layout(planes_layout, "hg_encode_codebook_plane")) return e;
     NSIG_REQUIRE(xyzs && S && planes, "hg_encode_codebook_plane: null pointer");
     NSIG_REQUIRE(bound > 0.0f, "hg_encode_codebook_plane: bound must be positive");
-    NSIG_REQUIRE((reinterpret_cast<uintptr_t>(planes) & 7) == 0, "hg_encode_codebook_plane: planes must be 8-byte aligned");
-    NSIG_REQUIRE(plan_to_reset == nullptr || (reinterpret_cast<uintptr_t>(plan_to_reset) & 15) == 0, "hg_encode_codebook_plane: plan must be 16-byte aligned");
+    NSIG_REQUIRE(aligned8(planes), "hg_encode_codebook_plane: planes must be 8-byte aligned");
+    NSIG_REQUIRE(plan_to_reset == nullptr || aligned16(plan_to_reset), "hg_encode_codebook_plane: plan must be 16-byte aligned");
     const uint32_t stride = ceil_div(M, 32u) * 32u;
     float2 *plane = planes_layout == NSIG_PLANES_MIXED ? mixed_f32_plane(planes, stride, NSIG_BASE_LEVELS) : reinterpret_cast<float2 *>(planes) + (size_t)NSIG_BASE_LEVELS * stride;
     k_encode_codebook_plane<<<ceil_div(stride, 256u), 256, 0, as_stream(stream)>>>(xyzs, M, bound, make_level_geom().cell[NSIG_BASE_LEVELS], S, plane, stride,
@@ -1173,18 +1178,20 @@ static int field_fwd_impl(const float *xyzs, const float *dirs, uint32_t M, floa
     NSIG_REQUIRE(xyzs && packed && sigmas, "field_fwd: null pointer");
     NSIG_REQUIRE(rgbs == nullptr || dirs != nullptr, "field_fwd: dirs is required when rgbs is requested");
     NSIG_REQUIRE(bound > 0.0f, "field_fwd: bound must be positive");
-    NSIG_REQUIRE((reinterpret_cast<uintptr_t>(packed) & 15) == 0, "field_fwd: packed must be 16-byte aligned");
+    NSIG_REQUIRE(aligned16(packed), "field_fwd: packed must be 16-byte aligned");
     TablePtrs base{};
     if (int e = fill_base_tables(base_tables_host, base, "field_fwd")) return e;
     const char *pk = reinterpret_cast<const char *>(packed);
     hipStream_t st = as_stream(stream);
     const bool f16 = mlp_precision() == 1;
     if (planes == nullptr) {  // fused: gather inside the MLP kernel (small batches)
-        if (f16) k_field_fwd<F16, 0><<<field_grid(M, true), 256, F16::kFwdLds, st>>>(xyzs, dirs, M, bound, base, make_level_geom(), S, nullptr, 0, pk, sigmas, rgbs, geo_feat, masks, ActTrace{}, rows_dev);
-        else k_field_fwd<Bf16x3, 0><<<field_grid(M, true), 256, Bf16x3::kFwdLds, st>>>(xyzs, dirs, M, bound, base, make_level_geom(), S, nullptr, 0, pk, sigmas, rgbs, geo_feat, masks, ActTrace{}, rows_dev);
+        with_mlp([&](auto tag) {
+            using P = decltype(tag);
+            k_field_fwd<P, 0><<<field_grid(M, true), 256, P::kFwdLds, st>>>(xyzs, dirs, M, bound, base, make_level_geom(), S, nullptr, 0, pk, sigmas, rgbs, geo_feat, masks, ActTrace{}, rows_dev);
+        });
         return check_launch("field_fwd");
     }
-    NSIG_REQUIRE((reinterpret_cast<uintptr_t>(planes) & 7) == 0, "field_fwd: planes must be 8-byte aligned");
+    NSIG_REQUIRE(aligned8(planes), "field_fwd: planes must be 8-byte aligned");
     const uint32_t stride = ceil_div(M, 32u) * 32u;
     const float2 *pl = reinterpret_cast<const float2 *>(planes);
     if (int e = check_layout(planes_layout, "field_fwd")) return e;
@@ -1192,22 +1199,27 @@ static int field_fwd_impl(const float *xyzs, const float *dirs, uint32_t M, floa
     NSIG_REQUIRE(!mixed || f16, "field_fwd: this plane set was written in the mixed (fp16) layout; the split-bf16 MLP needs hg_encode_planes");
     if (sigmas_clean != nullptr) {      // field_fwd_twin (it checked its own arguments): the same choice of loop as below
         if (f16 && fwd_pipelined() && geo_feat == nullptr) {
-            if (mixed) k_field_fwd_train_twin<F16, true><<<field_grid(M, true, 2), 256, F16::kFwdLds, st>>>(dirs, M, pl, stride, pk, sigmas, rgbs, masks, sigmas_clean, rgbs_clean);
-            else k_field_fwd_train_twin<F16, false><<<field_grid(M, true, 2), 256, F16::kFwdLds, st>>>(dirs, M, pl, stride, pk, sigmas, rgbs, masks, sigmas_clean, rgbs_clean);
-        } else if (f16) {
-            k_field_fwd_twin<F16><<<field_grid(M, true), 256, F16::kFwdLds, st>>>(dirs, M, pl, stride, pk, sigmas, rgbs, geo_feat, masks, mixed, sigmas_clean, rgbs_clean);
-        } else {
-            k_field_fwd_twin<Bf16x3><<<field_grid(M, true), 256, Bf16x3::kFwdLds, st>>>(dirs, M, pl, stride, pk, sigmas, rgbs, geo_feat, masks, false, sigmas_clean, rgbs_clean);
+            with_flag(mixed, [&](auto kMixed) {
+                k_field_fwd_train_twin<F16, decltype(kMixed)::value><<<field_grid(M, true, 2), 256, F16::kFwdLds, st>>>(dirs, M, pl, stride, pk, sigmas, rgbs, masks, sigmas_clean, rgbs_clean);
+            });
+        } else {      // (mixed is false under the split-bf16 MLP: required above)
+            with_mlp([&](auto tag) {
+                using P = decltype(tag);
+                k_field_fwd_twin<P><<<field_grid(M, true), 256, P::kFwdLds, st>>>(dirs, M, pl, stride, pk, sigmas, rgbs, geo_feat, masks, mixed, sigmas_clean, rgbs_clean);
+            });
         }
         return check_launch("field_fwd_twin");
     }
     if (f16 && fwd_pipelined() && dirs != nullptr && rgbs != nullptr && geo_feat == nullptr) {    // the training render's launch (masks) and staged no-grad renders
-        if (mixed) k_field_fwd_train<F16, true><<<field_grid(M, true, 2), 256, F16::kFwdLds, st>>>(dirs, M, S != nullptr, pl, stride, pk, sigmas, rgbs, masks, rows_dev);
-        else k_field_fwd_train<F16, false><<<field_grid(M, true, 2), 256, F16::kFwdLds, st>>>(dirs, M, S != nullptr, pl, stride, pk, sigmas, rgbs, masks, rows_dev);
+        with_flag(mixed, [&](auto kMixed) {
+            k_field_fwd_train<F16, decltype(kMixed)::value><<<field_grid(M, true, 2), 256, F16::kFwdLds, st>>>(dirs, M, S != nullptr, pl, stride, pk, sigmas, rgbs, masks, rows_dev);
+        });
         return check_launch("field_fwd");
     }
-    if (f16) k_field_fwd<F16, 1><<<field_grid(M, true), 256, F16::kFwdLds, st>>>(xyzs, dirs, M, bound, base, make_level_geom(), S, pl, stride, pk, sigmas, rgbs, geo_feat, masks, ActTrace{}, rows_dev, mixed);
-    else k_field_fwd<Bf16x3, 1><<<field_grid(M, true), 256, Bf16x3::kFwdLds, st>>>(xyzs, dirs, M, bound, base, make_level_geom(), S, pl, stride, pk, sigmas, rgbs, geo_feat, masks, ActTrace{}, rows_dev);
+    with_mlp([&](auto tag) {
+        using P = decltype(tag);
+        k_field_fwd<P, 1><<<field_grid(M, true), 256, P::kFwdLds, st>>>(xyzs, dirs, M, bound, base, make_level_geom(), S, pl, stride, pk, sigmas, rgbs, geo_feat, masks, ActTrace{}, rows_dev, mixed);
+    });
     return check_launch("field_fwd");
 }
 
@@ -1238,8 +1250,8 @@ NSIG_EXPORT int hg_encode_codebook_planes_multi(const float *xyzs, uint32_t M, f
     NSIG_REQUIRE(xyzs && S_multi && cplanes, "hg_encode_codebook_planes_multi: null pointer");
     if (int e = check_multi_k(K, "hg_encode_codebook_planes_multi")) return e;
     NSIG_REQUIRE(bound > 0.0f, "hg_encode_codebook_planes_multi: bound must be positive");
-    NSIG_REQUIRE((reinterpret_cast<uintptr_t>(S_multi) & 15) == 0, "hg_encode_codebook_planes_multi: S_multi must be 16-byte aligned");
-    NSIG_REQUIRE((reinterpret_cast<uintptr_t>(cplanes) & 7) == 0, "hg_encode_codebook_planes_multi: cplanes must be 8-byte aligned");
+    NSIG_REQUIRE(aligned16(S_multi), "hg_encode_codebook_planes_multi: S_multi must be 16-byte aligned");
+    NSIG_REQUIRE(aligned8(cplanes), "hg_encode_codebook_planes_multi: cplanes must be 8-byte aligned");
     NSIG_REQUIRE(M <= (1u << 27), "hg_encode_codebook_planes_multi: M=%u too large", M);
     if (M == 0) return NSIG_OK;
     const uint32_t stride = ceil_div(M, 32u) * 32u;
@@ -1248,8 +1260,9 @@ NSIG_EXPORT int hg_encode_codebook_planes_multi(const float *xyzs, uint32_t M, f
     const uint32_t grid = (uint32_t)(((uint64_t)stride * G + 255) / 256);
     const float cell = make_level_geom().cell[NSIG_BASE_LEVELS];
     const float2 *S = reinterpret_cast<const float2 *>(S_multi);
-    if (pair) k_encode_codebook_planes_multi<true><<<grid, 256, 0, as_stream(stream)>>>(xyzs, M, bound, cell, S, K, G, reinterpret_cast<float2 *>(cplanes), stride);
-    else k_encode_codebook_planes_multi<false><<<grid, 256, 0, as_stream(stream)>>>(xyzs, M, bound, cell, S, K, G, reinterpret_cast<float2 *>(cplanes), stride);
+    with_flag(pair, [&](auto kPair) {
+        k_encode_codebook_planes_multi<decltype(kPair)::value><<<grid, 256, 0, as_stream(stream)>>>(xyzs, M, bound, cell, S, K, G, reinterpret_cast<float2 *>(cplanes), stride);
+    });
     return check_launch("hg_encode_codebook_planes_multi");
 }
 
@@ -1258,8 +1271,8 @@ NSIG_EXPORT int field_fwd_multi(const float *dirs, uint32_t M, const void *packe
     NSIG_REQUIRE(dirs && packed && planes && cplanes && sigmas && rgbs, "field_fwd_multi: null pointer");
     if (int e = check_multi_k(K, "field_fwd_multi")) return e;
     if (int e = check_layout(planes_layout, "field_fwd_multi")) return e;
-    NSIG_REQUIRE((reinterpret_cast<uintptr_t>(packed) & 15) == 0, "field_fwd_multi: packed must be 16-byte aligned");
-    NSIG_REQUIRE((reinterpret_cast<uintptr_t>(planes) & 7) == 0 && (reinterpret_cast<uintptr_t>(cplanes) & 7) == 0, "field_fwd_multi: planes and cplanes must be 8-byte aligned");
+    NSIG_REQUIRE(aligned16(packed), "field_fwd_multi: packed must be 16-byte aligned");
+    NSIG_REQUIRE(aligned8(planes) && aligned8(cplanes), "field_fwd_multi: planes and cplanes must be 8-byte aligned");
     const bool f16 = mlp_precision() == 1, mixed = planes_layout == NSIG_PLANES_MIXED;
     NSIG_REQUIRE(!mixed || f16, "field_fwd_multi: this plane set was written in the mixed (fp16) layout; the split-bf16 MLP needs hg_encode_planes");
     NSIG_REQUIRE(M <= (1u << 27), "field_fwd_multi: M=%u too large", M);      // (the same range as the gather that fills cplanes: row indices and the stride stay far from 2^32)
@@ -1268,8 +1281,10 @@ NSIG_EXPORT int field_fwd_multi(const float *dirs, uint32_t M, const void *packe
     const float2 *pl = reinterpret_cast<const float2 *>(planes), *cp = reinterpret_cast<const float2 *>(cplanes);
     const char *pk = reinterpret_cast<const char *>(packed);
     hipStream_t st = as_stream(stream);
-    if (f16) k_field_fwd_multi<F16><<<field_grid(M, true), 256, F16::kFwdLds, st>>>(dirs, M, pl, stride, pk, mixed, cp, K, sigmas, rgbs);
-    else k_field_fwd_multi<Bf16x3><<<field_grid(M, true), 256, Bf16x3::kFwdLds, st>>>(dirs, M, pl, stride, pk, false, cp, K, sigmas, rgbs);
+    with_mlp([&](auto tag) {      // (mixed is false under the split-bf16 MLP: required above)
+        using P = decltype(tag);
+        k_field_fwd_multi<P><<<field_grid(M, true), 256, P::kFwdLds, st>>>(dirs, M, pl, stride, pk, mixed, cp, K, sigmas, rgbs);
+    });
     return check_launch("field_fwd_multi");
 }
 
@@ -1283,8 +1298,10 @@ NSIG_EXPORT int field_fwd_rows(const float *xyzs, const float *dirs, uint32_t M_
 NSIG_EXPORT int field_color_fwd(const float *dirs, const float *geo_feat, uint32_t M, const void *packed, float *rgbs, nsig_stream_t stream) {
     if (M == 0) return NSIG_OK;
     NSIG_REQUIRE(dirs && geo_feat && packed && rgbs, "field_color_fwd: null pointer");
-    if (mlp_precision() == 1) k_field_color<F16><<<field_grid(M), 256, F16::kFwdLds, as_stream(stream)>>>(dirs, geo_feat, M, reinterpret_cast<const char *>(packed), rgbs);
-    else k_field_color<Bf16x3><<<field_grid(M), 256, Bf16x3::kFwdLds, as_stream(stream)>>>(dirs, geo_feat, M, reinterpret_cast<const char *>(packed), rgbs);
+    with_mlp([&](auto tag) {
+        using P = decltype(tag);
+        k_field_color<P><<<field_grid(M), 256, P::kFwdLds, as_stream(stream)>>>(dirs, geo_feat, M, reinterpret_cast<const char *>(packed), rgbs);
+    });
     return check_launch("field_color_fwd");
 }
 
@@ -1295,12 +1312,11 @@ NSIG_EXPORT int field_bwd(const float *xyzs, uint32_t M, float bound, const floa
     NSIG_REQUIRE(xyzs && grad_sigmas && grad_rgbs && sigmas && rgbs && masks && packed, "field_bwd: null pointer");
     NSIG_REQUIRE(G || dfeat_out || rec_out, "field_bwd: at least one of G / dfeat_out / rec_out must be given");
     NSIG_REQUIRE(bound > 0.0f, "field_bwd: bound must be positive");
-    if (mlp_precision() == 1)
-        k_field_bwd<F16, false><<<field_grid(M), 256, F16::kBwdLds, as_stream(stream)>>>(xyzs, M, bound, 1.0f / kCodebookResolution, grad_sigmas, grad_rgbs, sigmas, rgbs, masks,
-                                                                                 reinterpret_cast<const char *>(packed), G, dfeat_out, rec_out);
-    else
-        k_field_bwd<Bf16x3, false><<<field_grid(M), 256, Bf16x3::kBwdLds, as_stream(stream)>>>(xyzs, M, bound, 1.0f / kCodebookResolution, grad_sigmas, grad_rgbs, sigmas, rgbs,
-                                                                                       masks, reinterpret_cast<const char *>(packed), G, dfeat_out, rec_out);
+    with_mlp([&](auto tag) {
+        using P = decltype(tag);
+        k_field_bwd<P, false><<<field_grid(M), 256, P::kBwdLds, as_stream(stream)>>>(xyzs, M, bound, 1.0f / kCodebookResolution, grad_sigmas, grad_rgbs, sigmas, rgbs, masks,
+                                                                             reinterpret_cast<const char *>(packed), G, dfeat_out, rec_out);
+    });
     return check_launch("field_bwd");
 }
 
@@ -1310,18 +1326,17 @@ NSIG_EXPORT int field_bwd_planned(const float *xyzs, uint32_t M, float bound, co
                                   const float *rgbs, const uint32_t *masks, const void *packed, void *plan, nsig_stream_t stream) {
     if (M == 0) return NSIG_OK;
     NSIG_REQUIRE(xyzs && grad_sigmas && grad_rgbs && sigmas && rgbs && masks && packed && plan, "field_bwd_planned: null pointer");
-    NSIG_REQUIRE(bound > 0.0f && (reinterpret_cast<uintptr_t>(plan) & 15) == 0 && M < (1u << 28), "field_bwd_planned: bound must be positive, plan 16-byte aligned, M < 2^28");
+    NSIG_REQUIRE(bound > 0.0f && aligned16(plan) && M < (1u << 28), "field_bwd_planned: bound must be positive, plan 16-byte aligned, M < 2^28");
     if (mlp_precision() == 1 && bwd_pipelined())
         k_field_bwd_train<F16><<<field_grid(M), 256, F16::kBwdLds, as_stream(stream)>>>(xyzs, M, bound, grad_sigmas, grad_rgbs, sigmas, rgbs, masks,
                                                                                 reinterpret_cast<const char *>(packed), scatter_plan_view(plan, M));
-    else if (mlp_precision() == 1)
-        k_field_bwd<F16, false><<<field_grid(M), 256, F16::kBwdLds, as_stream(stream)>>>(xyzs, M, bound, 1.0f / kCodebookResolution, grad_sigmas, grad_rgbs, sigmas, rgbs, masks,
+    else
+        with_mlp([&](auto tag) {
+            using P = decltype(tag);
+            k_field_bwd<P, false><<<field_grid(M), 256, P::kBwdLds, as_stream(stream)>>>(xyzs, M, bound, 1.0f / kCodebookResolution, grad_sigmas, grad_rgbs, sigmas, rgbs, masks,
                                                                                  reinterpret_cast<const char *>(packed), nullptr, nullptr, nullptr, GradTrace{}, 0,
                                                                                  scatter_plan_view(plan, M));
-    else
-        k_field_bwd<Bf16x3, false><<<field_grid(M), 256, Bf16x3::kBwdLds, as_stream(stream)>>>(xyzs, M, bound, 1.0f / kCodebookResolution, grad_sigmas, grad_rgbs, sigmas, rgbs,
-                                                                                       masks, reinterpret_cast<const char *>(packed), nullptr, nullptr, nullptr, GradTrace{}, 0,
-                                                                                       scatter_plan_view(plan, M));
+        });
     return check_launch("field_bwd_planned");
 }
 

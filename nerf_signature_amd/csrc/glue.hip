@@ -105,7 +105,7 @@ NSIG_EXPORT void *nsig_host_device_pointer(const void *pinned_host) {
 NSIG_EXPORT int loop_step_begin(float *G, uint32_t n_floats, const float *ring_dev, uint32_t slots, uint32_t width, uint32_t *counter, float *msg,
                                 nsig_stream_t stream) {
     NSIG_REQUIRE(G && ring_dev && counter && msg, "loop_step_begin: null pointer");
-    NSIG_REQUIRE((reinterpret_cast<uintptr_t>(G) & 15) == 0 && n_floats % 4 == 0, "loop_step_begin: G must be 16-byte aligned with a multiple of 4 floats");
+    NSIG_REQUIRE(aligned16(G) && n_floats % 4 == 0, "loop_step_begin: G must be 16-byte aligned with a multiple of 4 floats");
     NSIG_REQUIRE(slots >= 1 && width >= 1 && width <= 256, "loop_step_begin: slots >= 1 and 1 <= width <= 256");
     const uint32_t n4 = n_floats / 4;
     k_step_begin<<<ceil_div(n4 > 0 ? n4 : 1u, 256u), 256, 0, as_stream(stream)>>>(reinterpret_cast<float4 *>(G), n4, ring_dev, slots,

@@ -335,7 +335,7 @@ NSIG_EXPORT int rg_refresh_draw(int32_t *keys, int32_t *ids, uint32_t N, uint32_
     if (int e = check_refresh_grid("rg_refresh_draw", H)) return e;
     NSIG_REQUIRE(keys && ids && grid_cas && scratch && iter_dev, "rg_refresh_draw: null pointer");
     NSIG_REQUIRE(N >= 1 && N < (1u << 29) && cas < 8, "rg_refresh_draw: N must be in [1, 2^29), cascade < 8");
-    NSIG_REQUIRE((reinterpret_cast<uintptr_t>(scratch) & 3) == 0 && (reinterpret_cast<uintptr_t>(grid_cas) & 15) == 0, "rg_refresh_draw: scratch must be 4-byte, the grid 16-byte aligned");
+    NSIG_REQUIRE(aligned4(scratch) && aligned16(grid_cas), "rg_refresh_draw: scratch must be 4-byte, the grid 16-byte aligned");
     hipStream_t st = as_stream(stream);
     const uint32_t cells = H * H * H, n_bins = H * H, occ_blocks = ceil_div(cells, kOccCells);
     int32_t *drawn = reinterpret_cast<int32_t *>(scratch), *bins = drawn + 2 * (size_t)N, *occ_prefix = bins + n_bins, *block_sums = occ_prefix + cells;
@@ -343,16 +343,10 @@ NSIG_EXPORT int rg_refresh_draw(int32_t *keys, int32_t *ids, uint32_t N, uint32_
     k_refresh_bins<<<1, 1024, 0, st>>>(block_sums, occ_blocks);
     k_occ_prefix<<<occ_blocks, kOccThreads, 0, st>>>(grid_cas, cells, block_sums, occ_prefix);
     if (n_bins <= kDrawMaxBins) {      // the row histogram fits a workgroup's LDS: no global atomics (k_occ_count's clearing of `bins` is then unused: the totals overwrite them)
-        static bool attr_set = false;
-        const size_t lds = (size_t)n_bins * sizeof(int32_t);
-        if (!attr_set) {
-            if (hipFuncSetAttribute(reinterpret_cast<const void *>(k_refresh_hist_lds), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(kDrawMaxBins * sizeof(int32_t))) != hipSuccess ||
-                hipFuncSetAttribute(reinterpret_cast<const void *>(k_refresh_place_lds), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(kDrawMaxBins * sizeof(int32_t))) != hipSuccess) {
-                set_error("rg_refresh_draw: cannot reserve %zu bytes of LDS", (size_t)kDrawMaxBins * sizeof(int32_t));
-                return NSIG_ERR_LAUNCH;
-            }
-            attr_set = true;
-        }
+        static std::atomic<size_t> granted_hist{0}, granted_place{0};
+        const size_t lds = (size_t)n_bins * sizeof(int32_t), most = (size_t)kDrawMaxBins * sizeof(int32_t);      // (reserved once, for the largest histogram)
+        if (int e = reserve_lds(k_refresh_hist_lds, most, granted_hist, "rg_refresh_draw")) return e;
+        if (int e = reserve_lds(k_refresh_place_lds, most, granted_place, "rg_refresh_draw")) return e;
         const uint32_t n_wg = ceil_div(2u * N, kDrawChunk);
         int32_t *wg_hist = block_sums + occ_blocks;
         k_refresh_draw_keys<<<ceil_div(2u * N, 256u), 256, 0, st>>>(drawn, N, H, occ_prefix, seed, iter_dev, cas);
@@ -394,7 +388,7 @@ NSIG_EXPORT int rg_refresh_finish(float *grid, const float *fresh, uint32_t n_ce
     NSIG_REQUIRE(grid && fresh && partials && bitfield && mean_density && iter_dev, "rg_refresh_finish: null pointer");
     NSIG_REQUIRE(n_cells >= 8 && n_cells % 8 == 0 && window <= 16, "rg_refresh_finish: the cell count must be a positive multiple of 8, window <= 16");
     NSIG_REQUIRE(window == 0 || (count_ring && mean_count), "rg_refresh_finish: a window needs the count ring and somewhere to put the mean");
-    NSIG_REQUIRE((reinterpret_cast<uintptr_t>(grid) & 15) == 0 && (reinterpret_cast<uintptr_t>(partials) & 7) == 0, "rg_refresh_finish: grid must be 16-byte, partials 8-byte aligned");
+    NSIG_REQUIRE(aligned16(grid) && aligned8(partials), "rg_refresh_finish: grid must be 16-byte, partials 8-byte aligned");
     hipStream_t st = as_stream(stream);
     const uint32_t blocks = ceil_div(n_cells, kEmaThreads * kEmaPerThread), n_bytes = n_cells / 8;
     k_grid_ema<<<blocks, kEmaThreads, 0, st>>>(grid, fresh, n_cells, decay, reinterpret_cast<double *>(partials));

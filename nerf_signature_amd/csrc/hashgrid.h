@@ -35,6 +35,11 @@ inline LevelGeom make_level_geom() {
 struct TablePtrs {
     const float *p[NSIG_BASE_LEVELS];
 };
+// the host list of the 16 base tables' device pointers -> a launch argument; a null list or a null table is refused
+inline int fill_base_tables(const float *const *host, TablePtrs &base, const char *who) {
+    NSIG_REQUIRE(host, "%s: null base table list", who);
+    return take_pointers({base.p}, {host}, NSIG_BASE_LEVELS, who, "%s: base table %u is null");
+}
 struct CodebookPtrs {
     const float *p[NSIG_MAX_MESSAGE_DIM];
 };

@@ -1122,17 +1122,12 @@ NSIG_EXPORT int hg_codebook_presum(const float *const *tables_host, uint32_t D, 
     return check_launch("hg_codebook_presum");
 }
 
-static int fill_base(const float *const *host, TablePtrs &base, const char *who) {
-    NSIG_REQUIRE(host, "%s: null base table list", who);
-    return take_pointers({base.p}, {host}, NSIG_BASE_LEVELS, who, "%s: base table %u is null");
-}
-
 NSIG_EXPORT int hg_encode_fwd(const float *x01, uint32_t M, const float *const *base_tables_host, const float *S, float *feat,
                               nsig_stream_t stream) {
     if (M == 0) return NSIG_OK;
     NSIG_REQUIRE(x01 && feat, "hg_encode_fwd: null pointer");
     TablePtrs base{};
-    if (int e = fill_base(base_tables_host, base, "hg_encode_fwd")) return e;
+    if (int e = fill_base_tables(base_tables_host, base, "hg_encode_fwd")) return e;
     NSIG_REQUIRE(M <= (1u << 27), "hg_encode_fwd: M=%u too large", M);
     k_encode<<<ceil_div(M * 16u, 256), 256, 0, as_stream(stream)>>>(x01, M, base, make_level_geom(), S, feat);
     return check_launch("hg_encode_fwd");
@@ -1179,15 +1174,9 @@ NSIG_EXPORT int hg_level_lookup(const float *x01, uint32_t M, float resolution, 
 NSIG_EXPORT int hg_scatter_sliced(const float *rec, uint32_t M, float *G, nsig_stream_t stream) {
     if (M == 0) return NSIG_OK;
     NSIG_REQUIRE(rec && G, "hg_scatter_sliced: null pointer");
-    static bool attr_set = false;
+    static std::atomic<size_t> granted{0};
     const size_t lds = (size_t)kSliceRows * 2 * sizeof(float);
-    if (!attr_set) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(k_scatter_sliced), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
-            set_error("hg_scatter_sliced: cannot reserve %zu bytes of LDS", lds);
-            return NSIG_ERR_LAUNCH;
-        }
-        attr_set = true;
-    }
+    if (int e = reserve_lds(k_scatter_sliced, lds, granted, "hg_scatter_sliced")) return e;
     ScatterTargets tg{};
     tg.g[0] = G;
     k_scatter_sliced<<<kSlices * kReplicas, 1024, lds, as_stream(stream)>>>(rec, M, tg, 1u, (uint32_t)kReplicas);
@@ -1226,19 +1215,21 @@ NSIG_EXPORT int hg_codebook_presum_multi(const float *const *all_tables_host, co
     return check_launch("hg_codebook_presum_multi");
 }
 
+// no points: the 16 gradient tables of a level scatter are all zeros
+static int zero_level_tables(const ScatterTargets &tg, hipStream_t st, const char *who) {
+    for (int l = 0; l < NSIG_BASE_LEVELS; ++l)
+        if (hipMemsetAsync(tg.g[l], 0, (size_t)NSIG_TABLE_ROWS * 2 * sizeof(float), st) != hipSuccess) {
+            set_error("%s: hipMemsetAsync failed", who);
+            return NSIG_ERR_LAUNCH;
+        }
+    return NSIG_OK;
+}
+
 static size_t binned_scratch_bytes(uint32_t M, uint32_t sets) { return (size_t)sets * (sizeof(BinHeader) + (size_t)4 * M * sizeof(uint4)); }
 
 static int reserve_owner_lds(const char *who) {
-    static bool attr_set = false;
-    const size_t lds = (size_t)kBinRows * 2 * sizeof(unsigned long long);
-    if (!attr_set) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(k_scatter_binned), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
-            set_error("%s: cannot reserve %zu bytes of LDS", who, lds);
-            return NSIG_ERR_LAUNCH;
-        }
-        attr_set = true;
-    }
-    return NSIG_OK;
+    static std::atomic<size_t> granted{0};
+    return reserve_lds(k_scatter_binned, (size_t)kBinRows * 2 * sizeof(unsigned long long), granted, who);
 }
 
 // sets record arrays [sets][M][8] -> sets tables; scratch = sets headers, then sets queues
@@ -1276,7 +1267,7 @@ NSIG_EXPORT size_t hg_scatter_binned_scratch_bytes(uint32_t M) { return binned_s
 NSIG_EXPORT int hg_scatter_binned(const float *rec, uint32_t M, float *G, void *scratch, nsig_stream_t stream) {
     if (M == 0) return NSIG_OK;
     NSIG_REQUIRE(rec && G && scratch, "hg_scatter_binned: null pointer");
-    NSIG_REQUIRE((reinterpret_cast<uintptr_t>(rec) & 15) == 0 && (reinterpret_cast<uintptr_t>(scratch) & 15) == 0 && M < (1u << 28),
+    NSIG_REQUIRE(aligned16(rec) && aligned16(scratch) && M < (1u << 28),
                  "hg_scatter_binned: rec and scratch must be 16-byte aligned and M < 2^28");
     ScatterTargets tg{};
     tg.g[0] = G;
@@ -1288,7 +1279,7 @@ NSIG_EXPORT size_t hg_scatter_plan_bytes(uint32_t M) { return scatter_plan_bytes
 NSIG_EXPORT int hg_scatter_plan(const float *xyzs, uint32_t M, float bound, void *plan, nsig_stream_t stream) {
     if (M == 0) return NSIG_OK;
     NSIG_REQUIRE(xyzs && plan, "hg_scatter_plan: null pointer");
-    NSIG_REQUIRE((reinterpret_cast<uintptr_t>(plan) & 15) == 0 && M < (1u << 28) && bound > 0.0f, "hg_scatter_plan: plan must be 16-byte aligned, M < 2^28, bound > 0");
+    NSIG_REQUIRE(aligned16(plan) && M < (1u << 28) && bound > 0.0f, "hg_scatter_plan: plan must be 16-byte aligned, M < 2^28, bound > 0");
     const ScatterPlan pl = scatter_plan_view(plan, M);
     hipStream_t st = as_stream(stream);
     const uint32_t blocks = ceil_div(M, kBinThreads) < kBinGrid ? ceil_div(M, kBinThreads) : kBinGrid;
@@ -1300,7 +1291,7 @@ NSIG_EXPORT int hg_scatter_plan(const float *xyzs, uint32_t M, float bound, void
 NSIG_EXPORT int hg_scatter_planned(const void *plan, uint32_t M, float *G, nsig_stream_t stream) {
     if (M == 0) return NSIG_OK;
     NSIG_REQUIRE(plan && G, "hg_scatter_planned: null pointer");
-    NSIG_REQUIRE((reinterpret_cast<uintptr_t>(plan) & 15) == 0 && M < (1u << 28), "hg_scatter_planned: plan must be 16-byte aligned and M < 2^28");
+    NSIG_REQUIRE(aligned16(plan) && M < (1u << 28), "hg_scatter_planned: plan must be 16-byte aligned and M < 2^28");
     if (int e = reserve_owner_lds("hg_scatter_planned")) return e;
     const ScatterPlan pl = scatter_plan_view(const_cast<void *>(plan), M);
     ScatterTargets tg{};
@@ -1323,18 +1314,11 @@ NSIG_EXPORT int hg_scatter_levels(const float *xyzs, float bound, const void *d_
                                   void *scratch, nsig_stream_t stream) {
     NSIG_REQUIRE(xyzs && d_planes && G_host && scratch, "hg_scatter_levels: null pointer");
     NSIG_REQUIRE(bound > 0.0f && stride >= M && M < (1u << 28), "hg_scatter_levels: bad bound, stride < M or M >= 2^28");
-    NSIG_REQUIRE((reinterpret_cast<uintptr_t>(scratch) & 15) == 0, "hg_scatter_levels: scratch must be 16-byte aligned");
+    NSIG_REQUIRE(aligned16(scratch), "hg_scatter_levels: scratch must be 16-byte aligned");
     ScatterTargets tg{};
     if (int e = take_pointers({tg.g}, {G_host}, NSIG_BASE_LEVELS, "hg_scatter_levels", "%s: table %u has a null pointer")) return e;
     hipStream_t st = as_stream(stream);
-    if (M == 0) {
-        for (int l = 0; l < NSIG_BASE_LEVELS; ++l)
-            if (hipMemsetAsync(tg.g[l], 0, (size_t)NSIG_TABLE_ROWS * 2 * sizeof(float), st) != hipSuccess) {
-                set_error("hg_scatter_levels: hipMemsetAsync failed");
-                return NSIG_ERR_LAUNCH;
-            }
-        return NSIG_OK;
-    }
+    if (M == 0) return zero_level_tables(tg, st, "hg_scatter_levels");
     uint4 *rec = reinterpret_cast<uint4 *>(scratch);
     k_level_records<<<dim3(ceil_div(M, 256u), NSIG_BASE_LEVELS), 256, 0, st>>>(xyzs, bound, reinterpret_cast<const float2 *>(d_planes), M, stride,
                                                                               make_level_geom(), rec);
@@ -1349,7 +1333,7 @@ NSIG_EXPORT size_t hg_levels_plan_bytes(uint32_t M) { return levels_plan_bytes(M
 NSIG_EXPORT int hg_levels_plan(const float *xyzs, uint32_t M, const uint32_t *rows_dev, float bound, void *plan, nsig_stream_t stream) {
     if (M == 0) return NSIG_OK;
     NSIG_REQUIRE(xyzs && plan, "hg_levels_plan: null pointer");
-    NSIG_REQUIRE((reinterpret_cast<uintptr_t>(plan) & 15) == 0 && M < (1u << 27) && bound > 0.0f, "hg_levels_plan: plan must be 16-byte aligned, M < 2^27, bound > 0");
+    NSIG_REQUIRE(aligned16(plan) && M < (1u << 27) && bound > 0.0f, "hg_levels_plan: plan must be 16-byte aligned, M < 2^27, bound > 0");
     const LevelsPlan pl = levels_plan_view(plan, M);
     hipStream_t st = as_stream(stream);
     k_levels_count<<<dim3(pl.n_chunks, NSIG_BASE_LEVELS), kBinThreads, 0, st>>>(xyzs, M, rows_dev, bound, make_level_geom(), pl);
@@ -1364,20 +1348,14 @@ template <typename Prepare>
 static int levels_scatter_launch(const char *who, const float *xyzs, uint32_t M, const uint32_t *rows_dev, float bound, const void *d_planes, uint32_t stride, void *plan,
                                  const ScatterTargets &tg, const OwnerAdam &adam, hipStream_t st, Prepare prepare) {
     NSIG_REQUIRE(xyzs && d_planes && plan, "%s: null pointer", who);
-    NSIG_REQUIRE((reinterpret_cast<uintptr_t>(plan) & 15) == 0 && (reinterpret_cast<uintptr_t>(d_planes) & 7) == 0 && M < (1u << 27) && bound > 0.0f && stride >= M,
+    NSIG_REQUIRE(aligned16(plan) && aligned8(d_planes) && M < (1u << 27) && bound > 0.0f && stride >= M,
                  "%s: plan must be 16-byte and d_planes 8-byte aligned, M < 2^27, bound > 0, stride >= M", who);
     if (!adam.on)
         if (int e = owner_targets_aligned(tg, NSIG_BASE_LEVELS, who)) return e;
     if (int e = reserve_owner_lds(who)) return e;
     const size_t staging = (size_t)kLevelStage * sizeof(uint4);
-    static bool attr_set = false;
-    if (!attr_set) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(k_level_entries), hipFuncAttributeMaxDynamicSharedMemorySize, (int)staging) != hipSuccess) {
-            set_error("%s: cannot reserve %zu bytes of LDS", who, staging);
-            return NSIG_ERR_LAUNCH;
-        }
-        attr_set = true;
-    }
+    static std::atomic<size_t> granted{0};
+    if (int e = reserve_lds(k_level_entries, staging, granted, who)) return e;
     const LevelsPlan pl = levels_plan_view(plan, M);
     k_level_entries<<<dim3(pl.n_chunks, NSIG_BASE_LEVELS), kBinThreads, staging, st>>>(xyzs, M, rows_dev, bound, reinterpret_cast<const float2 *>(d_planes), stride,
                                                                                      make_level_geom(), pl);
@@ -1406,14 +1384,7 @@ NSIG_EXPORT int hg_levels_scatter(const float *xyzs, uint32_t M, const uint32_t 
     ScatterTargets tg{};
     if (int e = take_pointers({tg.g}, {G_host}, NSIG_BASE_LEVELS, "hg_levels_scatter", "%s: table %u has a null pointer")) return e;
     hipStream_t st = as_stream(stream);
-    if (M == 0) {
-        for (int l = 0; l < NSIG_BASE_LEVELS; ++l)
-            if (hipMemsetAsync(tg.g[l], 0, (size_t)NSIG_TABLE_ROWS * 2 * sizeof(float), st) != hipSuccess) {
-                set_error("hg_levels_scatter: hipMemsetAsync failed");
-                return NSIG_ERR_LAUNCH;
-            }
-        return NSIG_OK;
-    }
+    if (M == 0) return zero_level_tables(tg, st, "hg_levels_scatter");
     return levels_scatter_launch("hg_levels_scatter", xyzs, M, rows_dev, bound, d_planes, stride, plan, tg, OwnerAdam{}, st, []() { return (int)NSIG_OK; });
 }
 
@@ -1423,7 +1394,7 @@ NSIG_EXPORT int hg_levels_scatter_adam(const float *xyzs, uint32_t M, const uint
     NSIG_REQUIRE(params_host && exp_avg_host && exp_avg_sq_host && steps_host && lr && scratch, "hg_levels_scatter_adam: null pointer");
     NSIG_REQUIRE(M >= 1, "hg_levels_scatter_adam: M must be positive (a step without points still runs the owners: the device row count may be zero)");
     NSIG_REQUIRE(xyzs && d_planes && plan, "hg_levels_scatter_adam: null pointer");
-    NSIG_REQUIRE((reinterpret_cast<uintptr_t>(plan) & 15) == 0 && (reinterpret_cast<uintptr_t>(d_planes) & 7) == 0 && M < (1u << 27) && bound > 0.0f && stride >= M,
+    NSIG_REQUIRE(aligned16(plan) && aligned8(d_planes) && M < (1u << 27) && bound > 0.0f && stride >= M,
                  "hg_levels_scatter_adam: plan must be 16-byte and d_planes 8-byte aligned, M < 2^27, bound > 0, stride >= M");      // (before the step counts are touched)
     static_assert(NSIG_BASE_LEVELS <= kAdamGroup, "one group of the prepare launch");
     OwnerAdam adam{};
@@ -1443,15 +1414,9 @@ NSIG_EXPORT int hg_scatter_level(const float *xyzs, float bound, const void *d_p
     if (M == 0) return NSIG_OK;
     NSIG_REQUIRE(xyzs && d_plane && G, "hg_scatter_level: null pointer");
     NSIG_REQUIRE(level < NSIG_BASE_LEVELS && bound > 0.0f, "hg_scatter_level: level %u out of range or bad bound", level);
-    static bool attr_set = false;
+    static std::atomic<size_t> granted{0};
     const size_t lds = (size_t)kSliceRows * 2 * sizeof(float);
-    if (!attr_set) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(k_scatter_level), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
-            set_error("hg_scatter_level: cannot reserve %zu bytes of LDS", lds);
-            return NSIG_ERR_LAUNCH;
-        }
-        attr_set = true;
-    }
+    if (int e = reserve_lds(k_scatter_level, lds, granted, "hg_scatter_level")) return e;
     k_scatter_level<<<kSlices * kReplicas, 1024, lds, as_stream(stream)>>>(xyzs, bound, reinterpret_cast<const float2 *>(d_plane), M,
                                                                          1.0f / kBaseResolution[level], G);
     return check_launch("hg_scatter_level");

@@ -369,7 +369,7 @@ NSIG_EXPORT size_t mc_scratch_bytes(uint32_t nx, uint32_t ny, uint32_t nz) {
 NSIG_EXPORT int mc_count(const float *u, uint32_t nx, uint32_t ny, uint32_t nz, float threshold, void *scratch, uint32_t *totals, nsig_stream_t stream) {
     NSIG_REQUIRE(u && scratch && totals, "mc_count: null pointer");
     if (int e = check_dims("mc_count", nx, ny, nz)) return e;
-    NSIG_REQUIRE(reinterpret_cast<uintptr_t>(scratch) % 16 == 0, "mc_count: scratch must be 16-byte aligned");
+    NSIG_REQUIRE(aligned16(scratch), "mc_count: scratch must be 16-byte aligned");
     const McDims d = make_dims(nx, ny, nz);
     const McScratch s = mc_split(scratch, d.N);
     k_mc_count<<<s.nb, kMcThreads, 0, as_stream(stream)>>>(u, d, threshold, s.code, s.sums, s.nb);
@@ -381,7 +381,7 @@ NSIG_EXPORT int mc_emit(const float *u, uint32_t nx, uint32_t ny, uint32_t nz, f
                         float *vertices, int32_t *triangles, nsig_stream_t stream) {
     NSIG_REQUIRE(u && scratch, "mc_emit: null pointer");
     if (int e = check_dims("mc_emit", nx, ny, nz)) return e;
-    NSIG_REQUIRE(reinterpret_cast<uintptr_t>(scratch) % 16 == 0, "mc_emit: scratch must be 16-byte aligned");
+    NSIG_REQUIRE(aligned16(scratch), "mc_emit: scratch must be 16-byte aligned");
     NSIG_REQUIRE((n_vertices == 0) == (n_triangles == 0), "mc_emit: %u vertices with %u triangles: not the totals of mc_count", n_vertices, n_triangles);
     if (n_vertices == 0) return NSIG_OK;
     NSIG_REQUIRE(vertices && triangles, "mc_emit: null pointer");
@@ -396,7 +396,7 @@ NSIG_EXPORT int mc_vertex_normals(const float *u, uint32_t nx, uint32_t ny, uint
                                   float scale_x, float scale_y, float scale_z, float *normals, float *gradients, nsig_stream_t stream) {
     NSIG_REQUIRE(u && scratch, "mc_vertex_normals: null pointer");
     if (int e = check_dims("mc_vertex_normals", nx, ny, nz)) return e;
-    NSIG_REQUIRE(reinterpret_cast<uintptr_t>(scratch) % 16 == 0, "mc_vertex_normals: scratch must be 16-byte aligned");
+    NSIG_REQUIRE(aligned16(scratch), "mc_vertex_normals: scratch must be 16-byte aligned");
     NSIG_REQUIRE((uint64_t)n_vertices <= 3ull * nx * ny * nz, "mc_vertex_normals: %u vertices is out of range for %u x %u x %u nodes", n_vertices, nx, ny, nz);
     if (n_vertices == 0) return NSIG_OK;
     NSIG_REQUIRE(normals, "mc_vertex_normals: null pointer");
@@ -415,7 +415,7 @@ NSIG_EXPORT size_t mesh_components_scratch_bytes(uint32_t V, uint32_t T) {
 NSIG_EXPORT int mesh_components(const int32_t *triangles, uint32_t T, uint32_t V, int32_t *labels, void *scratch, nsig_stream_t stream) {
     NSIG_REQUIRE(V < (1u << 31) && T < (1u << 31), "mesh_components: V=%u, T=%u out of range (each below 2^31)", V, T);
     NSIG_REQUIRE(scratch && (triangles || T == 0) && (labels || V == 0), "mesh_components: null pointer");
-    NSIG_REQUIRE(reinterpret_cast<uintptr_t>(scratch) % 16 == 0, "mesh_components: scratch must be 16-byte aligned");
+    NSIG_REQUIRE(aligned16(scratch), "mesh_components: scratch must be 16-byte aligned");
     uint32_t *err = static_cast<uint32_t *>(scratch);
     k_cc_init<<<max(1u, ceil_div(V, kCcThreads)), kCcThreads, 0, as_stream(stream)>>>(labels, V, err);
     if (T) k_cc_hook<<<ceil_div(T, kCcThreads), kCcThreads, 0, as_stream(stream)>>>(triangles, T, V, labels, err);

@@ -288,9 +288,9 @@ NSIG_EXPORT int im_range_sse(const float *pred, const float *truth, uint32_t B, 
     NSIG_REQUIRE(pred && truth && scratch && extrema && sse, "im_range_sse: null pointer");
     NSIG_REQUIRE(B >= 1 && B <= kImMaxBatch, "im_range_sse: batch of %u images is out of range (1 .. %u)", B, kImMaxBatch);
     NSIG_REQUIRE(n >= 1 && n <= (1ull << 40), "im_range_sse: %llu values per image is out of range", (unsigned long long)n);
-    NSIG_REQUIRE(reinterpret_cast<uintptr_t>(scratch) % 16 == 0, "im_range_sse: scratch must be 16-byte aligned");
+    NSIG_REQUIRE(aligned16(scratch), "im_range_sse: scratch must be 16-byte aligned");
     const RangeScratch s = range_split(scratch, B, n);
-    const int vec = n % 4 == 0 && reinterpret_cast<uintptr_t>(pred) % 16 == 0 && reinterpret_cast<uintptr_t>(truth) % 16 == 0;
+    const int vec = n % 4 == 0 && aligned16(pred) && aligned16(truth);
     k_im_range<<<dim3(s.nb, B), kImThreads, 0, as_stream(stream)>>>(pred, truth, n, vec, s.ext, s.sse);
     k_im_range_finish<<<B, kImThreads, 0, as_stream(stream)>>>(s.ext, s.sse, s.nb, B, extrema, sse);
     return check_launch("im_range_sse");
@@ -309,7 +309,7 @@ NSIG_EXPORT int im_ssim(const float *pred, const float *truth, uint32_t B, uint3
     NSIG_REQUIRE(H >= (uint32_t)kWin && W >= (uint32_t)kWin && H <= kImMaxSide && W <= kImMaxSide,
                  "im_ssim: image of %u x %u pixels is out of range (each side %d .. %u: one 11 x 11 window at least)", H, W, kWin, kImMaxSide);
     NSIG_REQUIRE(extrema || data_range >= 0.0f, "im_ssim: without device extrema the data range must be a number >= 0");
-    NSIG_REQUIRE(reinterpret_cast<uintptr_t>(scratch) % 16 == 0, "im_ssim: scratch must be 16-byte aligned");
+    NSIG_REQUIRE(aligned16(scratch), "im_ssim: scratch must be 16-byte aligned");
     const uint32_t gx = ssim_tiles_x(W), gy = ssim_tiles_y(H);
     const dim3 grid(gx, gy, B);
     const SsimWindow win = make_window();

@@ -1251,7 +1251,7 @@ NSIG_EXPORT int rm_morton3D_invert(const int32_t *indices, uint32_t N, int32_t *
 NSIG_EXPORT int rm_packbits(const float *grid, uint32_t n_bytes, float density_thresh, uint8_t *bitfield,
                             nsig_stream_t stream) {
     NSIG_REQUIRE(grid && bitfield, "rm_packbits: null pointer");
-    NSIG_REQUIRE((reinterpret_cast<uintptr_t>(grid) & 15) == 0, "rm_packbits: grid must be 16-byte aligned");
+    NSIG_REQUIRE(aligned16(grid), "rm_packbits: grid must be 16-byte aligned");
     if (n_bytes == 0) return NSIG_OK;
     k_packbits<<<ceil_div(ceil_div(n_bytes, 4), 256), 256, 0, as_stream(stream)>>>(grid, n_bytes, density_thresh, bitfield);
     return check_launch("rm_packbits");
@@ -1604,7 +1604,7 @@ static int sample_rays(const char *name, const float *poses, uint32_t P, const f
     NSIG_REQUIRE(P > 0 && H > 0 && W > 0 && fx != 0.0f && fy != 0.0f, "%s: empty pose store, bad image size or focal length", name);
     NSIG_REQUIRE(gt == nullptr || images != nullptr, "%s: ground truth requested without an image store", name);
     NSIG_REQUIRE((uint64_t)H * W < (1ull << 32), "%s: image too large", name);
-    NSIG_REQUIRE(!RGBA || (reinterpret_cast<uintptr_t>(images) & 15u) == 0, "%s: the RGBA store must be 16-byte aligned", name);
+    NSIG_REQUIRE(!RGBA || aligned16(images), "%s: the RGBA store must be 16-byte aligned", name);
     k_sample_rays<RGBA><<<ceil_div(N, 256u), 256, 0, as_stream(stream)>>>(poses, P, images, fx, fy, cx, cy, H, W, N, step_counter, stride, offset, (uint32_t)seed,
                                                                           (uint32_t)(seed >> 32), rays_o, rays_d, gt, inds_out, pose_out, bg_out);
     return check_launch(name);
@@ -1647,7 +1647,7 @@ static int sample_rays_weighted(const char *name, const float *poses, uint32_t P
     NSIG_REQUIRE(P > 0 && H > 0 && W > 0 && fx != 0.0f && fy != 0.0f, "%s: empty pose store, bad image size or focal length", name);
     NSIG_REQUIRE(gt == nullptr || images != nullptr, "%s: ground truth requested without an image store", name);
     NSIG_REQUIRE((uint64_t)H * W < (1ull << 32), "%s: image too large", name);
-    NSIG_REQUIRE(!RGBA || (reinterpret_cast<uintptr_t>(images) & 15u) == 0, "%s: the RGBA store must be 16-byte aligned", name);
+    NSIG_REQUIRE(!RGBA || aligned16(images), "%s: the RGBA store must be 16-byte aligned", name);
     NSIG_REQUIRE(grid >= 1 && grid <= kMaxErrorGrid, "%s: grid %u out of range (1..%u)", name, grid, kMaxErrorGrid);
     NSIG_REQUIRE(N >= 1 && N <= grid * grid, "%s: N %u out of range (1..grid * grid = %u: a draw without replacement)", name, N, grid * grid);
     k_sample_rays_weighted<RGBA><<<1, kWeightedThreads, 0, as_stream(stream)>>>(poses, P, images, fx, fy, cx, cy, H, W, N, step_counter, stride, offset, (uint32_t)seed,
@@ -1676,7 +1676,7 @@ NSIG_EXPORT int rg_blend_random_background(const float *rgba, uint32_t N, const 
                                            nsig_stream_t stream) {
     if (N == 0) return NSIG_OK;
     NSIG_REQUIRE(rgba && bg_out && gt_out, "rg_blend_random_background: null pointer");
-    NSIG_REQUIRE((reinterpret_cast<uintptr_t>(rgba) & 15u) == 0, "rg_blend_random_background: rgba must be 16-byte aligned");
+    NSIG_REQUIRE(aligned16(rgba), "rg_blend_random_background: rgba must be 16-byte aligned");
     k_blend_random_background<<<ceil_div(N, 256u), 256, 0, as_stream(stream)>>>(reinterpret_cast<const float4 *>(rgba), N, step_counter, (uint32_t)seed,
                                                                                 (uint32_t)(seed >> 32), bg_out, gt_out);
     return check_launch("rg_blend_random_background");

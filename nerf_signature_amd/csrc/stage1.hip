@@ -279,7 +279,7 @@ NSIG_EXPORT int field_wgrad(uint32_t M, const uint32_t *rows_dev, const void *pl
                  "field_wgrad: null pointer");
     NSIG_REQUIRE(M >= 1 && M < (1u << 28), "field_wgrad: M=%u out of range", M);
     const void *all[] = {planes, act_hs, act_cin, act_h1, act_h2, d_hs, d_so, d_h1, d_h2, d_out, scratch};
-    for (const void *p : all) NSIG_REQUIRE((reinterpret_cast<uintptr_t>(p) & 15) == 0, "field_wgrad: every buffer must be 16-byte aligned");
+    for (const void *p : all) NSIG_REQUIRE(aligned16(p), "field_wgrad: every buffer must be 16-byte aligned");
     const uint32_t stride = ceil_div(M, 32u) * 32u, n_wg = wgrad_workgroups(M);
     WgradArgs a{reinterpret_cast<const float2 *>(planes), act_hs, act_cin, act_h1, act_h2, d_hs, d_so, d_h1, d_h2, d_out};
     hipStream_t st = as_stream(stream);

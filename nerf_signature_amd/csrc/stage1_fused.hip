@@ -343,7 +343,7 @@ static int bwd_wgrad_impl(const char *who, bool trace_f16, uint32_t M, const uin
                  grad_sigma_params && grad_color_params, "%s: null pointer", who);
     NSIG_REQUIRE(M >= 1 && M <= (1u << 26), "%s: M=%u out of range (1 .. 2^26, as field_fwd_trace: the lane part of an address is a 32-bit byte offset of up to 32 x stride)", who, M);
     const void *all[] = {packed, planes, act_hs, act_cin, act_h1, act_h2, d_planes, scratch};
-    for (const void *q : all) NSIG_REQUIRE((reinterpret_cast<uintptr_t>(q) & 15) == 0, "%s: packed, planes, the layer inputs, d_planes and scratch must be 16-byte aligned", who);
+    for (const void *q : all) NSIG_REQUIRE(aligned16(q), "%s: packed, planes, the layer inputs, d_planes and scratch must be 16-byte aligned", who);
     const uint32_t stride = ceil_div(M, 32u) * 32u, n_wg = fused_workgroups(M);
     FusedArgs a{grad_sigmas, grad_rgbs, sigmas, rgbs, masks, reinterpret_cast<const char *>(packed), reinterpret_cast<const float2 *>(planes),
                 reinterpret_cast<const float *>(act_hs), reinterpret_cast<const float *>(act_cin), reinterpret_cast<const float *>(act_h1), reinterpret_cast<const float *>(act_h2),

@@ -150,6 +150,63 @@ def test_optimiser_and_codebook_refusals_word_for_word(native):
     refused("hg_fanout_grad", "G must be 16-byte aligned", off, ok2, 2, 0, None)
 
 
+def test_parser_on_literal_declarations(native):
+    """parse_header on text written here: pointers of any depth, each scalar type, (void), a declaration over three lines, one inside a block comment, an unknown type."""
+    vp, u32, fl, c = native._vp, native._u32, native._fl, native._c
+    got = native.parse_header("""
+#define SOMETHING(x) 1
+typedef void *nsig_stream_t;
+int a(const float *const *x, void *, uint64_t seed, double, nsig_stream_t stream);   // int never(float x);
+size_t b(void);
+/* int inside_a_comment(uint32_t n);
+   int another(float x); */
+const char *c3(uint32_t n,
+               int32_t k, int flag,
+               float v, size_t bytes);
+void *d(const void *host);
+""")
+    assert got == {"a": (c.c_int, [vp, vp, c.c_uint64, c.c_double, vp]), "b": (c.c_size_t, []),
+                   "c3": (c.c_char_p, [u32, c.c_int32, c.c_int, fl, c.c_size_t]), "d": (vp, [vp])}
+    with pytest.raises(native.NativeError, match=r"bad\(uint32_t n, long double v\).*'long double v'"):
+        native.parse_header("int ok(float x);\nint bad(uint32_t n,\n        long double v);\n")
+    with pytest.raises(native.NativeError, match=r"unsigned frob\(int x\);"):      # a return type outside the four: refused, not skipped
+        native.parse_header("int ok(float x);\nunsigned frob(int x);\n")
+
+
+def test_parser_finds_every_declaration(native):
+    assert len(native.parse_header(open(os.path.join(ROOT, "include", "nerfsig.h")).read())) == len(_declared())
+    assert set(native._RESTYPES) == set(native.SIGNATURES) == set(_declared())
+
+
+def test_pinned_signatures_one_per_c_type(native):
+    """Written out here, not derived: a 64-bit seed passed as 32 bits, or a double as a float, loads and runs."""
+    c, vp, S, R = native._c, native._vp, native.SIGNATURES, native._RESTYPES
+    assert S["rg_sample_rays"][13] is c.c_uint64 and len(S["rg_sample_rays"]) == 20
+    assert S["wm_distort_draw"][1] is c.c_uint64 and S["wm_distort_draw"][0] is c.c_uint32
+    assert S["opt_ema_update"] == [c.c_uint32, vp, vp, vp, vp, c.c_double, vp]
+    assert S["hg_levels_scatter_adam"][7:11] == [vp, vp, vp, vp] and S["hg_levels_scatter_adam"][12:16] == [c.c_float] * 4
+    assert S["field_fwd_multi"][4] is c.c_int and S["field_fwd_multi"][6] is c.c_uint32
+    assert R["hg_planes_bytes"] is c.c_size_t and S["hg_planes_bytes"] == [c.c_uint32]
+    assert R["nsig_last_error"] is c.c_char_p and S["nsig_last_error"] == []
+    assert R["nsig_host_device_pointer"] is c.c_void_p and S["nsig_host_device_pointer"] == [vp]
+    assert S["rm_march_train_scan_write_max_rays"] == [] and R["rm_march_train_scan_write_max_rays"] is c.c_int
+    assert R["rg_sample_rays"] is c.c_int
+
+
+def test_missing_header_fails_loudly(native, tmp_path):
+    """The header is found relative to the package: a copy of the loader in a tree without include/nerfsig.h refuses to import, naming the path it looked at."""
+    import importlib.util
+    import shutil
+    pkg = tmp_path / "pkg"
+    pkg.mkdir()
+    shutil.copy(native.__file__, pkg / "_native.py")
+    spec = importlib.util.spec_from_file_location("_native_without_header", pkg / "_native.py")
+    with pytest.raises(Exception) as e:
+        spec.loader.exec_module(importlib.util.module_from_spec(spec))
+    assert type(e.value).__name__ == "NativeError" and isinstance(e.value, RuntimeError)       # (the copy's own NativeError class)
+    assert str(tmp_path / "pkg" / ".." / "include" / "nerfsig.h") in str(e.value)
+
+
 def test_missing_library_fails_loudly(native, monkeypatch):
     monkeypatch.setattr(native, "_lib", None)
     monkeypatch.setattr(native, "_bound", {})
