@@ -568,13 +568,28 @@ int dec_bn_gelu_bwd(const float *dy, const float *x, const float *gamma, const f
  *   params   host array of 29 device pointers: for l = 0..8 {conv weight [Cout,Cin_l,3,3], bn weight, bn bias}, then
  *            linear weight [1,1], linear bias [1].  conv biases are not inputs: BatchNorm's batch-mean subtraction cancels them.
  *   grads    host array of 29 device pointers, same order and shapes (written, not accumulated); grad_img has img's layout
- *   workspace: dec_workspace_bytes(B, Cin, H, W) bytes (0 = shape not supported: H*W <= 1024, Cin <= 32, LDS limits);
+ *   workspace: dec_workspace_bytes(B, Cin, H, W) bytes; 0 = shape not supported.  A shape is supported when all of these hold, with
+ *            R = 2 + the most image rows a run of 64 consecutive pixels (starting at a multiple of 64) touches:
+ *              - B * H * W >= 2 and H * W <= 1024;
+ *              - B * ceil(H * W / 64) <= 192                     (the batch statistics are combined from registers);
+ *              - R * (W + 2) <= 406                              (the rows a 64 -> 64 layer stages fit 160 KiB of LDS);
+ *              - Cin <= 32;
+ *              - Cin * (R * (W + 2) + 576) + 256 <= 16384        (Cin != 3 only: layer 0 keeps its input rows and weights in 64 KiB of LDS);
+ *              - Cin * (H + 2) * (W + 2) + 2496 <= 16384         (layer 0's weight gradient keeps the padded image in 64 KiB of LDS).
+ *            The largest Cin is therefore 25 at 6x6, 23 at 12x12 and 16x16, 20 at 24x24, 12 at 32x32.  input_mode 1 needs Cin <= 8.
  *            dec_backward reads what dec_forward left there, so the pair must share it and nothing may overwrite it between.
+ *   dec_workspace_layout (host only, no GPU call): where the intermediates lie in that workspace, for tests and tools.  offsets receives 72 byte
+ *            offsets in the order the workspace is carved: for l = 0..8 {x_l, xhat_l, gprime_l, dz_l, act_l (l < 8 only), stat_l, bsum_l, minv_l},
+ *            then pool.  x/xhat/gprime/dz/act are [B][H*W][C] fp32 (C = 64, layer 8: 1); stat (sum, M2 about the pair mean) and bsum (sum dz,
+ *            sum dz*xhat) are [pair*B + image][C][2], one partial per (run of 64 pixels, image); minv is [mean | 1/sqrt(var + eps)][C]; pool [B].
+ *            geom receives {ntile, npair, rows_max, nband, R, RS}: 32-pixel tiles, 64-pixel pairs, most halo rows a pair stages, the
+ *            weight-gradient kernel's row bands, rows per band and halo row stride.  An unsupported shape returns NSIG_ERR_ARG.
  *   weights_stream: pass `stream` again for one in-order launch sequence.  A different stream receives the parameter-gradient
  *            kernels (ordered after the data-gradient chain by an event), so that grad_img's consumers on `stream` need not wait
  *            for them; the caller then joins weights_stream before reading `grads`.
  */
 size_t dec_workspace_bytes(uint32_t B, uint32_t Cin, uint32_t H, uint32_t W);
+int dec_workspace_layout(uint32_t B, uint32_t Cin, uint32_t H, uint32_t W, uint64_t *offsets, uint32_t *geom);
 int dec_forward(const float *img, uint32_t input_mode, const float *mean_host, const float *std_host, const float *const *params_host,
                 uint32_t B, uint32_t Cin, uint32_t H, uint32_t W, float eps, void *workspace, float *decoded, float *clamped_out,
                 nsig_stream_t stream);

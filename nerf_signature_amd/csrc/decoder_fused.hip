@@ -1393,17 +1393,23 @@ static bool make_geom(uint32_t B, uint32_t Cin, uint32_t H, uint32_t W, float ep
 
 struct Carver {
     char *base;
+    uint64_t *offsets;   // optional: receives the byte offset of every array, in order
     size_t off = 0;
+    int n = 0;
     template <typename T>
     T *take(size_t count) {
         T *p = base ? reinterpret_cast<T *>(base + off) : nullptr;
+        if (offsets) offsets[n++] = off;
         off += (count * sizeof(T) + 255) / 256 * 256;
         return p;
     }
 };
 
-static size_t carve(void *base, const DecGeom &g, DecWs &ws) {
-    Carver c{reinterpret_cast<char *>(base)};
+constexpr int kDecLayoutOffsets = 8 * 8 + 7 + 1;   // x, xhat, gprime, dz, act (l < 8), stat, bsum, minv per layer, then pool: what dec_workspace_layout reports
+constexpr int kCarved = kDecLayoutOffsets + 4;     // + wpart, wpart0, wpart8, packed
+
+static size_t carve(void *base, const DecGeom &g, DecWs &ws, uint64_t *offsets = nullptr) {
+    Carver c{reinterpret_cast<char *>(base), offsets};
     const size_t BP = (size_t)g.B * g.P, np = (size_t)g.B * g.npair;
     for (int l = 0; l < kLayers; ++l) {
         const size_t C = l < 8 ? kC : 1;
@@ -1466,6 +1472,24 @@ NSIG_EXPORT size_t dec_workspace_bytes(uint32_t B, uint32_t Cin, uint32_t H, uin
     DecWs ws;
     if (B == 0 || Cin == 0 || Cin > kMaxCin || H == 0 || W == 0 || (uint64_t)H * W > kMaxP || (uint64_t)B * H * W < 2 || !make_geom(B, Cin, H, W, 0.0f, g)) return 0;
     return carve(nullptr, g, ws);
+}
+
+// Where the arrays dec_forward / dec_backward leave behind lie in the workspace, and the geometry make_geom chose: a host-only view for tests and
+// tools (no GPU call).  offsets: kDecLayoutOffsets byte offsets in carve()'s order -- for l = 0..8 {x, xhat, gprime, dz, act (l < 8 only), stat,
+// bsum, minv}, then pool; geom: {ntile, npair, rows_max, nband, R, RS}.
+NSIG_EXPORT int dec_workspace_layout(uint32_t B, uint32_t Cin, uint32_t H, uint32_t W, uint64_t *offsets, uint32_t *geom) {
+    static_assert(kDecLayoutOffsets == 72, "include/nerfsig.h documents 72 offsets");
+    NSIG_REQUIRE(offsets && geom, "dec_workspace_layout: null pointer");
+    NSIG_REQUIRE(dec_workspace_bytes(B, Cin, H, W) != 0, "dec_workspace_layout: unsupported image shape %ux%ux%ux%u (see dec_workspace_bytes)", B, Cin, H, W);
+    DecGeom g;
+    DecWs ws;
+    make_geom(B, Cin, H, W, 0.0f, g);
+    uint64_t carved[kCarved];
+    carve(nullptr, g, ws, carved);
+    std::memcpy(offsets, carved, sizeof(uint64_t) * kDecLayoutOffsets);
+    const uint32_t gv[6] = {g.ntile, g.npair, g.rows_max, g.nband, g.R, g.RS};
+    std::memcpy(geom, gv, sizeof(gv));
+    return 0;
 }
 
 // grad_img (through the clamp) = clamp mask x the transposed blur of gy: gx[p] = sum over the (q, tap) whose reflected source is p of k[tap] * gy[q].

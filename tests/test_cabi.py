@@ -43,6 +43,28 @@ def test_host_only_queries(native):
     native.call("mlp_set_precision", before)
 
 
+def test_decoder_workspace_layout_is_host_only(native):
+    """dec_workspace_layout: 72 offsets in carve order, increasing, 256-byte aligned, the last below dec_workspace_bytes; an unsupported shape and a null
+    pointer are refused."""
+    c = native._c
+    for shape in ((32, 3, 12, 12), (2, 3, 32, 32), (3, 3, 1, 1), (2, 25, 6, 6)):
+        off, geom = (c.c_uint64 * 72)(), (c.c_uint32 * 6)()
+        native.call("dec_workspace_layout", *shape, off, geom)
+        off, total = list(off), native.fn("dec_workspace_bytes")(*shape)
+        assert off[0] == 0 and all(b > a for a, b in zip(off, off[1:])) and all(o % 256 == 0 for o in off) and off[-1] + 4 * shape[0] <= total
+        B, _, H, W = shape
+        ntile, npair, rows_max, nband, R, RS = geom
+        assert ntile == -(-H * W // 32) and npair == -(-ntile // 2) and nband == -(-H // R) and RS % 8 == 0 and RS >= W + 2 and 3 <= rows_max <= H + 2
+        assert off[1] - off[0] == -(-B * H * W * 64 * 4 // 256) * 256                 # x_0 is [B][P][64] fp32
+    with pytest.raises(ValueError, match="unsupported image shape 193x3x5x5"):
+        native.call("dec_workspace_layout", 193, 3, 5, 5, (c.c_uint64 * 72)(), (c.c_uint32 * 6)())
+    with pytest.raises(ValueError, match="unsupported image shape"):
+        native.call("dec_workspace_layout", 2, 33, 6, 6, (c.c_uint64 * 72)(), (c.c_uint32 * 6)())
+    with pytest.raises(ValueError, match="null pointer"):
+        native.call("dec_workspace_layout", 2, 3, 6, 6, None, (c.c_uint32 * 6)())
+    assert native.SIGNATURES["dec_workspace_layout"] == [c.c_uint32] * 4 + [native._vp, native._vp]
+
+
 def test_argument_validation_needs_no_gpu(native):
     with pytest.raises(ValueError, match="null pointer"):
         native.call("rm_morton3D", None, 4, None, None)
