@@ -622,7 +622,30 @@ int dec_backward(const float *grad_decoded, const float *img, uint32_t input_mod
  * wm_distort_geom_fwd: out [B, H, W_out, C] = the layer (4: dist_param = (cos, sin) per image, W_out = W; 5: dist_param[0] = sf, W_out = floor(W * sf),
  * computed by the caller) on clamp(img [B, H, W, C]); clamped_out (optional) = clamp(img).  _bwd: grad_img [B, H, W, C] = clamp mask x the adjoint of
  * the resampling applied to grad_out [B, H, W_out, C] (gather form, deterministic).
+ *
+ * 6 mixed: every step trains against ONE kind of a set, and which one is not a launch argument but a word in device memory, so that one captured
+ * step serves every kind.  The `distortion` argument is then NSIG_DISTORT_MIXED_CODE(mask, n_images): mask bit k = kind k belongs to the set (bit 0:
+ * "none", an undistorted step), n_images = the number of rotation pairs the block holds (read by wm_distort_draw only; the other entry points know B).
+ * dist_param is the parameter BLOCK, device float[NSIG_MIXED_ROTATION + 2 n_images]:
+ *   [NSIG_MIXED_SELECTOR]    uint32: the kind of this step (0..5)
+ *   [NSIG_MIXED_BRIGHTNESS]  f      [NSIG_MIXED_SIGMA]  sigma      [NSIG_MIXED_SCALING]  sf
+ *   [NSIG_MIXED_ROTATION + 2 i], [+ 2 i + 1]   (cos, sin) of image i
+ * and dist_noise the noise tensor (needed when the set holds noise).  wm_distort_draw(6): selector = the (floor(u n))-th member of the set in kind order,
+ * u from (seed, *step_counter) in a sequence of its own; then the selected kind's parameter, bit for bit what wm_distort_draw(kind) writes into
+ * param_out[0..] at the same (seed, step) -- 5: sf = 0.75 + 0.5 u of the same word, what a host draws as distortion.host_uniform.  The rotation pairs are
+ * written every step: (1, 0) for every image unless rotation is selected; the noise only when selected (n_noise = its element count).
+ * dec_forward_train / wm_distort_fwd read the selector on load and run the selected kind's statements (4, 5 and 0: the clamped value -- the geometric
+ * kinds stay wm_distort_geom_fwd / _bwd on dist_param + NSIG_MIXED_ROTATION or + NSIG_MIXED_SCALING; at (1, 0) the rotation is an exact copy).
+ * dec_backward_train(6) always needs grad_scratch: one launch behind the epilogue reads the selector and applies the selected kind's adjoint and the
+ * clamp mask; wm_distort_bwd(6) is that launch.
  */
+#define NSIG_DISTORT_MIXED 6u
+#define NSIG_DISTORT_MIXED_CODE(mask, n_images) (NSIG_DISTORT_MIXED | ((uint32_t)(mask) << 8) | ((uint32_t)(n_images) << 16))
+#define NSIG_MIXED_SELECTOR 0
+#define NSIG_MIXED_BRIGHTNESS 1
+#define NSIG_MIXED_SIGMA 2
+#define NSIG_MIXED_SCALING 3
+#define NSIG_MIXED_ROTATION 4
 int dec_forward_train(const float *img, const float *mean_host, const float *std_host, const float *const *params_host, uint32_t B,
                       uint32_t Cin, uint32_t H, uint32_t W, float eps, void *workspace, float *decoded, float *clamped_out,
                       uint32_t distortion, const float *dist_param, const float *dist_noise, const float *bce_message, float bce_temp,

@@ -102,7 +102,7 @@ class BlockDecodeGraph:
         `scaling` (which changes the decoder's input width from step to step) is part of the captured forward."""
         if self.failed is not None or dropin_off("block_graph"):
             return None
-        if distortion is not None and (distortion.name == "scaling" or distortion.param is None or not distortion.param.is_cuda):
+        if distortion is not None and (distortion.name == "scaling" or distortion.mixed or distortion.param is None or not distortion.param.is_cuda):
             return None
         if not (torch.is_tensor(message) and rays_o.is_cuda and rays_o.dim() == 4 and model.training and torch.is_grad_enabled() and model.cuda_ray
                 and not torch.cuda.is_current_stream_capturing() and model.normalization is normalize_img and model.grad_sink is None

@@ -23,6 +23,21 @@ import torch.nn.functional as F
 from . import _native as nv
 
 KINDS = {"none": 0, "noise": 1, "brightness": 2, "blurring": 3, "rotation": 4, "scaling": 5}
+NAMES = {v: k for k, v in KINDS.items()}
+# The mixed layer (a set of kinds, one of them drawn per step): the native code 6 and the words of its parameter block (include/nerfsig.h)
+MIXED = 6
+SELECTOR, BRIGHTNESS, SIGMA, SCALING, ROTATION = 0, 1, 2, 3, 4
+
+
+def parse_kinds(distortion):
+    """The members of a mixed set, in kind order: from a tuple / list of names, "a+b+c", or "mixed" (all five).  "none" is a legal member (an undistorted step)."""
+    names = list(distortion) if isinstance(distortion, (tuple, list)) else (["noise", "brightness", "blurring", "rotation", "scaling"] if distortion == "mixed" else str(distortion).split("+"))
+    for n in names:
+        if n not in KINDS:
+            raise ValueError(f"distortion {distortion!r}: {n!r} is none of none, noise, rotation, scaling, blurring, brightness")
+    if not names or len(set(names)) != len(names):
+        raise ValueError(f"distortion {distortion!r}: a mixed set names at least one kind, each once")
+    return tuple(sorted(names, key=KINDS.get))
 
 
 class _Distort(torch.autograd.Function):
@@ -74,19 +89,41 @@ class _DistortGeometry(torch.autograd.Function):
         return gx, None, None, None
 
 
+_M64 = (1 << 64) - 1
+
+
+def _mix64(z):
+    """splitmix64's finaliser"""
+    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & _M64
+    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & _M64
+    return z ^ (z >> 31)
+
+
+def _draw_key(seed, step):
+    return _mix64((int(seed) ^ (0x9E3779B97F4A7C15 * (int(step) + 1))) & _M64)
+
+
 def host_uniform(seed, step, lo, hi):
     """One U[lo, hi) draw as a pure function of (seed, step) -- splitmix64's finaliser, the generator the device-side draws use -- for the one parameter a
     captured loop needs on the HOST (the scaling factor: it decides which captured shape a step replays); the same on every rank."""
-    mask = (1 << 64) - 1
-
-    def mix(z):
-        z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & mask
-        z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & mask
-        return z ^ (z >> 31)
-
-    key = mix((int(seed) ^ (0x9E3779B97F4A7C15 * (int(step) + 1))) & mask)
-    u = (mix(key ^ mask) >> 40) / 16777216.0
+    u = (_mix64(_draw_key(seed, step) ^ _M64) >> 40) / 16777216.0
     return lo + (hi - lo) * u
+
+
+def kinds_mask(kinds):
+    """The bit mask of a set of kinds (names or codes): bit k = kind k."""
+    return sum(1 << (KINDS[k] if isinstance(k, str) else int(k)) for k in set(kinds))
+
+
+def host_selector(seed, step, mask):
+    """Which kind of the set `mask` (bit k = kind k) the mixed layer trains against at (seed, step): the host's statement of wm_distort_draw(6)'s selector --
+    the (floor(u n))-th of the n members in kind order, u a 24-bit word of a sequence of its own under the step's key.  A captured loop whose set holds
+    scaling asks it which captured width to replay; the same on every rank."""
+    mask = int(mask)
+    if mask <= 0 or mask >> 6:
+        raise ValueError(f"host_selector: the mask {mask:#x} is empty or holds bits beyond the kinds 0..5")
+    members = [k for k in range(6) if (mask >> k) & 1]
+    return members[((_mix64(_draw_key(seed, step) ^ 0xC2B2AE3D27D4EB4F) >> 40) * len(members)) >> 24]
 
 
 def scaled_width(W, sf):
@@ -95,7 +132,9 @@ def scaled_width(W, sf):
 
 
 class DistortionLayer:
-    """distortion: one of none | noise | brightness | blurring | rotation | scaling.
+    """distortion: one of none | noise | brightness | blurring | rotation | scaling -- or a SET of them (a tuple / list of names, "a+b+c", "mixed" = all five; "none"
+    may be a member): every step then draws one kind of the set uniformly and that kind's parameter as the single-kind layer does (no composition).  The kind
+    is a word in device memory (the native code 6: one captured step serves every kind); set_mixed(kind, ...) sets it from host values.
 
     draw(shape, device)              the eager loop's per-step draws: torch's generators, the calls the reference's libraries make (from generators of
                                      the layer's own, seeded with `seed`)
@@ -106,9 +145,18 @@ class DistortionLayer:
                                      other kinds when the decoder's fused first layer is not available)"""
 
     def __init__(self, distortion="none", seed=0):
-        if distortion not in KINDS:
+        self.mixed = isinstance(distortion, (tuple, list)) or (isinstance(distortion, str) and (distortion == "mixed" or "+" in distortion))
+        if self.mixed:
+            # A SET of kinds ("mixed": all five; a tuple / list of names; "a+b+c"; "none" may be a member): every step draws one of them uniformly, then that
+            # kind's parameter as the single-kind layer does.  param is the native parameter block (selector word, every kind's parameter at its own word);
+            # `selected` is the step's kind where the host knows it (draw, set_mixed, select_on_host) and None where only the device does (a captured step).
+            self.kinds = parse_kinds(distortion)
+            self.name = distortion if isinstance(distortion, str) else "+".join(self.kinds)
+            self.kind, self.seed, self.mask, self.selected = MIXED, int(seed), kinds_mask(self.kinds), None
+        elif distortion not in KINDS:
             raise ValueError(f"distortion {distortion!r}: choose from none, noise, rotation, scaling, blurring, brightness (main_nerf_wtmk.py:75)")
-        self.name, self.kind, self.seed = distortion, KINDS[distortion], int(seed)
+        else:
+            self.name, self.kind, self.seed = distortion, KINDS[distortion], int(seed)
         self.param = self.noise = None
         self.factor = 1.0             # scaling: this step's factor as the host knows it (it decides a shape)
         # generators of the layer's own, seeded alike on every rank: the decoder is replicated in a data-parallel run (it sees the all-gathered
@@ -122,28 +170,124 @@ class DistortionLayer:
 
     @property
     def fused(self):
-        """applied inside the fused decoder's first layer (dec_forward_train)"""
+        """applied inside the fused decoder's first layer (dec_forward_train).  mixed: code 6 reads the step's kind on the device -- except in a step the HOST knows
+        to be a scaling step (another decoder width, hence another capture): there the decoder runs plain, behind the resampling launch."""
+        if self.mixed:
+            return self.selected != 5
         return 1 <= self.kind <= 3
 
     @property
     def geometric(self):
-        """a resampling kernel of its own in front of the decoder (wm_distort_geom_fwd)"""
+        """a resampling kernel of its own in front of the decoder (wm_distort_geom_fwd).  mixed: the scaling launch in a scaling step, else the rotation launch
+        whenever the set holds rotation -- always enqueued, an exact copy at the (1, 0) an unselected rotation keeps."""
+        if self.mixed:
+            return self.selected == 5 or bool(self.mask >> 4 & 1)
         return self.kind >= 4
 
+    @property
+    def code(self):
+        """the native `distortion` argument of the fused kinds' entry points (mixed: 6, the set's mask and the block's image count in one word)"""
+        return self.kind if not self.mixed else MIXED | self.mask << 8 | ((self.param.numel() - ROTATION) // 2) << 16
+
+    @property
+    def geom_kind(self):
+        """which resampling the launch in front of the decoder is (4 | 5)"""
+        return self.kind if not self.mixed else (5 if self.selected == 5 else 4)
+
+    @property
+    def geom_param(self):
+        """the device parameter that launch reads (mixed: the factor's word / the rotation pairs of the block)"""
+        return self.param if not self.mixed else (self.param[SCALING:SCALING + 1] if self.selected == 5 else self.param[ROTATION:])
+
     def out_width(self, W):
+        if self.mixed:
+            return scaled_width(W, self.factor) if self.selected == 5 else int(W)
         return scaled_width(W, self.factor) if self.kind == 5 else int(W)
 
+    def _mixed_buffers(self, shape, device):
+        n = ROTATION + 2 * int(shape[0])
+        if n >= ROTATION + 2 * 65536:
+            raise ValueError("the mixed layer's native code carries the image count in 16 bits")
+        if self.param is None or self.param.device != device or self.param.numel() != n:
+            host = torch.zeros(n, dtype=torch.float32)
+            host[ROTATION::2] = 1.0       # an unselected rotation: (cos, sin) = (1, 0); selector word 0: "none" until the first draw
+            self.param = host.to(device)
+        if self.mask >> 1 & 1 and (self.noise is None or tuple(self.noise.shape) != tuple(shape) or self.noise.device != device):
+            self.noise = torch.zeros(tuple(shape), dtype=torch.float32, device=device)
+
     def _buffers(self, shape, device):
+        if self.mixed:
+            return self._mixed_buffers(shape, device)
         n = 2 * int(shape[0]) if self.kind == 4 else 1       # rotation: (cos, sin) per image
         if self.param is None or self.param.device != device or self.param.numel() != n:
             self.param = torch.zeros(n, dtype=torch.float32, device=device)
         if self.kind == 1 and (self.noise is None or tuple(self.noise.shape) != tuple(shape) or self.noise.device != device):
             self.noise = torch.zeros(tuple(shape), dtype=torch.float32, device=device)
 
+    def _draw_mixed(self, shape, device):
+        """The eager loops' draw of a mixed set: one torch.randint from the layer's host generator picks the kind, then that kind's own draw (the calls below)."""
+        kind = self.kinds[int(torch.randint(len(self.kinds), (1,), generator=self._host_gen))]
+        gen = self._host_gen
+        if kind == "noise":
+            if self._dev_gen is None or self._dev_gen.device != device:
+                self._dev_gen = torch.Generator(device=device).manual_seed(self.seed)
+            self.set_mixed(kind)
+            torch.normal(0.0, math.sqrt(0.1), size=tuple(shape), generator=self._dev_gen, device=device, out=self.noise)
+        elif kind == "brightness":
+            self.set_mixed(kind, factor=float(torch.empty(1).uniform_(0.5, 1.5, generator=gen)))
+        elif kind == "blurring":
+            self.set_mixed(kind, sigma=float(torch.empty(1).uniform_(0.01, 0.5, generator=gen)))
+        elif kind == "rotation":
+            self.set_mixed(kind, radians=[math.radians(float(torch.empty(1).uniform_(-30.0, 30.0, generator=gen))) for _ in range(int(shape[0]))])
+        elif kind == "scaling":
+            self.set_mixed(kind, scaling=torch.empty(1).uniform_(0.75, 1.25, generator=gen).item())
+        else:
+            self.set_mixed(kind)
+
+    def set_mixed(self, kind, factor=None, sigma=None, radians=None, scaling=None, noise=None):
+        """This step's kind of a mixed set and its parameter, from host values (tests, tools, the eager draw): the selector word and the kind's word(s) of the
+        device block; every rotation pair is (1, 0) unless rotation is the kind.  noise: a tensor copied into the noise buffer.  The buffers must exist (draw,
+        draw_on_device or _buffers has sized them)."""
+        if not self.mixed or kind not in self.kinds:
+            raise ValueError(f"set_mixed: {kind!r} is no member of {self.name!r}")
+        need = {"brightness": factor, "blurring": sigma, "rotation": radians, "scaling": scaling}
+        if kind in need and need[kind] is None:
+            raise ValueError(f"set_mixed: {kind} needs its parameter")
+        n_images = (self.param.numel() - ROTATION) // 2
+        # writes only (as set_rotation / set_scaling): nothing is read back from the device, so an eager loop's per-step draw does not wait for it
+        self.param[SELECTOR:SELECTOR + 1].view(torch.int32).fill_(KINDS[kind])
+        if kind == "brightness":
+            self.param[BRIGHTNESS:BRIGHTNESS + 1].fill_(float(factor))
+        elif kind == "blurring":
+            self.param[SIGMA:SIGMA + 1].fill_(float(sigma))
+        elif kind == "scaling":
+            self.factor = float(scaling)
+            self.param[SCALING:SCALING + 1].fill_(self.factor)
+        if kind == "rotation":
+            if len(radians) != n_images:
+                raise ValueError(f"set_mixed: rotation takes one angle per image ({n_images})")
+            pairs = torch.tensor([[math.cos(a), math.sin(a)] for a in radians], dtype=torch.float32).reshape(-1)
+        else:
+            pairs = torch.tensor([1.0, 0.0]).repeat(n_images)
+        self.param[ROTATION:].copy_(pairs)
+        if noise is not None:
+            self.noise.copy_(noise)
+        self.selected = KINDS[kind]
+
+    def select_on_host(self, step):
+        """The kind the device draws at `step` (host_selector) -- and, for scaling, its factor (host_uniform) -- as host values: what decides which captured
+        shape a loop replays, and what out_width / fused / geometric answer afterwards.  Returns the kind's code."""
+        self.selected = host_selector(self.seed, step, self.mask)
+        if self.selected == 5:
+            self.factor = host_uniform(self.seed, step, 0.75, 1.25)
+        return self.selected
+
     def draw(self, shape, device):
         if not self.native:
             return
         self._buffers(shape, device)
+        if self.mixed:
+            return self._draw_mixed(shape, device)
         if self.kind == 1:        # utils_wtmk_disen.py:555: torch.normal(0, sqrt(0.1), size=pred_rgb.shape, device=pred_rgb.device)
             if self._dev_gen is None or self._dev_gen.device != device:
                 self._dev_gen = torch.Generator(device=device).manual_seed(self.seed)
@@ -172,6 +316,10 @@ class DistortionLayer:
         if self.kind == 5:
             raise NotImplementedError("the scaling factor decides the decoder's input width: it is drawn by the host (host_uniform, set_scaling)")
         self._buffers(shape, device)
+        if self.mixed:      # one call: the selector, then the selected kind's parameter (a scaling step's factor too: the word host_uniform gives the host)
+            nv.call("wm_distort_draw", self.code, self.seed, nv.ptr(step_counter), 0 if self.noise is None else self.noise.numel(), nv.ptr(self.param),
+                    nv.ptr(self.noise), nv.stream())
+            return
         n = self.noise.numel() if self.kind == 1 else (int(shape[0]) if self.kind == 4 else 0)
         nv.call("wm_distort_draw", self.kind, self.seed, nv.ptr(step_counter), n, nv.ptr(self.param), nv.ptr(self.noise), nv.stream())
 
@@ -179,6 +327,16 @@ class DistortionLayer:
         """pred_rgb: clamped blocks [B, H, W, 3].  raw: the unclamped render (native kinds back-propagate through the clamp themselves)."""
         if self.name == "none":
             return pred_rgb
+        if self.mixed:
+            if not pred_rgb.is_cuda:      # the selected kind's stock operators (the host knows the kind: draw / set_mixed / select_on_host)
+                name = NAMES[self.selected]
+                param = {"brightness": self.param[BRIGHTNESS:BRIGHTNESS + 1], "blurring": self.param[SIGMA:SIGMA + 1], "rotation": self.param[ROTATION:],
+                         "scaling": self.factor}.get(name)
+                return pred_rgb if name == "none" else reference_ops(pred_rgb, name, param, self.noise)
+            x = pred_rgb if raw is None else raw
+            if self.geometric:
+                x = _DistortGeometry.apply(x, self.geom_kind, self.geom_param, self.out_width(pred_rgb.shape[2]))[0]
+            return _Distort.apply(x, self.code, self.param, self.noise) if self.fused else x
         if not pred_rgb.is_cuda:
             return reference_ops(pred_rgb, self.name, self.param if self.kind != 5 else self.factor, self.noise)
         if self.geometric:

@@ -129,7 +129,7 @@ class _FusedDecoder(torch.autograd.Function):
                     raise ValueError("bce: message must be a contiguous float32 device tensor with one entry per image")
                 seed = torch.empty(B, dtype=torch.float32, device=img.device)
             nv.call("dec_forward_train", nv.ptr(img), mean, std, nv.ptr_array(ps), B, Cin, H, W, eps, nv.ptr(ws), nv.ptr(out), nv.ptr(clamped),
-                    dist.kind if dist is not None else 0, nv.ptr(dist.param) if dist is not None else None, nv.ptr(dist.noise) if dist is not None else None,
+                    dist.code if dist is not None else 0, nv.ptr(dist.param) if dist is not None else None, nv.ptr(dist.noise) if dist is not None else None,
                     nv.ptr(msg) if bce is not None else None, float(temp) if bce is not None else 0.0, float(scale) if bce is not None else 0.0, nv.ptr(seed),
                     nv.stream())
             _FusedDecoder.seed = None if seed is None else seed.view(B, 1)      # (the caller takes it right behind this call: trainer.train_step)
@@ -172,9 +172,9 @@ class _FusedDecoder(torch.autograd.Function):
                 t.record_stream(side)
         if ctx.dist is not None:     # (the draws in its buffers are still this step's: they are refreshed at the head of the next one)
             d = ctx.dist
-            scratch = torch.empty_like(img) if d.kind == 3 else None
+            scratch = torch.empty_like(img) if d.kind == 3 or d.mixed else None      # (mixed: the gradient always goes through the scratch image)
             nv.call("dec_backward_train", nv.ptr(grad_out.contiguous().view(-1)), nv.ptr(img), mean, std, nv.ptr_array(ps), B, Cin, H, W, nv.ptr(ws),
-                    nv.ptr_array(grads), nv.ptr(grad_img), d.kind, nv.ptr(d.param), nv.ptr(d.noise), nv.ptr(scratch), nv.stream(),
+                    nv.ptr_array(grads), nv.ptr(grad_img), d.code, nv.ptr(d.param), nv.ptr(d.noise), nv.ptr(scratch), nv.stream(),
                     nv.stream() if side is None else side.cuda_stream)
         else:
             nv.call("dec_backward", nv.ptr(grad_out.contiguous().view(-1)), nv.ptr(img), int(rendered), mean, std, nv.ptr_array(ps), B, Cin, H, W,
@@ -254,8 +254,9 @@ class HiddenDecoder_multi_views(nn.Module):
         if fused is not None and geometric:
             # rotation / scaling: one resampling launch in front of the chain; its output lies in [0, 1], so the first layer's clamp is the identity
             from .distortion import _DistortGeometry
-            resampled, pred = _DistortGeometry.apply(image, distortion.kind, distortion.param, width)
-            return _FusedDecoder.apply(resampled, fused[0], True, None, bce, *fused[1])[0], pred
+            resampled, pred = _DistortGeometry.apply(image, distortion.geom_kind, distortion.geom_param, width)
+            # (a mixed set: the chain still applies whichever of its fused kinds the step drew -- to an exact copy of the clamped blocks, the unselected rotation)
+            return _FusedDecoder.apply(resampled, fused[0], True, distortion if distortion.fused else None, bce, *fused[1])[0], pred
         if fused is not None:
             return _FusedDecoder.apply(image, fused[0], True, distortion if (distortion is not None and distortion.fused) else None, bce, *fused[1])
         pred = torch.clamp(image, min=0, max=1)

@@ -217,6 +217,12 @@ def test_bitacc(stage, n_messages=200, seed=4321, distortion="none", message_bat
 test_bitacc.__test__ = False
 
 
+def robustness(stage, kinds=("none", "noise", "brightness", "blurring", "rotation", "scaling"), n_messages=200, seed=4321, message_batch=None):
+    """{kind: bit accuracy} of the stage's model with the evaluated blocks under each distortion in turn (test_bitacc with the same messages and the same
+    evaluation seed for every kind): what a model trained against one kind, a mixed set or none keeps under each attack."""
+    return {kind: test_bitacc(stage, n_messages, seed, distortion=kind, message_batch=message_batch)[0] for kind in kinds}
+
+
 def test_views(stage, seed=9876, max_ray_batch=4096):
     """Trainer.test_image's loop (:816-933) as a generator of (pred, truth) [1, H, W, 3]: per test view a random message and
     eval_step(render_whole=True) -- the full view staged in max_ray_batch chunks -- beside the clean view."""

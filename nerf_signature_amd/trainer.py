@@ -234,7 +234,7 @@ def train_step(model, data, message, render_kwargs, lambda_w=1.0, lambda_i=1.0, 
             main.wait_stream(side_stream)
             new_segment = True
         image = dp.gather_blocks(image, wm["rays_o_block"].shape[0], shard[0])
-    if isinstance(distortion, str):
+    if isinstance(distortion, (str, tuple, list)):
         distortion = DistortionLayer(distortion) if distortion != "none" else None
         if distortion is not None:
             distortion.draw(tuple(image.shape), image.device)
@@ -318,8 +318,12 @@ def reference_trainer_train_step(self, data, message):
     layer = None
     if kind != "none":
         layer = self.__dict__.get("_nsig_distortion_layer")
-        if layer is None or layer.name != kind:
+        # (kept while the Trainer asks for the same thing: a tuple / list is a new object every time it is rebuilt, so it is compared by value with what the layer
+        #  was made from -- a layer rebuilt every step would re-seed its generator and draw the same kind and parameter for ever)
+        asked = tuple(kind) if isinstance(kind, (tuple, list)) else kind
+        if layer is None or self.__dict__.get("_nsig_distortion_asked") != asked:
             layer = self.__dict__["_nsig_distortion_layer"] = DistortionLayer(kind)
+            self.__dict__["_nsig_distortion_asked"] = asked
         o = data["watermark"]["rays_o_block"]
         layer.draw(tuple(o.shape), o.device)
     name = getattr(self.opt, "loss_w", "bce")
@@ -348,7 +352,7 @@ def eval_step(model, data, message, render_kwargs, render_whole=True, lambda_w=1
     if not render_whole:
         out = model.render(data["rays_o_block"], data["rays_d_block"], message, staged=False, bg_color=1, perturb=False, force_all_rays=True, **kw)
         pred_rgb, pred_depth = torch.clamp(out["image"], min=0, max=1), out["depth"]
-        if isinstance(distortion, str):
+        if isinstance(distortion, (str, tuple, list)):
             distortion = DistortionLayer(distortion) if distortion != "none" else None
         pred_rgb_dist = pred_rgb
         if distortion is not None:
@@ -381,7 +385,7 @@ def eval_blocks_multi(model, data, messages, render_kwargs, distortion=None):
     Returns (pred_rgb [K, D, bh, bw, 3], decoded [K, D, 1]): slice k is what eval_step returns for messages[k] when the K calls are made in this order."""
     out = model.render(data["rays_o_block"], data["rays_d_block"], messages, staged=False, bg_color=1, perturb=False, force_all_rays=True, **dict(render_kwargs))
     pred_rgb = torch.clamp(out["image"], min=0, max=1)
-    if isinstance(distortion, str):
+    if isinstance(distortion, (str, tuple, list)):
         distortion = DistortionLayer(distortion) if distortion != "none" else None
     decoded = []
     for k in range(pred_rgb.shape[0]):
@@ -565,6 +569,12 @@ class GraphedWatermarkLoop:
         at the head of its own step on the side stream: next to the optimiser as well, the two marches took longer than the
         optimiser and the pre-sum lost its cover."""
         self.distortion = None if distortion in (None, "none") else (distortion if isinstance(distortion, DistortionLayer) else DistortionLayer(distortion, distortion_seed))
+        # A mixed set (DistortionLayer of several kinds): which kind a replay trains against is drawn on the device (wm_distort_draw(6): a word the decoder's first
+        # launch and the one adjoint launch read), so ONE capture serves every kind -- except scaling, whose factor sets the decoder's width: a set that holds it
+        # keeps the single-kind loop's one capture per width beside the unscaled one, and step() asks the host's statement of the same draw
+        # (DistortionLayer.select_on_host at the count the replay's draw will see) which of them to replay.
+        self._mixed = self.distortion is not None and self.distortion.mixed
+        self._mixed_scaling = self._mixed and "scaling" in self.distortion.kinds
         # fixed_blocks (off by default): the watermark-block rays are one pair of tensors per dataset
         # (nerf/provider_wtmk.py:442-494) and everything their field pass reads except the codebook is frozen in this stage, so the
         # loop marches them ONCE, keeps the base-level feature planes and the scatter plan (NeRFNetwork.fix_rays / fieldops.FixedPoints)
@@ -709,8 +719,8 @@ class GraphedWatermarkLoop:
                     self.stage_width, nv.ptr(self.stage_counter), nv.ptr(self.msg_all), nv.stream())
         else:
             self.sink.zero_()
-            if self.content_sampler is not None and torch.cuda.is_current_stream_capturing():
-                self.stage_counter += 1      # (the opening kernel counts the replays when it stages the message)
+            if (self.content_sampler is not None or self._mixed) and torch.cuda.is_current_stream_capturing():
+                self.stage_counter += 1      # (the opening kernel counts the replays when it stages the message; a mixed layer's host mirror counts on it)
         if self.content_sampler is not None:
             ct = self.data["content"]
             self.content_sampler.sample_into(self.stage_counter, ct["rays_o"], ct["rays_d"], ct.get("images"))      # (no "images": online targets, see train_step)
@@ -883,6 +893,8 @@ class GraphedWatermarkLoop:
             o = self.data["watermark"]["rays_o_block"]
             self.distortion._buffers(tuple(o.shape), o.device)
             self.distortion.set_scaling(host_uniform(self.distortion.seed, self._replays, 0.75, 1.25))
+        if self._mixed:
+            self.distortion.selected = None      # the warm-up and the unscaled capture: the kind is the device's to draw
         beside = self.side_stream is not None
         self.content_backward_first = beside
         self.weights_stream = self.side_stream if not beside else (getattr(self, "_own_weights_stream", None) or torch.cuda.Stream())
@@ -922,6 +934,18 @@ class GraphedWatermarkLoop:
             for w in sorted(a_factor_of):
                 self.distortion.set_scaling(a_factor_of[w])
                 self.variants[w] = self._capture(cap_block, cap_content)
+        elif self._mixed_scaling:
+            # the unscaled capture (key W: the device-side selector decides among the other kinds; a scaling step whose width is W is the operator's plain copy,
+            # which is what this capture computes when the selector names no fused kind), then one per other width with the host-known scaling step set
+            W = self.data["watermark"]["rays_o_block"].shape[2]
+            a_factor_of = {scaled_width(W, f): f for f in (0.75 + 0.5 * i / 4096.0 for i in range(4096))}
+            self.distortion.selected = None
+            self.variants[W] = self._capture(cap_block, cap_content)
+            for w in sorted(a_factor_of):
+                if w != W:
+                    self.distortion.selected, self.distortion.factor = 5, a_factor_of[w]
+                    self.variants[w] = self._capture(cap_block, cap_content)
+            self.distortion.selected = None
         else:
             self.variants[None] = self._capture(cap_block, cap_content)
         self._select(next(iter(self.variants)))
@@ -1009,6 +1033,10 @@ class GraphedWatermarkLoop:
         if self.distortion is not None and self.distortion.name == "scaling":      # this step's factor (host-side draw) and the capture of its width
             self.distortion.set_scaling(host_uniform(self.distortion.seed, self._replays, 0.75, 1.25))
             self._select(self.distortion.out_width(self.data["watermark"]["rays_o_block"].shape[2]))
+        elif self._mixed:      # the kind this replay's device-side draw will select (its opening kernel advances the count first): a scaling step replays its width's capture
+            self.distortion.select_on_host(self._replays + 1)
+            if self._mixed_scaling:
+                self._select(self.distortion.out_width(self.data["watermark"]["rays_o_block"].shape[2]))
         self.selected.replay()
         self.steps_done += 1
         if self.opt_shard is not None:
