@@ -854,6 +854,53 @@ size_t im_ssim_scratch_bytes(uint32_t B, uint32_t H, uint32_t W, uint32_t C);
 int im_ssim(const float *pred, const float *truth, uint32_t B, uint32_t H, uint32_t W, uint32_t C, const float *extrema, float data_range,
             void *scratch, double *ssim, float *map, nsig_stream_t stream);
 
+/* ------------------------------------------------------------------ model tampering */
+
+/*
+ * What a holder of a released model's weights (nerf_signature_amd/release.py: 16 base tables, the signature table, the two MLP vectors) can do to
+ * them, on the device, for measuring how many signature bits survive (nerf_signature_amd/tamper.py; this project's own evaluation -- the reference
+ * has no live counterpart).  Every entry point takes a tensor list in the convention of opt_adam_dense_host / opt_ema_update: host arrays of device
+ * pointers (fp32, dense) and numel_host, any n >= 1, launched in groups of at most 32 tensors; a tensor of 0 elements is legal and ignored (its
+ * pointer is not looked at).  Nothing is allocated, no device value is read on the host, every launch is stream-ordered (capturable).  No float
+ * atomics; the select's histograms use integer atomics, whose sums do not depend on the order: the same inputs give the same bits everywhere.
+ * scratch: tm_scratch_bytes(n) bytes for a list of n tensors (0 for n = 0), 16-byte aligned, need not be initialised; tm_stats and tm_abs_kth may
+ * share it (they use different parts).
+ *
+ * tm_stats: stats (device, [n][4] double) = per tensor min, max, mean and unbiased standard deviation of its FINITE elements (non-finite ones are
+ * skipped), accumulated in double, the deviation in a second pass about the mean; fixed reduction shape (two runs: identical bits).  A tensor
+ * without a finite element gets 0, 0, 0, 0; one finite element: deviation 0.
+ *
+ * tm_abs_kth: *threshold_bits (device) = the exact k-th smallest magnitude (k 1-based, 1 .. the total count) over ALL listed values together, as
+ * the bit pattern bits & 0x7fffffff -- monotone in |x|; NaN magnitudes order above infinity, as their bits do -- and *count_le (device) = how many
+ * values have a magnitude not above it (>= k; more when values tie).  Radix select in three passes over the data (bits 30..20, 19..10, 9..0): per-
+ * workgroup LDS histograms merged into a global one, a one-workgroup launch between passes that leaves prefix and remaining rank on the device.
+ * No sort, no copy of the data.
+ *
+ * tm_apply: dst[i][j] = f(src[i][j]) in one pass; src == dst (per tensor) is allowed, any other overlap is not.  Every operation is fp32 and
+ * rounded on its own (no contraction), in the order written:
+ *   NSIG_TAMPER_PRUNE     y = ((bits of x) & 0x7fffffff) <= *threshold_bits ? +0.0f : x            (threshold_bits: device, tm_abs_kth's)
+ *   NSIG_TAMPER_NOISE     y = x + s_i * z(seed, i, j), s_i = (float)((double)strength * stats[i][3])   (stats: device, tm_stats'), z a unit normal:
+ *                           mix64(v): v = (v ^ v >> 30) * 0xBF58476D1CE4E5B9; v = (v ^ v >> 27) * 0x94D049BB133111EB; v ^ v >> 31     (64-bit, wrapping)
+ *                           key_i = mix64(seed ^ 0x9E3779B97F4A7C15 * (i + 1));  h = mix64(key_i + 0xD1B54A32D192ED03 * (j + 1))
+ *                           u1 = ((float)(h >> 40) + 1.0f) * 2^-24 in (0, 1];  u2 = (float)((h >> 8) & 0xFFFFFF) * 2^-24 in [0, 1)
+ *                           z = sqrtf(-2.0f * logf(u1)) * cosf(6.28318530717958648f * u2)                    (Box-Muller; |z| <= sqrt(48 ln 2) < 5.77)
+ *                         i is the tensor's index in the list, j the element's in the tensor
+ *   NSIG_TAMPER_QUANTIZE  b = bits in 2 .. 16: lo = (float)stats[i][0], hi = (float)stats[i][1], L = 2^b - 1, step = (hi - lo) / L,
+ *                         q = min(L, max(0, rintf((x - lo) / step))), y = lo + q * step; a tensor with hi == lo and a non-finite x pass through
+ *   NSIG_TAMPER_HALF      y = (float)(_Float16)x                                                   (round to nearest even; above 65504: infinity)
+ * strength: finite and >= 0 for every kind (read by NOISE only); bits, threshold_bits, stats, seed are read by the kinds that name them.
+ */
+#define NSIG_TAMPER_PRUNE 0u
+#define NSIG_TAMPER_NOISE 1u
+#define NSIG_TAMPER_QUANTIZE 2u
+#define NSIG_TAMPER_HALF 3u
+size_t tm_scratch_bytes(uint32_t n);
+int tm_stats(const float *const *src_host, const uint32_t *numel_host, uint32_t n, double *stats, void *scratch, nsig_stream_t stream);
+int tm_abs_kth(const float *const *src_host, const uint32_t *numel_host, uint32_t n, uint64_t k, uint32_t *threshold_bits, uint64_t *count_le,
+               void *scratch, nsig_stream_t stream);
+int tm_apply(const float *const *src_host, float *const *dst_host, const uint32_t *numel_host, uint32_t n, uint32_t kind, float strength, uint32_t bits,
+             const uint32_t *threshold_bits, const double *stats, uint64_t seed, nsig_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -186,6 +186,25 @@ def field_forward(xyzs, dirs, bound, base_tables, S, packed, want_rgb=True, want
     return sigmas, rgbs, geo, masks
 
 
+@torch.no_grad()
+def field_rows_runner(capacity, bound, base_tables, S, packed):
+    """The field pass of the device-controlled eval loop (renderer._eval_loop_on_device) over the base tables and ONE pre-sum S (or None): returns
+    fn(xyzs, dirs, rows_dev, sigmas, rgbs) that evaluates the first *rows_dev rows (a device count) with launches sized for `capacity`."""
+    base = [_check_table(t.detach(), "base table") for t in base_tables]
+    base_ptrs = nv.ptr_array(base)
+    use_planes = capacity >= PLANES_MIN_POINTS
+    ws = torch.empty(int(nv.fn("hg_planes_bytes")(capacity)), dtype=torch.uint8, device=packed.device) if use_planes else None
+    bound = float(bound)
+
+    def run(xyzs, dirs, rows_dev, sigmas, rgbs):
+        layout = encode_planes(xyzs, capacity, bound, base_ptrs, S, ws, rows_dev) if use_planes else PLANES_F32
+        nv.call("field_fwd_rows", nv.ptr(xyzs), nv.ptr(dirs), capacity, nv.ptr(rows_dev), bound, base_ptrs, nv.ptr(S), nv.ptr(packed), nv.ptr(sigmas),
+                nv.ptr(rgbs), nv.ptr(ws), layout, nv.stream())
+        run.keep = (base, S, packed, ws)      # (the launches above hold raw addresses)
+
+    return run
+
+
 MULTI_MAX_MESSAGES = 16      # include/nerfsig.h NSIG_MULTI_MAX_MESSAGES: the largest K of one multi-message launch
 
 

@@ -223,6 +223,37 @@ def robustness(stage, kinds=("none", "noise", "brightness", "blurring", "rotatio
     return {kind: test_bitacc(stage, n_messages, seed, distortion=kind, message_batch=message_batch)[0] for kind in kinds}
 
 
+MODEL_ATTACKS = (tuple(("prune", p) for p in (0.1, 0.3, 0.5, 0.7, 0.9)) + tuple(("noise", s) for s in (0.01, 0.03, 0.1, 0.3, 1.0))
+                 + tuple(("quantize", b) for b in (16, 8, 6, 4)) + (("half", 0),))
+
+
+@torch.no_grad()
+def model_robustness(stage, message, attacks=MODEL_ATTACKS, seeds=(0,), view=0):
+    """What survives an attack on the released WEIGHTS (robustness() above attacks the rendered image): stage['model'] is released under `message`
+    (release.release, a copy), the key is built from the stage's block rays, and for every (kind, strength) of `attacks` -- noise once per seed of `seeds`,
+    the other kinds are deterministic: seed 0 -- the 16 base tables, the signature table and both MLP vectors are tampered from their pristine copy
+    (tamper.Tamper), the key is verified (release.verify) and held-out view `view` is rendered and compared with the untampered release's (metrics.psnr:
+    an attack that destroys the picture is not an attack on the watermark; +inf where the render is bit-equal).
+    -> {(kind, strength, seed): {"bit_accuracy", "matches", "p_value", "psnr"}}.  The stage's model is left untouched."""
+    from . import metrics, release as rel
+    model, dev, H, W = stage["model"], stage["device"], stage["H"], stage["W"]
+    released = rel.release(model, message, copy=True)
+    key = rel.SignatureKey.from_block_rays(message, model.msg_decoder, stage["block_o"], stage["block_d"], stage["render_kwargs"])
+    r = rays.get_rays(stage["test_poses"][view:view + 1], stage["intr"], H, W, -1)
+    full = lambda: released.render(r["rays_o"], r["rays_d"], staged=True, bg_color=1, perturb=False, force_all_rays=True, **stage["render_kwargs"])["image"] \
+        .reshape(1, H, W, 3).clamp(0, 1)
+    truth = full()
+    tamper = released.tamper()
+    out = {}
+    for kind, strength in attacks:
+        for seed in (seeds if kind == "noise" else (0,)):
+            tamper.apply(kind, strength, seed=seed)
+            v = rel.verify(released, key)
+            out[(kind, strength, seed)] = {"bit_accuracy": v["bit_accuracy"], "matches": v["matches"], "p_value": v["p_value"], "psnr": float(metrics.psnr(full(), truth))}
+    tamper.restore()
+    return out
+
+
 def test_views(stage, seed=9876, max_ray_batch=4096):
     """Trainer.test_image's loop (:816-933) as a generator of (pred, truth) [1, H, W, 3]: per test view a random message and
     eval_step(render_whole=True) -- the full view staged in max_ray_batch chunks -- beside the clean view."""
