@@ -26,6 +26,7 @@
 #include <algorithm>
 #include <cstring>
 
+#include "distortion.h"
 #include "wave.h"
 
 namespace nsig {
@@ -62,74 +63,17 @@ struct DecWs {
 
 // How the image reaches layer 0.  mode 0: [B][Cin][H][W], used as it is.  mode 1: the rendered blocks [B][H][W][Cin] straight
 // from the compositor; clamp to [0,1] and (x - mean_c)/std_c (utils_wtmk_disen.py:599-601: torch.clamp, permute, normalize_img)
-// are applied on load, and their backward in the image-gradient epilogue.
+// are applied on load, and their backward in the image-gradient epilogue -- with the training step's distortion layer (distortion.h; mode 1 only)
+// between the clamp and the normalisation.
 struct DecInput {
     uint32_t mode;
     float mean[8], istd[8];
-    // The distortion layer of the training step (Trainer.distortion_layer, utils_wtmk_disen.py:551-577, applied at :594 between the clamp and the
-    // normalisation; mode 1 only).  0 none; 1 noise: x + noise[b][y][x][c] (the reference draws N(0, 0.1) per element); 2 brightness: clamp(f * x, 0, 1)
-    // (torchvision ColorJitter(brightness=0.5): ONE factor f in [0.5, 1.5] per call, blended against black); 3 blurring: the 3x3 Gaussian of
-    // torchvision GaussianBlur(3, sigma in [0.01, 0.5]) -- taps exp(-0.5 (d / sigma)^2), d in {-1, 0, 1}, normalised, reflect padding.
-    // f / sigma are read from dparam[0] ON THE DEVICE (so a captured step can draw them itself), the noise from dnoise.
-    // 6 mixed (distort = 6 | the set's mask << 8): the kind itself is a word in device memory -- dparam is the block of include/nerfsig.h (selector, then every kind's parameter at its own
-    // word), read once per call of distorted_value (the same word for every lane: a scalar load), after which the selected kind's statements run.
-    uint32_t distort, H, W;
-    const float *dparam, *dnoise;
+    Distortion dist;
 };
-enum : uint32_t { kDistNone = 0, kDistNoise = 1, kDistBrightness = 2, kDistBlur = 3, kDistRotation = 4, kDistScaling = 5, kDistMixed = NSIG_DISTORT_MIXED };
-constexpr uint32_t kDistAllKinds = 0x3Fu;      // the bits a mixed set's mask may hold: one per kind 0..5
 
-// this step's kind.  `code` = 6 | mask << 8 (the host checked what every member of the mask needs: a noise tensor, two pixels for the blur), so a selector
-// word that names no member of the set -- a block nobody has drawn into yet -- reads as "none" instead of reaching for a buffer that may not be there
-__device__ inline uint32_t mixed_selector(uint32_t code, const float *__restrict__ block) {
-    const uint32_t sel = reinterpret_cast<const uint32_t *>(block)[NSIG_MIXED_SELECTOR];
-    return (sel <= kDistScaling && ((code >> (8 + sel)) & 1u)) ? sel : (uint32_t)kDistNone;
-}
-// the word of the block where `kind` keeps what the single-kind code reads as dparam[0]
-__device__ inline uint32_t mixed_param_word(uint32_t kind) {
-    return kind == kDistBrightness ? NSIG_MIXED_BRIGHTNESS : (kind == kDistBlur ? NSIG_MIXED_SIGMA : (kind == kDistScaling ? NSIG_MIXED_SCALING : NSIG_MIXED_ROTATION));
-}
-
-__device__ inline float clamp01(float v) { return fminf(fmaxf(v, 0.0f), 1.0f); }
-__device__ inline int reflect1(int i, int n) { return i < 0 ? -i : (i >= n ? 2 * n - 2 - i : i); }   // torch 'reflect' padding by one (n >= 2)
-// side weight a and centre weight b of the normalised 1-d kernel [a, b, a]
-__device__ inline void blur_taps(float sigma, float &a, float &b) {
-    const float e = __expf(-0.5f / (sigma * sigma));
-    b = 1.0f / (1.0f + 2.0f * e);
-    a = e * b;
-}
-// the distorted value of channel c at pixel pix of image im, from the rendered blocks [B][H][W][Cin] (before the normalisation)
-__device__ inline float distorted_value(const float *__restrict__ img, const DecInput &in, uint32_t im, uint32_t c, uint32_t pix, uint32_t Cin, uint32_t P) {
-    const float *base = img + (size_t)im * P * Cin + c;
-    uint32_t kind = in.distort;
-    const float *dparam = in.dparam;
-    if ((kind & 0xFFu) == kDistMixed) {      // this step's kind and its parameter's word: from here on the single kind's statements (4, 5, 0: the clamped value)
-        kind = mixed_selector(kind, in.dparam);
-        dparam = in.dparam + mixed_param_word(kind);
-    }
-    if (kind == kDistBlur) {
-        float a, b;
-        blur_taps(dparam[0], a, b);
-        const int y = (int)(pix / in.W), x = (int)(pix - (uint32_t)y * in.W);
-        float acc = 0.0f;
-#pragma unroll
-        for (int dy = -1; dy <= 1; ++dy) {
-            const int yy = reflect1(y + dy, (int)in.H);
-            float row = 0.0f;
-#pragma unroll
-            for (int dx = -1; dx <= 1; ++dx) row += (dx == 0 ? b : a) * clamp01(base[(size_t)(yy * (int)in.W + reflect1(x + dx, (int)in.W)) * Cin]);
-            acc += (dy == 0 ? b : a) * row;
-        }
-        return acc;
-    }
-    const float x = clamp01(base[(size_t)pix * Cin]);
-    if (kind == kDistNoise) return x + in.dnoise[((size_t)im * P + pix) * Cin + c];
-    if (kind == kDistBrightness) return clamp01(dparam[0] * x);
-    return x;
-}
 __device__ inline float input_value(const float *__restrict__ img, const DecInput &in, uint32_t im, uint32_t c, uint32_t pix, uint32_t Cin, uint32_t P) {
     if (in.mode == 0) return img[((size_t)im * Cin + c) * P + pix];
-    return (distorted_value(img, in, im, c, pix, Cin, P) - in.mean[c]) * in.istd[c];
+    return (distorted_value(img, in.dist, im, c, pix, Cin, P) - in.mean[c]) * in.istd[c];
 }
 
 struct DecParams {
@@ -818,17 +762,10 @@ __global__ void __launch_bounds__(kT) k_dec_conv(int layer, DecParams prm, DecWs
                     } else {   // through the normalisation and the clamp (gradient passes where 0 <= x <= 1, as torch.clamp)
                         const size_t e = ((size_t)im * g.P + qo) * g.Cin + c;
                         const float x = img[e];
-                        float gy = acc[r] * inp.istd[c];          // d loss / d (distorted value)
-                        if (inp.distort >= kDistBlur) {           // the blur's adjoint needs the neighbours' gradients: k_dec_blur_adjoint finishes the job
-                                                                  // (mixed, 6: whichever kind the step drew, k_dec_blur_adjoint<true> does; 4, 5 never reach the chain)
-                            grad_img[e] = gy;
-                        } else {
-                            if (inp.distort == kDistBrightness) {
-                                const float f = inp.dparam[0], fx = f * clamp01(x);
-                                gy = (fx >= 0.0f && fx <= 1.0f) ? gy * f : 0.0f;
-                            }
-                            grad_img[e] = (x >= 0.0f && x <= 1.0f) ? gy : 0.0f;
-                        }
+                        const float gy = acc[r] * inp.istd[c];          // d loss / d (distorted value)
+                        // the blur's adjoint needs the neighbours' gradients, and a mixed set's (6) kind is the device's to know: k_distort_adjoint finishes
+                        // both from the scratch image this leaves (4, 5 never reach the chain); every other single kind is finished here
+                        grad_img[e] = inp.dist.code >= kDistBlur ? gy : pointwise_adjoint(inp.dist.code, inp.dist.param, x, gy);
                     }
                 }
             }
@@ -1513,245 +1450,8 @@ NSIG_EXPORT int dec_workspace_layout(uint32_t B, uint32_t Cin, uint32_t H, uint3
     return 0;
 }
 
-// grad_img (through the clamp) = clamp mask x the transposed blur of gy: gx[p] = sum over the (q, tap) whose reflected source is p of k[tap] * gy[q].
-// One thread per (image, pixel, channel); the 3 x 3 outputs q around p are visited and each one's taps re-reflected.
-//
-// kMixed (distortion 6, `code` = 6 | mask << 8, dparam = the parameter block): the mixed layer's adjoint, one launch whatever the step drew -- the selector is
-// read first (the same word for every thread) and the selected kind's adjoint applied to gy (the scratch image the epilogue left, or wm_distort_bwd's
-// grad_out): blurring, the statements below with the block's sigma; brightness, the factor where f * clamp(x) stays inside [0, 1] (k_distort_bwd's
-// statements); noise, none and the geometric kinds (whose resampling is a launch of its own), the identity.  Then the clamp mask, as for every kind.
-template <bool kMixed>
-__global__ void __launch_bounds__(256) k_dec_blur_adjoint(const float *__restrict__ gy, const float *__restrict__ img, const float *__restrict__ dparam, uint32_t B,
-                                                          uint32_t H, uint32_t W, uint32_t Cin, float *__restrict__ grad_img, uint32_t code) {
-    const uint32_t i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= B * H * W * Cin) return;
-    if constexpr (kMixed) {
-        const uint32_t kind = mixed_selector(code, dparam);
-        if (kind != kDistBlur) {
-            const float x = img[i];
-            float g = gy[i];
-            if (kind == kDistBrightness) {
-                const float f = dparam[NSIG_MIXED_BRIGHTNESS], fx = f * clamp01(x);
-                g = (fx >= 0.0f && fx <= 1.0f) ? g * f : 0.0f;
-            }
-            grad_img[i] = (x >= 0.0f && x <= 1.0f) ? g : 0.0f;
-            return;
-        }
-    }
-    const uint32_t c = i % Cin, pix = (i / Cin) % (H * W), im = i / (Cin * H * W);
-    const int y = (int)(pix / W), x = (int)(pix % W);
-    float a, b;
-    blur_taps(dparam[kMixed ? NSIG_MIXED_SIGMA : 0], a, b);
-    float acc = 0.0f;
-    for (int qy = y - 2; qy <= y + 2; ++qy) {
-        if (qy < 0 || qy >= (int)H) continue;
-        float wy = 0.0f;          // total weight with which output row qy reads input row y (reflection can map two taps onto it)
-        for (int dy = -1; dy <= 1; ++dy)
-            if (reflect1(qy + dy, (int)H) == y) wy += dy == 0 ? b : a;
-        if (wy == 0.0f) continue;
-        for (int qx = x - 2; qx <= x + 2; ++qx) {
-            if (qx < 0 || qx >= (int)W) continue;
-            float wx = 0.0f;
-            for (int dx = -1; dx <= 1; ++dx)
-                if (reflect1(qx + dx, (int)W) == x) wx += dx == 0 ? b : a;
-            if (wx != 0.0f) acc += wy * wx * gy[((size_t)im * H * W + (size_t)qy * W + qx) * Cin + c];
-        }
-    }
-    const float v = img[i];
-    grad_img[i] = (v >= 0.0f && v <= 1.0f) ? acc : 0.0f;
-}
-
-// The step's random draws, counter-based: everything is a function of (seed, *step, element) -- a replayed graph draws fresh values every
-// step without a host-side generator.  param[0]: brightness factor U[0.5, 1.5] / blur sigma U[0.01, 0.5]; noise[i] ~ N(0, 0.1) (Box-Muller).
-__device__ inline uint64_t mix64(uint64_t z) {      // splitmix64's finaliser
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
-// (the four pieces below are shared by the single-kind draw and the mixed one: the same statements, hence the same bits)
-__device__ inline uint64_t draw_key(uint64_t seed, const uint32_t *__restrict__ step) { return mix64(seed ^ (0x9E3779B97F4A7C15ull * ((uint64_t)(step ? step[0] : 0u) + 1ull))); }
-__device__ inline float draw_unit(uint64_t key) { return (float)(mix64(key ^ 0xFFFFFFFFFFFFFFFFull) >> 40) * (1.0f / 16777216.0f); }      // [0, 1)
-// one angle in [-30, 30) degrees per image, stored as (cos, sin): param[2 i], param[2 i + 1]
-__device__ inline void draw_rotation(uint64_t key, uint32_t i, float *__restrict__ param) {
-    const float u = (float)(mix64(key ^ (0xA0761D6478BD642Full * ((uint64_t)i + 1ull))) >> 40) * (1.0f / 16777216.0f);
-    const float a = (60.0f * u - 30.0f) * 0.0174532925199432958f;
-    param[2 * i] = cosf(a);
-    param[2 * i + 1] = sinf(a);
-}
-__device__ inline float draw_noise(uint64_t key, uint32_t i) {
-    const uint64_t h = mix64(key + 0xD1B54A32D192ED03ull * ((uint64_t)i + 1ull));
-    const float u1 = ((float)(uint32_t)(h >> 40) + 1.0f) * (1.0f / 16777216.0f);                   // (0, 1]
-    const float u2 = (float)(uint32_t)((h >> 8) & 0xFFFFFFu) * (1.0f / 16777216.0f);              // [0, 1)
-    return 0.316227766016837933f * sqrtf(-2.0f * logf(u1)) * cosf(6.28318530717958648f * u2);      // sigma = sqrt(0.1)
-}
-__global__ void __launch_bounds__(256) k_distort_draw(uint32_t kind, uint64_t seed, const uint32_t *__restrict__ step, uint32_t n, float *__restrict__ param,
-                                                      float *__restrict__ noise) {
-    const uint32_t i = blockIdx.x * 256 + threadIdx.x;
-    const uint64_t key = draw_key(seed, step);
-    if (i == 0 && param && kind != kDistRotation) {
-        const float u = draw_unit(key);
-        param[0] = kind == kDistBrightness ? 0.5f + u : (kind == kDistBlur ? 0.01f + 0.49f * u : 0.0f);
-    }
-    if (kind == kDistRotation && i < n) draw_rotation(key, i, param);
-    if (kind == kDistNoise && noise && i < n) noise[i] = draw_noise(key, i);
-}
-// The mixed layer's draws (distortion 6).  First WHICH kind this step trains against: the (floor(u n))-th member of the set (mask bit k = kind k, n members), u a
-// 24-bit word of a sequence of its own (distortion.host_selector is the host's statement of it).  Then that kind's parameter at its word of the block -- the
-// statements above, so bit for bit what k_distort_draw(kind) writes at this (seed, step); scaling: 0.75 + 0.5 u, the factor the host draws for the same key
-// (distortion.host_uniform; both are one rounding of the same sum).  The rotation pairs are written EVERY step, (1, 0) unless rotation is selected: the
-// resampling launch of a set that holds rotation is always enqueued, and at (1, 0) it copies.  The noise tensor is written only when noise is selected.
-// Every thread derives the selector itself (nothing is read back from the block); thread 0 stores it.
-__global__ void __launch_bounds__(256) k_distort_draw_mixed(uint32_t mask, uint64_t seed, const uint32_t *__restrict__ step, uint32_t n_images, uint32_t n_noise,
-                                                            float *__restrict__ block, float *__restrict__ noise) {
-    const uint32_t i = blockIdx.x * 256 + threadIdx.x;
-    const uint64_t key = draw_key(seed, step);
-    uint32_t pick = (uint32_t)(((mix64(key ^ 0xC2B2AE3D27D4EB4Full) >> 40) * (uint64_t)__popc(mask)) >> 24), kind = 0;
-    for (uint32_t k = 0; k <= kDistScaling; ++k)
-        if ((mask >> k) & 1u) {
-            if (pick == 0) {
-                kind = k;
-                break;
-            }
-            --pick;
-        }
-    if (i == 0) {
-        reinterpret_cast<uint32_t *>(block)[NSIG_MIXED_SELECTOR] = kind;
-        const float u = draw_unit(key);
-        if (kind == kDistBrightness) block[NSIG_MIXED_BRIGHTNESS] = 0.5f + u;
-        if (kind == kDistBlur) block[NSIG_MIXED_SIGMA] = 0.01f + 0.49f * u;
-        if (kind == kDistScaling) block[NSIG_MIXED_SCALING] = 0.75f + 0.5f * u;
-    }
-    if (i < n_images) {
-        if (kind == kDistRotation) {
-            draw_rotation(key, i, block + NSIG_MIXED_ROTATION);
-        } else {
-            block[NSIG_MIXED_ROTATION + 2 * i] = 1.0f;
-            block[NSIG_MIXED_ROTATION + 2 * i + 1] = 0.0f;
-        }
-    }
-    if (kind == kDistNoise && i < n_noise) noise[i] = draw_noise(key, i);
-}
-
-// the layer alone, [B][H][W][C] -> [B][H][W][C] (decoder shapes the fused chain does not implement; tests)
-__global__ void __launch_bounds__(256) k_distort_fwd(const float *__restrict__ img, DecInput in, uint32_t B, uint32_t Cin, float *__restrict__ out) {
-    const uint32_t P = in.H * in.W, i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= B * P * Cin) return;
-    out[i] = distorted_value(img, in, i / (P * Cin), i % Cin, (i / Cin) % P, Cin, P);
-}
-__global__ void __launch_bounds__(256) k_distort_bwd(const float *__restrict__ gy, const float *__restrict__ img, DecInput in, uint32_t B, uint32_t Cin,
-                                                     float *__restrict__ gx) {
-    const uint32_t P = in.H * in.W, i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= B * P * Cin) return;
-    const float x = img[i];
-    float g = gy[i];
-    if (in.distort == kDistBrightness) {
-        const float f = in.dparam[0], fx = f * clamp01(x);
-        g = (fx >= 0.0f && fx <= 1.0f) ? g * f : 0.0f;
-    }
-    gx[i] = (x >= 0.0f && x <= 1.0f) ? g : 0.0f;
-}
-
-// ---- the two kinds that change the sampling geometry (rotation, scaling): kernels of their own in front of / behind the decoder, which then reads their
-// output as an ordinary rendered image (values in [0, 1]: its clamp is the identity and passes every gradient).
-//
-// rotation (torchvision RandomRotation((-30, 30)) per image: nearest-neighbour resampling about the centre, zeros outside, same size): the source of output
-// pixel (x, y), measured from the centre ((W - 1) / 2, (H - 1) / 2), is round-half-even(cos * x - sin * y, sin * x + cos * y).  Every product and sum is
-// rounded on its own (no fused multiply-add): the host-side statement of the same map (distortion.rotate_nearest) picks the same pixels bit for bit.
-// At (cos, sin) = (1, 0) -- what a mixed set's draw leaves when another kind is selected -- the launch is an exact copy of clamp(img): xs = x - cx is exact
-// (an integer minus a half-integer, both far below 2^23), 1 * xs = xs, 0 * ys = +-0, xs - +-0 = xs, and xs + cx = x exactly, so rintf gives (x, y) itself, always
-// inside.  Its adjoint (k_distort_geom_bwd) then sums ONE term: its centre candidate round(1 * u + 0 * w + cx) is x itself, and of the 3 x 3 outputs around it each
-// one's source is that output itself, so only q = p matches -- grad = 0 + gy[p], the clamp mask applied as in the decoder's own epilogue.
-__device__ inline bool rotation_source(float c, float s, int x, int y, int H, int W, int &ix, int &iy) {
-    const float cx = 0.5f * (float)(W - 1), cy = 0.5f * (float)(H - 1);
-    const float xs = __fsub_rn((float)x, cx), ys = __fsub_rn((float)y, cy);
-    const float sx = __fadd_rn(__fsub_rn(__fmul_rn(c, xs), __fmul_rn(s, ys)), cx);
-    const float sy = __fadd_rn(__fadd_rn(__fmul_rn(s, xs), __fmul_rn(c, ys)), cy);
-    ix = (int)rintf(sx);
-    iy = (int)rintf(sy);
-    return ix >= 0 && ix < W && iy >= 0 && iy < H;
-}
-// scaling (F.interpolate(image [3, H, W], scale_factor = sf, mode = 'linear'): 1-d, along W only, W_out = floor(W * sf), align_corners = False with the
-// given factor kept for the coordinates): source position max(0, (xd + 0.5) / sf - 0.5), its two neighbours blended linearly -- except where W_out == W,
-// which the operator special-cases as a plain copy whatever the factor (ATen upsample_linear1d: "special case: just copy")
-__device__ inline void scaling_source(float rscale, int xd, int W, int Wo, int &x0, int &x1, float &l0, float &l1) {
-    if (Wo == W) {
-        x0 = x1 = xd;
-        l0 = 1.0f;
-        l1 = 0.0f;
-        return;
-    }
-    float src = rscale * ((float)xd + 0.5f) - 0.5f;
-    src = src < 0.0f ? 0.0f : src;
-    x0 = (int)src;
-    x0 = x0 > W - 1 ? W - 1 : x0;
-    x1 = x0 + (x0 < W - 1 ? 1 : 0);
-    l1 = src - (float)x0;
-    l0 = 1.0f - l1;
-}
-__device__ inline float scaling_rscale(const float *__restrict__ param) { return (float)(1.0 / (double)param[0]); }
-
-// out [B][H][Wo][C] = the layer on clamp(img [B][H][W][C]); clamped_out (optional) = clamp(img)
-__global__ void __launch_bounds__(256) k_distort_geom_fwd(const float *__restrict__ img, uint32_t kind, const float *__restrict__ param, uint32_t B, uint32_t H,
-                                                          uint32_t W, uint32_t Wo, uint32_t C, float *__restrict__ out, float *__restrict__ clamped_out) {
-    const uint32_t i = blockIdx.x * 256 + threadIdx.x;
-    if (clamped_out && i < B * H * W * C) clamped_out[i] = clamp01(img[i]);
-    if (i >= B * H * Wo * C) return;
-    const uint32_t c = i % C, x = (i / C) % Wo, y = (i / (C * Wo)) % H, im = i / (C * Wo * H);
-    const float *base = img + (size_t)im * H * W * C + c;
-    if (kind == kDistRotation) {
-        int ix, iy;
-        out[i] = rotation_source(param[2 * im], param[2 * im + 1], (int)x, (int)y, (int)H, (int)W, ix, iy) ? clamp01(base[((size_t)iy * W + ix) * C]) : 0.0f;
-    } else {
-        int x0, x1;
-        float l0, l1;
-        scaling_source(scaling_rscale(param), (int)x, (int)W, (int)Wo, x0, x1, l0, l1);
-        out[i] = l0 * clamp01(base[((size_t)y * W + x0) * C]) + l1 * clamp01(base[((size_t)y * W + x1) * C]);
-    }
-}
-// grad_img [B][H][W][C] = the clamp's mask x the layer's adjoint applied to gy [B][H][Wo][C].  Gather form (one thread per source element, fixed summation
-// order: deterministic).  rotation: an output pixel q reads source p only if |R^-1 q - p| <= 1/2 per axis, hence |q - R p| < 0.71: q lies in the 3 x 3
-// neighbourhood of round(R p) -- each candidate's source is re-derived with the forward's own arithmetic.  scaling: every output column of the row is tried.
-__global__ void __launch_bounds__(256) k_distort_geom_bwd(const float *__restrict__ gy, const float *__restrict__ img, uint32_t kind, const float *__restrict__ param,
-                                                          uint32_t B, uint32_t H, uint32_t W, uint32_t Wo, uint32_t C, float *__restrict__ gx) {
-    const uint32_t i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= B * H * W * C) return;
-    const uint32_t c = i % C, x = (i / C) % W, y = (i / (C * W)) % H, im = i / (C * W * H);
-    const float v = img[i];
-    if (!(v >= 0.0f && v <= 1.0f)) {
-        gx[i] = 0.0f;
-        return;
-    }
-    const float *g = gy + (size_t)im * H * Wo * C + c;
-    float acc = 0.0f;
-    if (kind == kDistRotation) {
-        const float cs = param[2 * im], sn = param[2 * im + 1];
-        const float cx = 0.5f * (float)(W - 1), cy = 0.5f * (float)(H - 1), u = (float)x - cx, w = (float)y - cy;
-        const int qx0 = (int)rintf(cs * u + sn * w + cx), qy0 = (int)rintf(-sn * u + cs * w + cy);
-        for (int qy = qy0 - 1; qy <= qy0 + 1; ++qy)
-            for (int qx = qx0 - 1; qx <= qx0 + 1; ++qx) {
-                if (qx < 0 || qx >= (int)W || qy < 0 || qy >= (int)H) continue;
-                int ix, iy;
-                if (rotation_source(cs, sn, qx, qy, (int)H, (int)W, ix, iy) && ix == (int)x && iy == (int)y) acc += g[((size_t)qy * Wo + qx) * C];
-            }
-    } else {
-        const float rs = scaling_rscale(param);
-        for (int xd = 0; xd < (int)Wo; ++xd) {
-            int x0, x1;
-            float l0, l1;
-            scaling_source(rs, xd, (int)W, (int)Wo, x0, x1, l0, l1);
-            const float gq = g[((size_t)y * Wo + xd) * C];
-            if (x0 == (int)x) acc += l0 * gq;
-            if (x1 == (int)x) acc += l1 * gq;
-        }
-    }
-    gx[i] = acc;
-}
-
 static int make_input(uint32_t mode, const float *mean, const float *stdev, uint32_t Cin, DecInput &in) {
     in.mode = mode;
-    in.distort = kDistNone;
-    in.H = in.W = 0;
-    in.dparam = in.dnoise = nullptr;
     for (int c = 0; c < 8; ++c) in.mean[c] = 0.0f, in.istd[c] = 1.0f;
     if (mode == 0) return 0;
     if (mode != 1 || !mean || !stdev || Cin > 8) return 1;
@@ -1763,42 +1463,6 @@ static int make_input(uint32_t mode, const float *mean, const float *stdev, uint
     return 0;
 }
 
-static int set_distortion(DecInput &in, uint32_t distortion, const float *param, const float *noise, uint32_t H, uint32_t W) {
-    if (distortion == kDistNone) return 0;
-    if (in.mode != 1 || distortion > kDistBlur) return 1;
-    if (distortion == kDistNoise ? noise == nullptr : param == nullptr) return 1;
-    if (distortion == kDistBlur && (H < 2 || W < 2)) return 1;      // reflect padding by one needs two pixels
-    in.distort = distortion;
-    in.H = H;
-    in.W = W;
-    in.dparam = param;
-    in.dnoise = noise;
-    return 0;
-}
-
-// distortion 6 | mask << 8 (| n_images << 16, which only the draw reads): why the call is refused, or nullptr after filling `in`.  Everything any member of the
-// set could need is checked here, before a launch: which member a step uses is known on the device only.
-static bool is_mixed(uint32_t distortion) { return (distortion & 0xFFu) == kDistMixed; }
-static const char *mixed_refusal(uint32_t distortion, const float *block, const float *noise, uint32_t H, uint32_t W) {
-    const uint32_t mask = (distortion >> 8) & 0xFFu;
-    if (mask == 0 || (mask & ~kDistAllKinds)) return "the mixed distortion's set is empty or holds bits beyond the kinds 0..5";
-    if (block == nullptr) return "the mixed distortion needs its parameter block (dist_param)";
-    if (((mask >> kDistNoise) & 1u) && noise == nullptr) return "the mixed distortion's set holds noise: it needs the noise tensor (dist_noise)";
-    if (((mask >> kDistBlur) & 1u) && (H < 2 || W < 2)) return "the mixed distortion's set holds the blur: H and W must be at least 2";
-    return nullptr;
-}
-static const char *set_mixed_distortion(DecInput &in, uint32_t distortion, const float *block, const float *noise, uint32_t H, uint32_t W) {
-    if (in.mode != 1) return "the mixed distortion needs input_mode 1";
-    const char *why = mixed_refusal(distortion, block, noise, H, W);
-    if (why) return why;
-    in.distort = distortion & 0xFFFFu;
-    in.H = H;
-    in.W = W;
-    in.dparam = block;
-    in.dnoise = noise;
-    return nullptr;
-}
-
 static int dec_forward_impl(const float *img, uint32_t input_mode, const float *mean_host, const float *std_host, const float *const *params,
                             uint32_t B, uint32_t Cin, uint32_t H, uint32_t W, float eps, void *workspace, float *decoded, float *clamped_out,
                             uint32_t distortion, const float *dist_param, const float *dist_noise, const float *bce_message, float bce_temp, float bce_scale,
@@ -1807,13 +1471,8 @@ static int dec_forward_impl(const float *img, uint32_t input_mode, const float *
     NSIG_REQUIRE(bce_seed == nullptr || bce_message != nullptr, "dec_forward_train: bce_seed needs bce_message");
     DecInput inp;
     NSIG_REQUIRE(make_input(input_mode, mean_host, std_host, Cin, inp) == 0, "dec_forward: input_mode is 0, or 1 with Cin <= 8 means and positive stds");
-    if (is_mixed(distortion)) {
-        const char *why = set_mixed_distortion(inp, distortion, dist_param, dist_noise, H, W);
-        NSIG_REQUIRE(why == nullptr, "dec_forward_train: %s", why);
-    } else {
-        NSIG_REQUIRE(set_distortion(inp, distortion, dist_param, dist_noise, H, W) == 0,
-                     "dec_forward_train: distortion is 0..3, needs input_mode 1, its device parameter (2, 3) or noise tensor (1), and H, W >= 2 for the blur");
-    }
+    const char *why = describe_distortion(inp.dist, distortion, dist_param, dist_noise, H, W, input_mode);
+    NSIG_REQUIRE(why == nullptr, "dec_forward_train: %s", why);
     DecGeom g;
     NSIG_REQUIRE(B >= 1 && Cin >= 1 && Cin <= kMaxCin && H >= 1 && W >= 1 && (uint64_t)H * W <= kMaxP && (uint64_t)B * H * W > 1 &&
                      make_geom(B, Cin, H, W, eps, g),
@@ -1858,14 +1517,14 @@ static int dec_backward_impl(const float *grad_decoded, const float *img, uint32
     NSIG_REQUIRE(grad_decoded && img && params && workspace && grads && grad_img, "dec_backward: null pointer");
     DecInput inp;
     NSIG_REQUIRE(make_input(input_mode, mean_host, std_host, Cin, inp) == 0, "dec_backward: input_mode is 0, or 1 with Cin <= 8 means and positive stds");
-    if (is_mixed(distortion)) {
-        const char *why = set_mixed_distortion(inp, distortion, dist_param, dist_noise, H, W);
-        NSIG_REQUIRE(why == nullptr, "dec_backward_train: %s", why);
-        NSIG_REQUIRE(grad_scratch != nullptr, "dec_backward_train: the mixed distortion's image gradient goes through the scratch image (grad_scratch)");
-    } else {
-        NSIG_REQUIRE(set_distortion(inp, distortion, dist_param, dist_noise, H, W) == 0 && (distortion != kDistBlur || grad_scratch != nullptr),
-                     "dec_backward_train: distortion is 0..3, needs input_mode 1, its device parameter / noise tensor, and for the blur a scratch image");
-    }
+    const char *why = describe_distortion(inp.dist, distortion, dist_param, dist_noise, H, W, input_mode);
+    NSIG_REQUIRE(why == nullptr, "dec_backward_train: %s", why);
+    // the blur's adjoint gathers its neighbours' gradients, and which kind a mixed step drew the host cannot know: the epilogue leaves d loss / d (distorted
+    // image) in the scratch image and the one adjoint launch (the blur's gather or the pointwise kinds, then the clamp mask) follows.  Every other single
+    // kind is finished in the epilogue.
+    const bool through_scratch = inp.dist.code >= kDistBlur;
+    NSIG_REQUIRE(!through_scratch || grad_scratch != nullptr, "dec_backward_train: the %s image gradient goes through the scratch image (grad_scratch)",
+                 is_mixed(inp.dist.code) ? "mixed distortion's" : "blur's");
     DecGeom g;
     NSIG_REQUIRE(B >= 1 && Cin >= 1 && Cin <= kMaxCin && H >= 1 && W >= 1 && (uint64_t)H * W <= kMaxP && make_geom(B, Cin, H, W, 0.0f, g),
                  "dec_backward: unsupported image shape");
@@ -1889,15 +1548,8 @@ static int dec_backward_impl(const float *grad_decoded, const float *img, uint32
     k_dec_head_bwd<<<B, 256, 0, s>>>(grad_decoded, prm, ws, g);
     k_dec_l8_bwd<<<grid, 256, l8b_lds(g), s>>>(prm, ws, g);
     for (int l = 7; l >= 1; --l) launch_conv<kDgrad>(dim3(g.npair, B, 2), conv_lds(g), s, l, prm, ws, g, nullptr, nullptr, inp);
-    if (inp.distort == kDistBlur) {     // the epilogue leaves d loss / d (blurred image) in the scratch image; the blur's adjoint and the clamp mask follow
-        launch_conv<kDgradImg>(grid, conv_lds(g), s, 0, prm, ws, g, grad_scratch, img, inp);
-        k_dec_blur_adjoint<false><<<ceil_div(B * H * W * Cin, 256u), 256, 0, s>>>(grad_scratch, img, inp.dparam, B, H, W, Cin, grad_img, 0u);
-    } else if (is_mixed(inp.distort)) {     // the host cannot know which kind the step drew: always the scratch image, then the one adjoint that reads the selector
-        launch_conv<kDgradImg>(grid, conv_lds(g), s, 0, prm, ws, g, grad_scratch, img, inp);
-        k_dec_blur_adjoint<true><<<ceil_div(B * H * W * Cin, 256u), 256, 0, s>>>(grad_scratch, img, inp.dparam, B, H, W, Cin, grad_img, inp.distort);
-    } else {
-        launch_conv<kDgradImg>(grid, conv_lds(g), s, 0, prm, ws, g, grad_img, img, inp);
-    }
+    launch_conv<kDgradImg>(grid, conv_lds(g), s, 0, prm, ws, g, through_scratch ? grad_scratch : grad_img, img, inp);
+    if (through_scratch) launch_distort_adjoint(grad_scratch, img, inp.dist, B, Cin, grad_img, s);
     // The parameter gradients are not needed before the optimiser; what waits on this function is the image gradient (the block
     // render's backward).  On request they are queued on a second stream, ordered after the data-gradient chain by an event.
     hipStream_t sw = as_stream(weights_stream);
@@ -1932,90 +1584,4 @@ NSIG_EXPORT int dec_backward_train(const float *grad_decoded, const float *img, 
                                        nsig_stream_t weights_stream) {
     return dec_backward_impl(grad_decoded, img, 1, mean_host, std_host, params, B, Cin, H, W, workspace, grads, grad_img, distortion, dist_param, dist_noise,
                              grad_scratch, stream, weights_stream);
-}
-
-NSIG_EXPORT int wm_distort_draw(uint32_t distortion, uint64_t seed, const uint32_t *step_counter, uint32_t n_noise, float *param_out, float *noise_out,
-                                nsig_stream_t stream) {
-    if (is_mixed(distortion)) {     // param_out = the parameter block; the set and the number of images travel in the code (NSIG_DISTORT_MIXED_CODE)
-        const uint32_t mask = (distortion >> 8) & 0xFFu, n_images = distortion >> 16;
-        const char *why = mixed_refusal(distortion, param_out, noise_out, 2, 2);
-        NSIG_REQUIRE(why == nullptr, "wm_distort_draw: %s", why);
-        NSIG_REQUIRE(!((mask >> kDistNoise) & 1u) || n_noise >= 1, "wm_distort_draw: the mixed distortion's set holds noise: n_noise = the noise tensor's element count");
-        NSIG_REQUIRE(!((mask >> kDistRotation) & 1u) || n_images >= 1,
-                     "wm_distort_draw: the mixed distortion's set holds rotation: the code carries the number of images (NSIG_DISTORT_MIXED_CODE)");
-        const uint32_t noise_elems = ((mask >> kDistNoise) & 1u) ? n_noise : 0u;
-        const uint32_t n = std::max(std::max(n_images, noise_elems), 1u);
-        k_distort_draw_mixed<<<ceil_div(n, 256u), 256, 0, as_stream(stream)>>>(mask, seed, step_counter, n_images, noise_elems, param_out, noise_out);
-        return check_launch("wm_distort_draw");
-    }
-    NSIG_REQUIRE(distortion >= kDistNoise && distortion <= kDistRotation,
-                 "wm_distort_draw: distortion is 1 (noise), 2 (brightness), 3 (blurring) or 4 (rotation); the scaling factor decides a tensor shape: the host draws it");
-    NSIG_REQUIRE(distortion == kDistNoise ? (noise_out != nullptr && n_noise >= 1) : param_out != nullptr, "wm_distort_draw: missing output buffer");
-    NSIG_REQUIRE(distortion != kDistRotation || n_noise >= 1, "wm_distort_draw: rotation draws one angle per image (n_noise = the number of images)");
-    const uint32_t n = (distortion == kDistNoise || distortion == kDistRotation) ? n_noise : 1u;
-    k_distort_draw<<<ceil_div(n, 256u), 256, 0, as_stream(stream)>>>(distortion, seed, step_counter, n, param_out, noise_out);
-    return check_launch("wm_distort_draw");
-}
-
-static int standalone_input(DecInput &in, uint32_t distortion, const float *param, const float *noise, uint32_t H, uint32_t W) {
-    in.mode = 1;
-    for (int c = 0; c < 8; ++c) in.mean[c] = 0.0f, in.istd[c] = 1.0f;
-    in.distort = kDistNone;
-    in.H = H;
-    in.W = W;
-    in.dparam = in.dnoise = nullptr;
-    return set_distortion(in, distortion, param, noise, H, W);
-}
-
-NSIG_EXPORT int wm_distort_fwd(const float *img, uint32_t B, uint32_t H, uint32_t W, uint32_t C, uint32_t distortion, const float *dist_param,
-                               const float *dist_noise, float *out, nsig_stream_t stream) {
-    NSIG_REQUIRE(img && out && B >= 1 && H >= 1 && W >= 1 && C >= 1 && (uint64_t)B * H * W * C < (1ull << 31), "wm_distort_fwd: bad arguments");
-    DecInput in;
-    if (is_mixed(distortion)) {
-        standalone_input(in, kDistNone, nullptr, nullptr, H, W);
-        const char *why = set_mixed_distortion(in, distortion, dist_param, dist_noise, H, W);
-        NSIG_REQUIRE(why == nullptr, "wm_distort_fwd: %s", why);
-    } else {
-        NSIG_REQUIRE(standalone_input(in, distortion, dist_param, dist_noise, H, W) == 0, "wm_distort_fwd: distortion is 0..3 with its device parameter / noise tensor (blur: H, W >= 2)");
-    }
-    k_distort_fwd<<<ceil_div(B * H * W * C, 256u), 256, 0, as_stream(stream)>>>(img, in, B, C, out);
-    return check_launch("wm_distort_fwd");
-}
-
-NSIG_EXPORT int wm_distort_bwd(const float *grad_out, const float *img, uint32_t B, uint32_t H, uint32_t W, uint32_t C, uint32_t distortion,
-                               const float *dist_param, const float *dist_noise, float *grad_img, nsig_stream_t stream) {
-    NSIG_REQUIRE(grad_out && img && grad_img && B >= 1 && H >= 1 && W >= 1 && C >= 1 && (uint64_t)B * H * W * C < (1ull << 31), "wm_distort_bwd: bad arguments");
-    DecInput in;
-    if (is_mixed(distortion)) {     // the one adjoint launch that reads the selector, as behind the fused chain's epilogue
-        const char *why = mixed_refusal(distortion, dist_param, dist_noise, H, W);
-        NSIG_REQUIRE(why == nullptr, "wm_distort_bwd: %s", why);
-        k_dec_blur_adjoint<true><<<ceil_div(B * H * W * C, 256u), 256, 0, as_stream(stream)>>>(grad_out, img, dist_param, B, H, W, C, grad_img, distortion & 0xFFFFu);
-        return check_launch("wm_distort_bwd");
-    }
-    NSIG_REQUIRE(standalone_input(in, distortion, dist_param, dist_noise, H, W) == 0, "wm_distort_bwd: distortion is 0..3 with its device parameter / noise tensor (blur: H, W >= 2)");
-    if (distortion == kDistBlur)
-        k_dec_blur_adjoint<false><<<ceil_div(B * H * W * C, 256u), 256, 0, as_stream(stream)>>>(grad_out, img, dist_param, B, H, W, C, grad_img, 0u);
-    else
-        k_distort_bwd<<<ceil_div(B * H * W * C, 256u), 256, 0, as_stream(stream)>>>(grad_out, img, in, B, C, grad_img);
-    return check_launch("wm_distort_bwd");
-}
-
-NSIG_EXPORT int wm_distort_geom_fwd(const float *img, uint32_t B, uint32_t H, uint32_t W, uint32_t C, uint32_t distortion, const float *dist_param, uint32_t W_out,
-                                    float *out, float *clamped_out, nsig_stream_t stream) {
-    NSIG_REQUIRE(img && out && dist_param && B >= 1 && H >= 1 && W >= 1 && C >= 1 && W_out >= 1 && (uint64_t)B * H * (W > W_out ? W : W_out) * C < (1ull << 31),
-                 "wm_distort_geom_fwd: bad arguments");
-    NSIG_REQUIRE((distortion == kDistRotation && W_out == W) || distortion == kDistScaling,
-                 "wm_distort_geom_fwd: distortion is 4 (rotation: W_out = W, dist_param = (cos, sin) per image) or 5 (scaling: dist_param[0] = the factor, W_out = floor(W * factor))");
-    k_distort_geom_fwd<<<ceil_div(B * H * (W > W_out ? W : W_out) * C, 256u), 256, 0, as_stream(stream)>>>(img, distortion, dist_param, B, H, W, W_out, C, out, clamped_out);
-    return check_launch("wm_distort_geom_fwd");
-}
-
-NSIG_EXPORT int wm_distort_geom_bwd(const float *grad_out, const float *img, uint32_t B, uint32_t H, uint32_t W, uint32_t C, uint32_t distortion,
-                                    const float *dist_param, uint32_t W_out, float *grad_img, nsig_stream_t stream) {
-    NSIG_REQUIRE(grad_out && img && grad_img && dist_param && B >= 1 && H >= 1 && W >= 1 && C >= 1 && W_out >= 1 &&
-                     (uint64_t)B * H * (W > W_out ? W : W_out) * C < (1ull << 31),
-                 "wm_distort_geom_bwd: bad arguments");
-    NSIG_REQUIRE((distortion == kDistRotation && W_out == W) || distortion == kDistScaling, "wm_distort_geom_bwd: distortion is 4 (rotation, W_out = W) or 5 (scaling)");
-    k_distort_geom_bwd<<<ceil_div(B * H * W * C, 256u), 256, 0, as_stream(stream)>>>(grad_out, img, distortion, dist_param, B, H, W, W_out, C, grad_img);
-    return check_launch("wm_distort_geom_bwd");
 }

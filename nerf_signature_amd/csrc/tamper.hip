@@ -228,7 +228,7 @@ __global__ void __launch_bounds__(256) k_tm_select_pick(TmSelect *__restrict__ s
 
 // ----------------------------------------------------------------------------- apply
 
-// The unit normal of (seed, tensor i, element j): the distortion layer's counter hash (decoder_fused.hip mix64 / draw_noise, without its 0.316 factor)
+// The unit normal of (seed, tensor i, element j): the distortion layer's counter hash (distortion.hip mix64 / draw_noise, without its 0.316 factor)
 __device__ inline uint64_t tm_mix64(uint64_t z) {      // splitmix64's finaliser
     z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
     z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;

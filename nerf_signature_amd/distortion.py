@@ -27,6 +27,7 @@ NAMES = {v: k for k, v in KINDS.items()}
 # The mixed layer (a set of kinds, one of them drawn per step): the native code 6 and the words of its parameter block (include/nerfsig.h)
 MIXED = 6
 SELECTOR, BRIGHTNESS, SIGMA, SCALING, ROTATION = 0, 1, 2, 3, 4
+_WORDS = {2: slice(BRIGHTNESS, BRIGHTNESS + 1), 3: slice(SIGMA, SIGMA + 1), 4: slice(ROTATION, None), 5: slice(SCALING, SCALING + 1)}      # kind -> its words of the block
 
 
 def parse_kinds(distortion):
@@ -133,8 +134,10 @@ def scaled_width(W, sf):
 
 class DistortionLayer:
     """distortion: one of none | noise | brightness | blurring | rotation | scaling -- or a SET of them (a tuple / list of names, "a+b+c", "mixed" = all five; "none"
-    may be a member): every step then draws one kind of the set uniformly and that kind's parameter as the single-kind layer does (no composition).  The kind
-    is a word in device memory (the native code 6: one captured step serves every kind); set_mixed(kind, ...) sets it from host values.
+    may be a member): every step then draws one kind of the set uniformly and that kind's parameter as the single-kind layer does (no composition).  A single
+    kind is the set of itself: `kinds` has one member, `selected` is that kind for ever and `param` is its parameter.  A mixed set's kind is a word in device
+    memory (the native code 6: one captured step serves every kind), `param` is the native parameter block (selector word, every kind's parameter at its own word)
+    and `selected` is the step's kind where the host knows it (draw, set_mixed, select_on_host) and None where only the device does (a captured step).
 
     draw(shape, device)              the eager loop's per-step draws: torch's generators, the calls the reference's libraries make (from generators of
                                      the layer's own, seeded with `seed`)
@@ -147,16 +150,15 @@ class DistortionLayer:
     def __init__(self, distortion="none", seed=0):
         self.mixed = isinstance(distortion, (tuple, list)) or (isinstance(distortion, str) and (distortion == "mixed" or "+" in distortion))
         if self.mixed:
-            # A SET of kinds ("mixed": all five; a tuple / list of names; "a+b+c"; "none" may be a member): every step draws one of them uniformly, then that
-            # kind's parameter as the single-kind layer does.  param is the native parameter block (selector word, every kind's parameter at its own word);
-            # `selected` is the step's kind where the host knows it (draw, set_mixed, select_on_host) and None where only the device does (a captured step).
             self.kinds = parse_kinds(distortion)
             self.name = distortion if isinstance(distortion, str) else "+".join(self.kinds)
-            self.kind, self.seed, self.mask, self.selected = MIXED, int(seed), kinds_mask(self.kinds), None
         elif distortion not in KINDS:
             raise ValueError(f"distortion {distortion!r}: choose from none, noise, rotation, scaling, blurring, brightness (main_nerf_wtmk.py:75)")
         else:
-            self.name, self.kind, self.seed = distortion, KINDS[distortion], int(seed)
+            self.kinds, self.name = (distortion,), distortion
+        self.seed, self.mask = int(seed), kinds_mask(self.kinds)
+        self.kind = MIXED if self.mixed else KINDS[distortion]
+        self.selected = None if self.mixed else self.kind
         self.param = self.noise = None
         self.factor = 1.0             # scaling: this step's factor as the host knows it (it decides a shape)
         # generators of the layer's own, seeded alike on every rank: the decoder is replicated in a data-parallel run (it sees the all-gathered
@@ -170,109 +172,99 @@ class DistortionLayer:
 
     @property
     def fused(self):
-        """applied inside the fused decoder's first layer (dec_forward_train).  mixed: code 6 reads the step's kind on the device -- except in a step the HOST knows
-        to be a scaling step (another decoder width, hence another capture): there the decoder runs plain, behind the resampling launch."""
-        if self.mixed:
-            return self.selected != 5
-        return 1 <= self.kind <= 3
+        """applied inside the fused decoder's first layer (dec_forward_train: the codes 1..3, and 6, which reads the step's kind on the device) -- except in a step
+        the HOST knows to be a scaling step (another decoder width, hence another capture): there the decoder runs plain, behind the resampling launch."""
+        return self.kind in (1, 2, 3, MIXED) and self.selected != 5
 
     @property
     def geometric(self):
-        """a resampling kernel of its own in front of the decoder (wm_distort_geom_fwd).  mixed: the scaling launch in a scaling step, else the rotation launch
-        whenever the set holds rotation -- always enqueued, an exact copy at the (1, 0) an unselected rotation keeps."""
-        if self.mixed:
-            return self.selected == 5 or bool(self.mask >> 4 & 1)
-        return self.kind >= 4
+        """a resampling kernel of its own in front of the decoder (wm_distort_geom_fwd): the scaling launch in a scaling step, else the rotation launch whenever
+        the set holds rotation -- always enqueued, an exact copy at the (1, 0) an unselected rotation keeps."""
+        return self.selected == 5 or "rotation" in self.kinds
 
     @property
     def code(self):
-        """the native `distortion` argument of the fused kinds' entry points (mixed: 6, the set's mask and the block's image count in one word)"""
+        """the native `distortion` argument: a single kind's own code (never a one-member 6: code 6 always goes through the scratch image and its extra launch);
+        a mixed set: 6, the set's mask and the block's image count in one word"""
         return self.kind if not self.mixed else MIXED | self.mask << 8 | ((self.param.numel() - ROTATION) // 2) << 16
+
+    @property
+    def needs_grad_scratch(self):
+        """the fused decoder's image gradient goes through a scratch image and the layer's adjoint launch (dec_backward_train: the blur, and every mixed set)"""
+        return self.kind in (3, MIXED)
 
     @property
     def geom_kind(self):
         """which resampling the launch in front of the decoder is (4 | 5)"""
-        return self.kind if not self.mixed else (5 if self.selected == 5 else 4)
+        return 5 if self.selected == 5 else 4
 
     @property
     def geom_param(self):
-        """the device parameter that launch reads (mixed: the factor's word / the rotation pairs of the block)"""
-        return self.param if not self.mixed else (self.param[SCALING:SCALING + 1] if self.selected == 5 else self.param[ROTATION:])
+        """the device parameter that launch reads"""
+        return self.word(self.geom_kind)
+
+    def word(self, kind):
+        """the device words that hold `kind`'s parameter: `param` itself, or the kind's slice of a mixed set's block; None for a kind without one"""
+        if kind not in _WORDS:
+            return None
+        return self.param[_WORDS[kind]] if self.mixed else self.param
 
     def out_width(self, W):
-        if self.mixed:
-            return scaled_width(W, self.factor) if self.selected == 5 else int(W)
-        return scaled_width(W, self.factor) if self.kind == 5 else int(W)
+        return scaled_width(W, self.factor) if self.selected == 5 else int(W)
 
-    def _mixed_buffers(self, shape, device):
-        n = ROTATION + 2 * int(shape[0])
-        if n >= ROTATION + 2 * 65536:
-            raise ValueError("the mixed layer's native code carries the image count in 16 bits")
-        if self.param is None or self.param.device != device or self.param.numel() != n:
-            host = torch.zeros(n, dtype=torch.float32)
-            host[ROTATION::2] = 1.0       # an unselected rotation: (cos, sin) = (1, 0); selector word 0: "none" until the first draw
-            self.param = host.to(device)
-        if self.mask >> 1 & 1 and (self.noise is None or tuple(self.noise.shape) != tuple(shape) or self.noise.device != device):
-            self.noise = torch.zeros(tuple(shape), dtype=torch.float32, device=device)
+    def widths(self, W):
+        """{decoder input width: a scaling factor that gives it} over the factor's range [0.75, 1.25): the shapes a captured loop has to hold"""
+        return {scaled_width(W, f): f for f in (0.75 + 0.5 * i / 4096.0 for i in range(4096))}
 
     def _buffers(self, shape, device):
-        if self.mixed:
-            return self._mixed_buffers(shape, device)
-        n = 2 * int(shape[0]) if self.kind == 4 else 1       # rotation: (cos, sin) per image
+        n_images = int(shape[0])
+        n = ROTATION + 2 * n_images if self.mixed else (2 * n_images if self.kind == 4 else 1)       # rotation: (cos, sin) per image
+        if self.mixed and n_images >= 65536:
+            raise ValueError("the mixed layer's native code carries the image count in 16 bits")
         if self.param is None or self.param.device != device or self.param.numel() != n:
             self.param = torch.zeros(n, dtype=torch.float32, device=device)
-        if self.kind == 1 and (self.noise is None or tuple(self.noise.shape) != tuple(shape) or self.noise.device != device):
+            if self.mixed:
+                self.param[ROTATION::2] = 1.0       # an unselected rotation: (cos, sin) = (1, 0); selector word 0: "none" until the first draw
+        if "noise" in self.kinds and (self.noise is None or tuple(self.noise.shape) != tuple(shape) or self.noise.device != device):
             self.noise = torch.zeros(tuple(shape), dtype=torch.float32, device=device)
 
-    def _draw_mixed(self, shape, device):
-        """The eager loops' draw of a mixed set: one torch.randint from the layer's host generator picks the kind, then that kind's own draw (the calls below)."""
-        kind = self.kinds[int(torch.randint(len(self.kinds), (1,), generator=self._host_gen))]
-        gen = self._host_gen
-        if kind == "noise":
-            if self._dev_gen is None or self._dev_gen.device != device:
-                self._dev_gen = torch.Generator(device=device).manual_seed(self.seed)
-            self.set_mixed(kind)
-            torch.normal(0.0, math.sqrt(0.1), size=tuple(shape), generator=self._dev_gen, device=device, out=self.noise)
-        elif kind == "brightness":
-            self.set_mixed(kind, factor=float(torch.empty(1).uniform_(0.5, 1.5, generator=gen)))
-        elif kind == "blurring":
-            self.set_mixed(kind, sigma=float(torch.empty(1).uniform_(0.01, 0.5, generator=gen)))
-        elif kind == "rotation":
-            self.set_mixed(kind, radians=[math.radians(float(torch.empty(1).uniform_(-30.0, 30.0, generator=gen))) for _ in range(int(shape[0]))])
-        elif kind == "scaling":
-            self.set_mixed(kind, scaling=torch.empty(1).uniform_(0.75, 1.25, generator=gen).item())
-        else:
-            self.set_mixed(kind)
-
-    def set_mixed(self, kind, factor=None, sigma=None, radians=None, scaling=None, noise=None):
-        """This step's kind of a mixed set and its parameter, from host values (tests, tools, the eager draw): the selector word and the kind's word(s) of the
-        device block; every rotation pair is (1, 0) unless rotation is the kind.  noise: a tensor copied into the noise buffer.  The buffers must exist (draw,
-        draw_on_device or _buffers has sized them)."""
-        if not self.mixed or kind not in self.kinds:
-            raise ValueError(f"set_mixed: {kind!r} is no member of {self.name!r}")
-        need = {"brightness": factor, "blurring": sigma, "rotation": radians, "scaling": scaling}
-        if kind in need and need[kind] is None:
-            raise ValueError(f"set_mixed: {kind} needs its parameter")
-        n_images = (self.param.numel() - ROTATION) // 2
-        # writes only (as set_rotation / set_scaling): nothing is read back from the device, so an eager loop's per-step draw does not wait for it
-        self.param[SELECTOR:SELECTOR + 1].view(torch.int32).fill_(KINDS[kind])
-        if kind == "brightness":
-            self.param[BRIGHTNESS:BRIGHTNESS + 1].fill_(float(factor))
-        elif kind == "blurring":
-            self.param[SIGMA:SIGMA + 1].fill_(float(sigma))
-        elif kind == "scaling":
-            self.factor = float(scaling)
-            self.param[SCALING:SCALING + 1].fill_(self.factor)
-        if kind == "rotation":
-            if len(radians) != n_images:
-                raise ValueError(f"set_mixed: rotation takes one angle per image ({n_images})")
-            pairs = torch.tensor([[math.cos(a), math.sin(a)] for a in radians], dtype=torch.float32).reshape(-1)
-        else:
-            pairs = torch.tensor([1.0, 0.0]).repeat(n_images)
-        self.param[ROTATION:].copy_(pairs)
+    def _set(self, kind, value=None, noise=None):
+        """This step's kind and its parameter, from host values (tests, tools, the eager draw): the kind's word(s) and, in a mixed set's block, the selector word and
+        every rotation pair at (1, 0) unless rotation is the kind.  value: the brightness factor / the sigma / the scaling factor / one angle (radians) per image;
+        noise: a tensor copied into the noise buffer.  The buffers must exist (draw, draw_on_device or _buffers has sized them)."""
+        if kind not in self.kinds:
+            raise ValueError(f"{kind!r} is no member of {self.name!r}")
+        code = KINDS[kind]
+        if code >= 2 and value is None:
+            raise ValueError(f"{kind} needs its parameter")
+        # writes only: nothing is read back from the device, so an eager loop's per-step draw does not wait for it
+        if self.mixed:
+            self.param[SELECTOR:SELECTOR + 1].view(torch.int32).fill_(code)
+        if code == 4:
+            if 2 * len(value) != self.word(4).numel():
+                raise ValueError(f"rotation takes one angle per image ({self.word(4).numel() // 2})")
+            self.word(4).copy_(torch.tensor([[math.cos(a), math.sin(a)] for a in value], dtype=torch.float32).reshape(-1))
+        elif self.mixed:
+            self.word(4).copy_(torch.tensor([1.0, 0.0]).repeat(self.word(4).numel() // 2))
+        if code == 5:
+            self.factor = float(value)
+            self.word(5).fill_(self.factor)
+        elif code in (2, 3):
+            self.word(code).fill_(float(value))
         if noise is not None:
             self.noise.copy_(noise)
-        self.selected = KINDS[kind]
+        self.selected = code
+
+    def set_mixed(self, kind, factor=None, sigma=None, radians=None, scaling=None, noise=None):
+        """this step's kind of a set and its parameter by name (_set)"""
+        self._set(kind, {"brightness": factor, "blurring": sigma, "rotation": radians, "scaling": scaling}.get(kind), noise)
+
+    def set_rotation(self, radians):
+        """this step's angles, one per image (host values -> the device buffer the kernels read)"""
+        self._set("rotation", radians)
+
+    def set_scaling(self, sf):
+        self._set("scaling", sf)
 
     def select_on_host(self, step):
         """The kind the device draws at `step` (host_selector) -- and, for scaling, its factor (host_uniform) -- as host values: what decides which captured
@@ -282,66 +274,54 @@ class DistortionLayer:
             self.factor = host_uniform(self.seed, step, 0.75, 1.25)
         return self.selected
 
+    def _draw_kind(self, kind, shape, device):
+        """one kind's draw as the reference's libraries make it, from the layer's generators"""
+        gen = self._host_gen
+        if kind == "noise":           # utils_wtmk_disen.py:555: torch.normal(0, sqrt(0.1), size=pred_rgb.shape, device=pred_rgb.device)
+            if self._dev_gen is None or self._dev_gen.device != device:
+                self._dev_gen = torch.Generator(device=device).manual_seed(self.seed)
+            self._set(kind)
+            torch.normal(0.0, math.sqrt(0.1), size=tuple(shape), generator=self._dev_gen, device=device, out=self.noise)
+        elif kind == "brightness":    # ColorJitter.get_params: float(torch.empty(1).uniform_(lo, hi)) on the host
+            self._set(kind, float(torch.empty(1).uniform_(0.5, 1.5, generator=gen)))
+        elif kind == "blurring":      # GaussianBlur.get_params: torch.empty(1).uniform_(sigma_min, sigma_max).item()
+            self._set(kind, float(torch.empty(1).uniform_(0.01, 0.5, generator=gen)))
+        elif kind == "rotation":      # RandomRotation.get_params, once per image (utils_wtmk_disen.py:560): float(torch.empty(1).uniform_(-30, 30))
+            self._set(kind, [math.radians(float(torch.empty(1).uniform_(-30.0, 30.0, generator=gen))) for _ in range(int(shape[0]))])
+        elif kind == "scaling":       # utils_wtmk_disen.py:563: sf = torch.empty(1).uniform_(0.75, 1.25).item(), ONE factor per call
+            self._set(kind, torch.empty(1).uniform_(0.75, 1.25, generator=gen).item())
+        else:
+            self._set(kind)
+
     def draw(self, shape, device):
+        """The eager loops' draw: a mixed set picks its kind with one torch.randint from the layer's host generator (a single kind draws none), then the kind's own draw."""
         if not self.native:
             return
         self._buffers(shape, device)
-        if self.mixed:
-            return self._draw_mixed(shape, device)
-        if self.kind == 1:        # utils_wtmk_disen.py:555: torch.normal(0, sqrt(0.1), size=pred_rgb.shape, device=pred_rgb.device)
-            if self._dev_gen is None or self._dev_gen.device != device:
-                self._dev_gen = torch.Generator(device=device).manual_seed(self.seed)
-            torch.normal(0.0, math.sqrt(0.1), size=tuple(shape), generator=self._dev_gen, device=device, out=self.noise)
-        elif self.kind == 2:      # ColorJitter.get_params: float(torch.empty(1).uniform_(lo, hi)) on the host
-            self.param.fill_(float(torch.empty(1).uniform_(0.5, 1.5, generator=self._host_gen)))
-        elif self.kind == 3:      # GaussianBlur.get_params: torch.empty(1).uniform_(sigma_min, sigma_max).item()
-            self.param.fill_(float(torch.empty(1).uniform_(0.01, 0.5, generator=self._host_gen)))
-        elif self.kind == 4:      # RandomRotation.get_params, once per image (utils_wtmk_disen.py:560): float(torch.empty(1).uniform_(-30, 30))
-            angles = [math.radians(float(torch.empty(1).uniform_(-30.0, 30.0, generator=self._host_gen))) for _ in range(int(shape[0]))]
-            self.set_rotation(angles)
-        else:                     # utils_wtmk_disen.py:563: sf = torch.empty(1).uniform_(0.75, 1.25).item(), ONE factor per call
-            self.set_scaling(torch.empty(1).uniform_(0.75, 1.25, generator=self._host_gen).item())
-
-    def set_rotation(self, radians):
-        """this step's angles, one per image (host values -> the device buffer the kernels read)"""
-        self.param.copy_(torch.tensor([[math.cos(a), math.sin(a)] for a in radians], dtype=torch.float32).reshape(-1))
-
-    def set_scaling(self, sf):
-        self.factor = float(sf)
-        self.param.fill_(self.factor)
+        pick = int(torch.randint(len(self.kinds), (1,), generator=self._host_gen)) if self.mixed else 0
+        self._draw_kind(self.kinds[pick], shape, device)
 
     def draw_on_device(self, step_counter, shape, device):
-        """The captured loop's draws (noise, brightness, blurring, rotation): a pure function of (seed, *step_counter) computed on the device.  The scaling
-        factor is a host value (it selects the captured shape): trainer.GraphedWatermarkLoop sets it through host_uniform / set_scaling."""
+        """The captured loop's draws: a pure function of (seed, *step_counter) computed on the device -- a mixed set's selector, then the selected kind's parameter
+        (a scaling step's factor too: the word host_uniform gives the host).  A lone scaling factor is a host value (it selects the captured shape):
+        trainer.GraphedWatermarkLoop sets it through host_uniform / set_scaling."""
         if self.kind == 5:
             raise NotImplementedError("the scaling factor decides the decoder's input width: it is drawn by the host (host_uniform, set_scaling)")
         self._buffers(shape, device)
-        if self.mixed:      # one call: the selector, then the selected kind's parameter (a scaling step's factor too: the word host_uniform gives the host)
-            nv.call("wm_distort_draw", self.code, self.seed, nv.ptr(step_counter), 0 if self.noise is None else self.noise.numel(), nv.ptr(self.param),
-                    nv.ptr(self.noise), nv.stream())
-            return
-        n = self.noise.numel() if self.kind == 1 else (int(shape[0]) if self.kind == 4 else 0)
-        nv.call("wm_distort_draw", self.kind, self.seed, nv.ptr(step_counter), n, nv.ptr(self.param), nv.ptr(self.noise), nv.stream())
+        n = self.noise.numel() if self.noise is not None else (int(shape[0]) if self.kind == 4 else 0)
+        nv.call("wm_distort_draw", self.code, self.seed, nv.ptr(step_counter), n, nv.ptr(self.param), nv.ptr(self.noise), nv.stream())
 
     def __call__(self, pred_rgb, raw=None):
         """pred_rgb: clamped blocks [B, H, W, 3].  raw: the unclamped render (native kinds back-propagate through the clamp themselves)."""
         if self.name == "none":
             return pred_rgb
-        if self.mixed:
-            if not pred_rgb.is_cuda:      # the selected kind's stock operators (the host knows the kind: draw / set_mixed / select_on_host)
-                name = NAMES[self.selected]
-                param = {"brightness": self.param[BRIGHTNESS:BRIGHTNESS + 1], "blurring": self.param[SIGMA:SIGMA + 1], "rotation": self.param[ROTATION:],
-                         "scaling": self.factor}.get(name)
-                return pred_rgb if name == "none" else reference_ops(pred_rgb, name, param, self.noise)
-            x = pred_rgb if raw is None else raw
-            if self.geometric:
-                x = _DistortGeometry.apply(x, self.geom_kind, self.geom_param, self.out_width(pred_rgb.shape[2]))[0]
-            return _Distort.apply(x, self.code, self.param, self.noise) if self.fused else x
-        if not pred_rgb.is_cuda:
-            return reference_ops(pred_rgb, self.name, self.param if self.kind != 5 else self.factor, self.noise)
+        if not pred_rgb.is_cuda:      # the selected kind's stock operators (the host knows the kind: draw / set_mixed / select_on_host)
+            name = NAMES[self.selected]
+            return pred_rgb if name == "none" else reference_ops(pred_rgb, name, self.factor if name == "scaling" else self.word(self.selected), self.noise)
+        x = pred_rgb if raw is None else raw
         if self.geometric:
-            return _DistortGeometry.apply(pred_rgb if raw is None else raw, self.kind, self.param, self.out_width(pred_rgb.shape[2]))[0]
-        return _Distort.apply(pred_rgb if raw is None else raw, self.kind, self.param, self.noise)
+            x = _DistortGeometry.apply(x, self.geom_kind, self.geom_param, self.out_width(pred_rgb.shape[2]))[0]
+        return _Distort.apply(x, self.code, self.param, self.noise) if self.fused else x
 
 
 def gaussian_kernel(sigma, dtype=torch.float32, device="cpu"):

@@ -172,7 +172,7 @@ class _FusedDecoder(torch.autograd.Function):
                 t.record_stream(side)
         if ctx.dist is not None:     # (the draws in its buffers are still this step's: they are refreshed at the head of the next one)
             d = ctx.dist
-            scratch = torch.empty_like(img) if d.kind == 3 or d.mixed else None      # (mixed: the gradient always goes through the scratch image)
+            scratch = torch.empty_like(img) if d.needs_grad_scratch else None
             nv.call("dec_backward_train", nv.ptr(grad_out.contiguous().view(-1)), nv.ptr(img), mean, std, nv.ptr_array(ps), B, Cin, H, W, nv.ptr(ws),
                     nv.ptr_array(grads), nv.ptr(grad_img), d.code, nv.ptr(d.param), nv.ptr(d.noise), nv.ptr(scratch), nv.stream(),
                     nv.stream() if side is None else side.cuda_stream)

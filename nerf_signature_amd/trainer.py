@@ -19,7 +19,7 @@ from . import dp
 from . import metrics
 from .capture import SegmentedCapture, warm_up
 from .dp import GradExchange, exchange_active, world_size
-from .distortion import DistortionLayer, host_uniform, scaled_width
+from .distortion import DistortionLayer, host_uniform
 from .hidden_models import normalize_img, set_grad_arena, set_weights_stream
 
 
@@ -930,7 +930,7 @@ class GraphedWatermarkLoop:
         self.variants = {}
         if self.distortion is not None and self.distortion.name == "scaling":
             W = self.data["watermark"]["rays_o_block"].shape[2]
-            a_factor_of = {scaled_width(W, f): f for f in (0.75 + 0.5 * i / 4096.0 for i in range(4096))}
+            a_factor_of = self.distortion.widths(W)
             for w in sorted(a_factor_of):
                 self.distortion.set_scaling(a_factor_of[w])
                 self.variants[w] = self._capture(cap_block, cap_content)
@@ -938,7 +938,7 @@ class GraphedWatermarkLoop:
             # the unscaled capture (key W: the device-side selector decides among the other kinds; a scaling step whose width is W is the operator's plain copy,
             # which is what this capture computes when the selector names no fused kind), then one per other width with the host-known scaling step set
             W = self.data["watermark"]["rays_o_block"].shape[2]
-            a_factor_of = {scaled_width(W, f): f for f in (0.75 + 0.5 * i / 4096.0 for i in range(4096))}
+            a_factor_of = self.distortion.widths(W)
             self.distortion.selected = None
             self.variants[W] = self._capture(cap_block, cap_content)
             for w in sorted(a_factor_of):
