@@ -55,59 +55,104 @@ __global__ void k_adam_prepare(StepPtrs steps, const float *__restrict__ message
 // next bit equals the current one the freshly updated row is already in registers, otherwise the partner table's row is read
 // (about D/2 extra 4 MiB streams: +9 % traffic) -- instead of a separate 128 MiB pre-sum pass at the head of the next step.
 // The sum keeps the table order, so S_next is bit-identical to k_codebook_presum_sel's.
+//
+// The step's selection is resolved ONCE per wave, not per table: lane i reads message[i] / next_message[i] / the two scalars of table i, two ballots make the masks
+// `sel` (bit i: message[i] != 0) and `oth` (bit i: the next bit differs, S_next takes the partner's row), and the scalars of table i come out of lane i by v_readlane.
+// The table loop then carries no scalar-memory dependency but the tables' addresses (kernel arguments at a computed index), and those are fetched four tables ahead.
+// Four tables per trip, as a rolling pipeline over four register slots: table i is updated and stored from slot i % 4, and table i + 4 is requested into that slot
+// right there -- in front of the wait for table i + 1, which vmcnt counts in issue order and so does not cover table i's stores.  A wave then keeps the rows of
+// 3-4 tables in flight for the whole walk, where two tables per trip had 6-8 requests for part of a trip and nothing across the trip's stores.
+//
+// kSelCols = 2 columns per thread (half a table apart), so 512 workgroups of 256 threads: 8 waves per CU, 18-32 16-byte requests per thread.  The old grid's 1024
+// workgroups were 16 waves per CU -- one residency wave when alone, but in the step the march-ahead's k_march_index (one wave per ray: 18 per CU) is already there and
+// the two do not fit into a CU's 32 wave slots together: the workgroups that had to wait for a slot walked their 32 tables late and were the launch's tail
+// (LABNOTES, "Codebook Adam beside the march-ahead").  Half the waves at twice the depth are all resident from the start and stream just as fast.
+constexpr uint32_t kSelCols = 2, kSelColumns = NSIG_TABLE_ROWS / 2 / kSelCols, kSelColStride = kSelColumns * (uint32_t)sizeof(float4);
+template <bool NEXT, bool NT, int C>
+struct AdamSlot {
+    float *bp, *bm, *bv;      // the selected table and its moments (wave-uniform)
+    float4 p[C], m[C], v[C], o[C];      // per column; o: the partner table's row
+    bool other;               // S_next takes the partner's row (wave-uniform)
+
+    static __device__ __forceinline__ float4 *at(const float *base, uint32_t byte_off) {
+        return reinterpret_cast<float4 *>(reinterpret_cast<char *>(const_cast<float *>(base)) + byte_off);
+    }
+    __device__ __forceinline__ void request(const AdamPairPtrs &a, uint32_t i, uint64_t sel, uint64_t oth, uint32_t byte_off) {
+        const uint32_t j = 2 * i + ((uint32_t)(sel >> i) & 1u);
+        bp = a.p[j]; bm = a.m[j]; bv = a.v[j];
+#pragma unroll
+        for (int c = 0; c < C; ++c) {
+            p[c] = ld4<NT>(at(bp, byte_off + c * kSelColStride)); m[c] = ld4<NT>(at(bm, byte_off + c * kSelColStride)); v[c] = ld4<NT>(at(bv, byte_off + c * kSelColStride));
+        }
+        other = NEXT && ((uint32_t)(oth >> i) & 1u);
+        if (other) {
+#pragma unroll
+            for (int c = 0; c < C; ++c) o[c] = ld4<NT>(at(a.p[j ^ 1u], byte_off + c * kSelColStride));
+        }
+        __builtin_amdgcn_sched_barrier(0);      // the requests stay here, in front of the next table's update (LABNOTES 17a: the scheduler moves them to their first use)
+    }
+    // torch's update of table i, its stores, and S_next's term of the table: the fresh row or the partner's
+    __device__ __forceinline__ void update_store(const float4 *g, uint32_t i, float sc_ss, float sc_ib, float beta1, float beta2, float eps, uint32_t byte_off, float4 *acc) {
+        const float ss = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(sc_ss), (int)i));
+        const float ib = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(sc_ib), (int)i));
+#pragma unroll
+        for (int c = 0; c < C; ++c) {
+            adam_update4(g[c], p[c], m[c], v[c], beta1, beta2, eps, ss, ib);
+            st4<NT>(at(bp, byte_off + c * kSelColStride), p[c]); st4<NT>(at(bm, byte_off + c * kSelColStride), m[c]); st4<NT>(at(bv, byte_off + c * kSelColStride), v[c]);
+            if (NEXT) {
+                const float4 t = other ? o[c] : p[c];
+                acc[c].x += t.x; acc[c].y += t.y; acc[c].z += t.z; acc[c].w += t.w;
+                // the sum is taken HERE: left alone, the compiler sinks the four tables' adds to the end of the trip, keeps every o alive until then, loads the next
+                // partner rows into other registers and copies them over behind a vmcnt(0) -- a full drain of the trip's loads and stores
+                asm volatile("" : "+v"(acc[c].x), "+v"(acc[c].y), "+v"(acc[c].z), "+v"(acc[c].w));
+            }
+        }
+    }
+};
+
 template <bool NEXT, bool NT>
 __global__ void __launch_bounds__(256) k_codebook_adam_sel(const float4 *__restrict__ G, AdamPairPtrs a, const float *__restrict__ message,
                                                            const float *__restrict__ scratch, uint32_t D, float beta1, float beta2, float eps,
                                                            float grad_scale, const float *__restrict__ next_message, float4 *__restrict__ S_next) {
+    constexpr int C = kSelCols;
     const uint32_t e = blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= NSIG_TABLE_ROWS / 2) return;
-    float4 g = ld4<NT>(G + e);
-    g.x *= grad_scale; g.y *= grad_scale; g.z *= grad_scale; g.w *= grad_scale;
-    float4 acc = {0.f, 0.f, 0.f, 0.f};
-    const float4 zero = {0.f, 0.f, 0.f, 0.f};
-    // two tables per trip: six 16-byte loads in flight per thread before the first dependent store
+    if (e >= kSelColumns) return;      // (whole waves: the grid is a multiple of 256)
+    const uint32_t lane = threadIdx.x & 63u, byte_off = e * (uint32_t)sizeof(float4);
+    const bool bit = lane < D && message[lane] != 0.0f;
+    const uint64_t sel = __ballot(bit);
+    const uint64_t oth = NEXT ? __ballot(lane < D && (next_message[lane] != 0.0f) != bit) : 0;
+    const float sc_ss = lane < D ? scratch[lane] : 0.f, sc_ib = lane < D ? scratch[D + lane] : 0.f;      // D <= NSIG_MAX_MESSAGE_DIM = one wave's lanes
+    float4 g[C], acc[C];
+#pragma unroll
+    for (int c = 0; c < C; ++c) {
+        g[c] = ld4<NT>(G + e + c * kSelColumns);
+        g[c].x *= grad_scale; g[c].y *= grad_scale; g[c].z *= grad_scale; g[c].w *= grad_scale;
+        acc[c] = make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+    AdamSlot<NEXT, NT, C> slot[4];
+#pragma unroll
+    for (uint32_t k = 0; k < 4; ++k)
+        if (k < D) slot[k].request(a, k, sel, oth, byte_off);
     uint32_t i = 0;
-    for (; i + 2 <= D; i += 2) {
-        const uint32_t j0 = 2 * i + (message[i] != 0.0f), j1 = 2 * i + 2 + (message[i + 1] != 0.0f);
-        float4 *pp0 = reinterpret_cast<float4 *>(a.p[j0]) + e, *pm0 = reinterpret_cast<float4 *>(a.m[j0]) + e, *pv0 = reinterpret_cast<float4 *>(a.v[j0]) + e;
-        float4 *pp1 = reinterpret_cast<float4 *>(a.p[j1]) + e, *pm1 = reinterpret_cast<float4 *>(a.m[j1]) + e, *pv1 = reinterpret_cast<float4 *>(a.v[j1]) + e;
-        bool other0 = false, other1 = false;      // wave-uniform
-        float4 o0 = zero, o1 = zero;
-        if (NEXT) {
-            other0 = (next_message[i] != 0.0f) != (message[i] != 0.0f);
-            other1 = (next_message[i + 1] != 0.0f) != (message[i + 1] != 0.0f);
-            if (other0) o0 = ld4<NT>(reinterpret_cast<const float4 *>(a.p[j0 ^ 1u]) + e);
-            if (other1) o1 = ld4<NT>(reinterpret_cast<const float4 *>(a.p[j1 ^ 1u]) + e);
-        }
-        float4 p0 = ld4<NT>(pp0), m0 = ld4<NT>(pm0), v0 = ld4<NT>(pv0), p1 = ld4<NT>(pp1), m1 = ld4<NT>(pm1), v1 = ld4<NT>(pv1);
-        const float ss0 = scratch[i], ib0 = scratch[D + i], ss1 = scratch[i + 1], ib1 = scratch[D + i + 1];
-        adam_update4(g, p0, m0, v0, beta1, beta2, eps, ss0, ib0);
-        adam_update4(g, p1, m1, v1, beta1, beta2, eps, ss1, ib1);
-        st4<NT>(pp0, p0); st4<NT>(pm0, m0); st4<NT>(pv0, v0); st4<NT>(pp1, p1); st4<NT>(pm1, m1); st4<NT>(pv1, v1);
-        if (NEXT) {
-            const float4 c0 = other0 ? o0 : p0, c1 = other1 ? o1 : p1;
-            acc.x += c0.x; acc.y += c0.y; acc.z += c0.z; acc.w += c0.w;
-            acc.x += c1.x; acc.y += c1.y; acc.z += c1.z; acc.w += c1.w;
+    for (; i + 8 <= D; i += 4) {      // every table of the trip has a successor four tables on
+#pragma unroll
+        for (uint32_t k = 0; k < 4; ++k) {
+            slot[k].update_store(g, i + k, sc_ss, sc_ib, beta1, beta2, eps, byte_off, acc);
+            slot[k].request(a, i + k + 4, sel, oth, byte_off);
         }
     }
-    for (; i < D; ++i) {
-        const uint32_t j = 2 * i + (message[i] != 0.0f);
-        float4 *pp = reinterpret_cast<float4 *>(a.p[j]) + e, *pm = reinterpret_cast<float4 *>(a.m[j]) + e, *pv = reinterpret_cast<float4 *>(a.v[j]) + e;
-        bool other = false;
-        float4 o = zero;
-        if (NEXT) {
-            other = (next_message[i] != 0.0f) != (message[i] != 0.0f);
-            if (other) o = ld4<NT>(reinterpret_cast<const float4 *>(a.p[j ^ 1u]) + e);
-        }
-        float4 p = ld4<NT>(pp), m = ld4<NT>(pm), v = ld4<NT>(pv);
-        adam_update4(g, p, m, v, beta1, beta2, eps, scratch[i], scratch[D + i]);
-        st4<NT>(pp, p); st4<NT>(pm, m); st4<NT>(pv, v);
-        if (NEXT) {
-            const float4 c = other ? o : p;
-            acc.x += c.x; acc.y += c.y; acc.z += c.z; acc.w += c.w;
+    for (; i < D; i += 4) {           // the last 1 .. 7 tables: D % 4 and D < 4 (a rank's share of the sharded optimiser) end here
+#pragma unroll
+        for (uint32_t k = 0; k < 4; ++k) {
+            if (i + k >= D) break;
+            slot[k].update_store(g, i + k, sc_ss, sc_ib, beta1, beta2, eps, byte_off, acc);
+            if (i + k + 4 < D) slot[k].request(a, i + k + 4, sel, oth, byte_off);
         }
     }
-    if (NEXT) S_next[e] = acc;
+    if (NEXT) {
+#pragma unroll
+        for (int c = 0; c < C; ++c) S_next[e + c * kSelColumns] = acc[c];
+    }
 }
 
 // ----------------------------------------------------------------------------- EMA of the parameters
@@ -267,10 +312,10 @@ static int codebook_adam_sel(const char *who, const float *G, float *const *para
     // non-temporal accesses (same-box A/B of the bench step, three pairs: 1.124-1.138 ms against 1.151-1.157 with plain accesses; the kernel alone takes
     // the same 160-164 us either way, the next step's gather gains)
     if (next_message)
-        k_codebook_adam_sel<true, true><<<NSIG_TABLE_ROWS / 2 / 256, 256, 0, st>>>(reinterpret_cast<const float4 *>(G), a, message, scratch, D, beta1, beta2, eps,
+        k_codebook_adam_sel<true, true><<<kSelColumns / 256, 256, 0, st>>>(reinterpret_cast<const float4 *>(G), a, message, scratch, D, beta1, beta2, eps,
                                                                                  grad_scale, next_message, reinterpret_cast<float4 *>(S_next));
     else
-        k_codebook_adam_sel<false, false><<<NSIG_TABLE_ROWS / 2 / 256, 256, 0, st>>>(reinterpret_cast<const float4 *>(G), a, message, scratch, D, beta1, beta2, eps,
+        k_codebook_adam_sel<false, false><<<kSelColumns / 256, 256, 0, st>>>(reinterpret_cast<const float4 *>(G), a, message, scratch, D, beta1, beta2, eps,
                                                                                grad_scale, nullptr, nullptr);
     return check_launch(who);
 }
