@@ -397,6 +397,7 @@ __global__ void k_error_map_update(float *__restrict__ error_map, uint32_t P, ui
 struct GridView {
     const uint8_t *bits;
     float bound, dt_gamma, dt_min, dt_max, dt_const, inv_H, H3f, Hf, Cf, top;
+    uint32_t last_bit;      // C * H^3 - 1: see grid_bit
     double Hd;
 };
 
@@ -414,6 +415,8 @@ __host__ inline GridView make_grid_view(const uint8_t *bits, float bound, float 
     g.Hf = (float)H;
     g.Cf = (float)C;
     g.top = (float)(H - 1);
+    const uint64_t n_bits = (uint64_t)C * H * H * H;
+    g.last_bit = n_bits - 1u > 0xffffffffull ? 0xffffffffu : (uint32_t)(n_bits - 1u);
     g.Hd = (double)H;
     return g;
 }
@@ -437,6 +440,13 @@ __device__ inline int cascade_of(const GridView &g, float x, float y, float z, f
     return max(lp, ls);
 }
 
+// raymarching.cu:339,378: H3 is a float there, so the bit index level * H^3 + morton is a float sum.  Above 2^24 (C * H^3 > 2^24: H = 256 with two cascades) it
+// rounds to even, and for the last cell of the last cascade it rounds UP to C * H^3 -- one bit past the bitfield, where the reference reads whatever follows its
+// buffer.  The rounding is kept (it is what the reference computes); the one index past the end is brought back to the last bit, that cell's own.
+__device__ inline uint32_t grid_bit(const GridView &g, int level, int nx, int ny, int nz) {
+    return min((uint32_t)((float)level * g.H3f + (float)morton3((uint32_t)nx, (uint32_t)ny, (uint32_t)nz)), g.last_bit);
+}
+
 __device__ inline int cell_coord(const GridView &g, float v, float inv_extent) {
     // raymarching.cu:374-376: float bracket, double product, float clamp, truncation.
     return (int)clampf((float)(0.5 * (double)fmaf(v, inv_extent, 1.0f) * g.Hd), 0.0f, g.top);
@@ -454,7 +464,7 @@ __device__ inline bool probe(const GridView &g, const Ray &r, float t, float &x,
     const float extent = fminf(ldexpf(1.0f, level), g.bound);
     const float inv_extent = 1.0f / extent;
     const int nx = cell_coord(g, x, inv_extent), ny = cell_coord(g, y, inv_extent), nz = cell_coord(g, z, inv_extent);
-    const uint32_t bit = (uint32_t)((float)level * g.H3f + (float)morton3((uint32_t)nx, (uint32_t)ny, (uint32_t)nz));
+    const uint32_t bit = grid_bit(g, level, nx, ny, nz);
     if (g.bits[bit >> 3] & (1u << (bit & 7u))) return true;
     const float fx = (fmaf(0.5f, copysignf(1.0f, r.dx), (float)nx + 0.5f) * g.inv_H) * 2.0f - 1.0f;
     const float fy = (fmaf(0.5f, copysignf(1.0f, r.dy), (float)ny + 0.5f) * g.inv_H) * 2.0f - 1.0f;
@@ -498,7 +508,7 @@ struct Walker {
             if (lv != level) { level = lv; extent = fminf(ldexpf(1.0f, lv), g.bound); inv_extent = 1.0f / extent; }
         }
         const int nx = cell(x), ny = cell(y), nz = cell(z);
-        const uint32_t bit = (uint32_t)((float)level * g.H3f + (float)morton3((uint32_t)nx, (uint32_t)ny, (uint32_t)nz));
+        const uint32_t bit = grid_bit(g, level, nx, ny, nz);
         if (g.bits[bit >> 3] & (1u << (bit & 7u))) return true;
         const float fx = (fmaf(0.5f, copysignf(1.0f, r.dx), (float)nx + 0.5f) * g.inv_H) * 2.0f - 1.0f;
         const float fy = (fmaf(0.5f, copysignf(1.0f, r.dy), (float)ny + 0.5f) * g.inv_H) * 2.0f - 1.0f;

@@ -164,7 +164,7 @@ ORACLE_API void oracle_packbits(const float *grid, uint32_t n_bytes, float thres
 typedef struct {
     float ox, oy, oz, dx, dy, dz, rdx, rdy, rdz;
     float bound, dt_gamma, dt_min, dt_max, rH, H3f, Hf, Cf;
-    uint32_t H;
+    uint32_t H, last_bit;
     const uint8_t *grid;
 } MarchCtx;
 
@@ -177,6 +177,7 @@ static void march_ctx_init(MarchCtx *c, const float *o, const float *d, const ui
     c->rH = 1.0f / (float)H;                                            /* :338 */
     c->H3f = (float)(H * H * H);                                        /* :339 */
     c->Hf = (float)H; c->Cf = (float)C; c->H = H;
+    { const uint64_t bits = (uint64_t)C * H * H * H - 1u; c->last_bit = bits > 0xffffffffull ? 0xffffffffu : (uint32_t)bits; }
     c->dt_min = (2.0f * kSqrt3) / (float)max_steps;                     /* :345 */
     c->dt_max = ((2.0f * kSqrt3) * (float)(1u << (C - 1))) / (float)H;  /* :346 */
     c->grid = grid;
@@ -204,8 +205,11 @@ static inline int probe(const MarchCtx *c, float t, float *px, float *py, float 
     const int ny = (int)clampf((float)(0.5 * (double)fmaf(y, mip_rbound, 1.0f) * (double)c->H), 0.0f, top);
     const int nz = (int)clampf((float)(0.5 * (double)fmaf(z, mip_rbound, 1.0f) * (double)c->H), 0.0f, top);
 
-    /* :378 -- float arithmetic, then conversion to uint32. */
-    const uint32_t index = (uint32_t)((float)level * c->H3f + (float)morton_encode((uint32_t)nx, (uint32_t)ny, (uint32_t)nz));
+    /* :378 -- float arithmetic (H3 is a float, :339), then conversion to uint32.  Where C * H^3 > 2^24 the sum rounds to even, and for the last cell of the
+     * last cascade it rounds up to C * H^3, one bit past the bitfield: the reference reads whatever follows its buffer there.  That one index is brought
+     * back to the last bit (the cell's own), here and in the kernels; every other rounding is kept. */
+    uint32_t index = (uint32_t)((float)level * c->H3f + (float)morton_encode((uint32_t)nx, (uint32_t)ny, (uint32_t)nz));
+    if (index > c->last_bit) index = c->last_bit;
     const int occ = (c->grid[index >> 3] & (1u << (index & 7u))) != 0;
 
     *px = x; *py = y; *pz = z; *pdt = dt;
