@@ -337,6 +337,19 @@ int opt_codebook_adam_sel_next(const float *G, float *const *params_host, float 
                                float beta2, float eps, float grad_scale, float *scratch, const float *next_message,
                                float *S_next, nsig_stream_t stream);
 
+/* opt_codebook_adam_sel[_next] with opt_adam_dense's update of n_dense <= 32 dense tensors (the decoder) inside the same launch: its chunks are the launch's closing
+ * workgroups, behind the 512 of the table walk, and the one prepare launch advances the dense step counts with the tables'.  The results -- tables, moments, step counts,
+ * S_next, every dense tensor and its moments -- have the bits of the two separate calls with the same device scalars; grad_scale scales G, dense_grad_scale the dense
+ * gradients.  next_message and S_next may both be NULL (opt_codebook_adam_sel's walk); n_dense == 0 is the plain launch.  The dense lists are opt_adam_dense's;
+ * dense_scratch: NSIG_ADAM_DENSE_SCRATCH_BYTES device bytes, 16-byte aligned (the dense step scalars and the launch's chunk table, rewritten by every call). */
+#define NSIG_ADAM_DENSE_SCRATCH_BYTES 2048
+int opt_codebook_adam_sel_next_dense(const float *G, float *const *params_host, float *const *exp_avg_host, float *const *exp_avg_sq_host,
+                                     float *const *steps_host, const float *message, uint32_t D, const float *lr, float beta1,
+                                     float beta2, float eps, float grad_scale, float *scratch, const float *next_message,
+                                     float *S_next, uint32_t n_dense, float *const *dense_params_host, const float *const *dense_grads_host,
+                                     float *const *dense_exp_avg_host, float *const *dense_exp_avg_sq_host, float *const *dense_steps_host,
+                                     const uint32_t *dense_numel_host, float dense_grad_scale, void *dense_scratch, nsig_stream_t stream);
+
 /* ------------------------------------------------------------------ field network */
 
 /* Re-lays the two flat tcnn-style parameter vectors (sigma: 3072, color: 7168 fp32, layout in
@@ -437,10 +450,12 @@ int field_fwd_rows(const float *xyzs, const float *dirs, uint32_t M_capacity, co
                    const float *const *base_tables_host, const float *S, const void *packed, float *sigmas, float *rgbs, const void *planes,
                    int planes_layout, nsig_stream_t stream);
 
-/* Reads the 16 base tables (and S when given) once, each through the XCD whose workgroups will gather from it in hg_encode_planes, so that
- * the launch finds its tables in L2 instead of starting on caches a streaming pass (the optimiser's) has flushed: the bench workload's block
- * launch 282 -> 258 us; the pass itself takes ~20 us alone -- it pays where it can run beside something else (trainer.GraphedWatermarkLoop).
- * Replaces nothing in the reference (a scheduling aid); sink: one writable float, never written. */
+/* Reads, through each of the eight XCDs, the finest table its workgroups will gather from in hg_encode_planes -- S and seven base tables, or eight base tables
+ * without S: 4 MiB each, one L2's worth -- so that the launch finds them in L2 instead of starting on caches a streaming pass (the optimiser's) has flushed: the
+ * bench workload's block launch 282 -> 258 us.  The coarser tables an XCD also serves are left out: read through the same XCD they made three of the eight read
+ * 12 MiB where others read 4, the pass took as long as its fullest XCD (~20 us, at the end of the step with nothing beside it) and they pushed the fine table out
+ * of the L2 they shared; the pass now takes ~7 us and the step is faster without them (LABNOTES, "Optimiser tail").  It pays where it can run beside something
+ * else (trainer.GraphedWatermarkLoop).  Replaces nothing in the reference (a scheduling aid); sink: one writable float, never written. */
 int hg_warm_tables(const float *const *base_tables_host, const float *S, float *sink, nsig_stream_t stream);
 
 /* Rays that do not change between training steps (the watermark blocks: nerf/provider_wtmk.py:442-494 computes

@@ -54,11 +54,12 @@ __device__ __forceinline__ void st4(float4 *p, const float4 &a) {
     __builtin_nontemporal_store(v, reinterpret_cast<nsig_f32x4 *>(p));
 }
 
-// Tensor i of a multi-tensor launch has the workgroups chunk0[i] .. chunk0[i + 1] - 1: the tensor this workgroup serves (uniform)
-__device__ inline uint32_t chunk_owner(const uint32_t *chunk0, uint32_t n) {
+// Tensor i of a multi-tensor launch has the workgroups chunk0[i] .. chunk0[i + 1] - 1: the tensor workgroup `block` serves (uniform)
+__device__ inline uint32_t chunk_owner(const uint32_t *chunk0, uint32_t n, uint32_t block) {
     uint32_t i = 0;
-    while (i + 1 < n && blockIdx.x >= chunk0[i + 1]) ++i;
+    while (i + 1 < n && block >= chunk0[i + 1]) ++i;
     return i;
 }
+__device__ inline uint32_t chunk_owner(const uint32_t *chunk0, uint32_t n) { return chunk_owner(chunk0, n, blockIdx.x); }
 
 }  // namespace nsig

@@ -180,17 +180,21 @@ __device__ inline void encode_tile_level(const float2 *__restrict__ table, float
     else *reinterpret_cast<f32x2_t *>(out) = vv;
 }
 
-// Reads the tables of a slot through that slot's XCD (blockIdx % 8): its L2 then holds the slot's fine table when the encoder starts.
+// Reads a slot's finest table (its first) through that slot's XCD (blockIdx % 8): its L2 then holds that table when the encoder starts.  Only that one: it is the
+// L2's size, and the slot's coarser tables behind it made the pass as long as the fullest slot's 12 MiB (include/nerfsig.h, hg_warm_tables).
 __global__ void __launch_bounds__(256) k_warm_tables(TablePtrs base, const float *__restrict__ S, SlotTable tab, float *__restrict__ sink) {
     const uint32_t slot = blockIdx.x & 7u, wg = blockIdx.x >> 3, n_wg = gridDim.x >> 3;
     float acc = 0.0f;
-    for (int i = 0; i < tab.n[slot]; ++i) {
-        const int l = tab.level[slot][i];
+    if (tab.n[slot] > 0) {
+        const int l = tab.level[slot][0];
         const float4 *t = reinterpret_cast<const float4 *>(l == NSIG_BASE_LEVELS ? S : base.p[l]);
-        if (t == nullptr) continue;
-        for (uint32_t e = wg * 256 + threadIdx.x; e < NSIG_TABLE_ROWS / 2; e += n_wg * 256) {
-            const float4 v = t[e];
-            acc += v.x + v.y + v.z + v.w;
+        // eight requests per lane before the first is waited for (the default grid: all of a lane's eight): one at a time, the pass was eight memory latencies long
+        for (uint32_t e = wg * 256 + threadIdx.x; t != nullptr && e < NSIG_TABLE_ROWS / 2; e += 8 * n_wg * 256) {
+            float4 v[8];
+#pragma unroll
+            for (uint32_t k = 0; k < 8; ++k) v[k] = t[min(e + k * n_wg * 256, NSIG_TABLE_ROWS / 2 - 1)];
+#pragma unroll
+            for (uint32_t k = 0; k < 8; ++k) acc += v[k].x + v[k].y + v[k].z + v[k].w;
         }
     }
     if (acc == 1.2345e-33f) *sink = acc;      // (never: keeps the loads)

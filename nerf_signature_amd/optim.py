@@ -207,10 +207,16 @@ def _prepare_device_state(opt, tables):
     return [_adam_state(opt, t, device_count=True) for t in tables]
 
 
-def _step_shared_sel(opt, tables, message_dev, G, lr_dev, grad_scale=1.0, next_message_dev=None, S_next=None):
+DENSE_SCRATCH_BYTES = 2048      # NSIG_ADAM_DENSE_SCRATCH_BYTES
+DENSE_IN_LAUNCH = 32            # dense tensors that fit into the codebook launch (opt_codebook_adam_sel_next_dense)
+
+
+def _step_shared_sel(opt, tables, message_dev, G, lr_dev, grad_scale=1.0, next_message_dev=None, S_next=None, dense=None, dense_grad_scale=1.0):
     """Adam step of table 2i + message[i] for every bit, everything message-dependent resolved on the device.
     next_message_dev + S_next: the same pass also writes the pre-summed codebook of the next step's message into S_next
-    (opt_codebook_adam_sel_next)."""
+    (opt_codebook_adam_sel_next).
+    dense: parameters with a dense `.grad` (the decoder's, at most DENSE_IN_LAUNCH, one (betas, eps) with the tables: dense_parameters) whose update rides in the
+    same launch (opt_codebook_adam_sel_next_dense) instead of a prepare and a pass of its own behind it (step_dense): same results, bit for bit."""
     group = opt._group_of(tables[0])
     beta1, beta2 = group["betas"]
     cache = getattr(opt, "_sel_cache", None)
@@ -225,11 +231,24 @@ def _step_shared_sel(opt, tables, message_dev, G, lr_dev, grad_scale=1.0, next_m
     if next_message_dev is not None:
         if S_next is None or S_next.dtype != torch.float32 or not S_next.is_contiguous() or S_next.numel() != tables[0].numel():
             raise ValueError("step_shared_sel: S_next must be a contiguous float32 tensor of one table's size")
-        nv.call("opt_codebook_adam_sel_next", nv.ptr(G), pp, pm, pv, ps, nv.ptr(message_dev), D, nv.ptr(lr_dev), float(beta1), float(beta2),
-                float(group["eps"]), float(grad_scale), nv.ptr(scratch), nv.ptr(next_message_dev), nv.ptr(S_next), nv.stream())
+    head = (nv.ptr(G), pp, pm, pv, ps, nv.ptr(message_dev), D, nv.ptr(lr_dev), float(beta1), float(beta2), float(group["eps"]), float(grad_scale), nv.ptr(scratch))
+    if dense:
+        if len(dense) > DENSE_IN_LAUNCH:
+            raise ValueError(f"step_shared_sel: at most {DENSE_IN_LAUNCH} dense tensors ride in the codebook launch")
+        states = _prepare_device_state(opt, dense)
+        dense_scratch = getattr(opt, "_dense_fused_scratch", None)
+        if dense_scratch is None:
+            dense_scratch = opt._dense_fused_scratch = torch.empty(DENSE_SCRATCH_BYTES, dtype=torch.uint8, device=tables[0].device)
+        n = len(dense)
+        nv.call("opt_codebook_adam_sel_next_dense", *head, nv.ptr(next_message_dev), nv.ptr(S_next) if next_message_dev is not None else None, n,
+                nv.ptr_array([p.data for p in dense]), nv.ptr_array([p.grad for p in dense]),
+                *(nv.ptr_array([st[key] for st in states]) for key in ("exp_avg", "exp_avg_sq", "step")), (ctypes.c_uint32 * n)(*[p.numel() for p in dense]),
+                float(dense_grad_scale), nv.ptr(dense_scratch), nv.stream())
+        _bump_versions(dense)
+    elif next_message_dev is not None:
+        nv.call("opt_codebook_adam_sel_next", *head, nv.ptr(next_message_dev), nv.ptr(S_next), nv.stream())
     else:
-        nv.call("opt_codebook_adam_sel", nv.ptr(G), pp, pm, pv, ps, nv.ptr(message_dev), D, nv.ptr(lr_dev), float(beta1), float(beta2),
-                float(group["eps"]), float(grad_scale), nv.ptr(scratch), nv.stream())
+        nv.call("opt_codebook_adam_sel", *head, nv.stream())
     _bump_versions(tables)
 
 
@@ -248,10 +267,8 @@ def _adam_dense(optimizer, params, group, lr_dev, scratch, grad_scale=1.0):
     _bump_versions(params)
 
 
-def _step_dense(opt, lr_dev, grad_scale=1.0):
-    """torch.optim.Adam's update of every parameter that carries a dense `.grad` (the decoder) through opt_adam_dense: one
-    pass of 1024-element chunks instead of the generic multi-tensor kernel's 64K-element ones.  State in torch's capturable
-    format (device step counts), so `step()` and `state_dict()` keep working on it."""
+def _dense_parameters(opt):
+    """(group, [parameters]) of everything that carries a dense `.grad` (the decoder): contiguous float32 CUDA tensors under one (betas, eps); (None, []) if nothing does."""
     todo = []
     for group in opt.param_groups:
         for p in group["params"]:
@@ -261,11 +278,20 @@ def _step_dense(opt, lr_dev, grad_scale=1.0):
                 raise NotImplementedError("step_dense handles contiguous float32 CUDA parameters")
             todo.append((group, p))
     if not todo:
-        return
+        return None, []
     group = todo[0][0]
     if any(g["betas"] != group["betas"] or g["eps"] != group["eps"] for g, _ in todo):
         raise NotImplementedError("step_dense expects one (betas, eps) for all dense parameters")
-    ps = [p for _, p in todo]
+    return group, [p for _, p in todo]
+
+
+def _step_dense(opt, lr_dev, grad_scale=1.0):
+    """torch.optim.Adam's update of every parameter that carries a dense `.grad` (the decoder) through opt_adam_dense: one
+    pass of 1024-element chunks instead of the generic multi-tensor kernel's 64K-element ones.  State in torch's capturable
+    format (device step counts), so `step()` and `state_dict()` keep working on it."""
+    group, ps = _dense_parameters(opt)
+    if not ps:
+        return
     n = len(ps)
     scratch = getattr(opt, "_dense_scratch", None)
     if scratch is None or scratch.numel() < 64 * ((n + 31) // 32):
@@ -273,6 +299,7 @@ def _step_dense(opt, lr_dev, grad_scale=1.0):
     _adam_dense(opt, ps, group, lr_dev, scratch, grad_scale)
 
 
+CodebookAdam.dense_parameters = _dense_parameters
 CodebookAdam.step_dense = torch.no_grad()(_step_dense)
 
 

@@ -761,8 +761,18 @@ class GraphedWatermarkLoop:
             tables, msg, msg_next = self.tables[2 * b0:2 * b1], self.msg_dev[b0:b1], self.msg_next_dev[b0:b1]
         # ... and the next step's pre-sum, in place (both renders of this step are done with the buffer)
         S = self.model._presum_cache[1]
-        self.optimizer.step_shared_sel(tables, msg, self.sink.G, self.lr_dev, scale_cb, next_message_dev=msg_next, S_next=S)
-        self.optimizer.step_dense(self.lr_dev, scale)      # the decoder's parameters: opt_adam_dense
+        # The decoder's parameters ride in the codebook launch (opt_codebook_adam_sel_next_dense): their prepare and their pass were two launches behind the walk, at
+        # the step's end, with nothing to wait for there.  Where the walk is a rank's share (the sharded optimiser), where the optimiser was not asked for fused
+        # kernels, or with more tensors than the launch takes, the decoder keeps its own pass (opt_adam_dense).
+        from .optim import DENSE_IN_LAUNCH
+        group, dense = self.optimizer.dense_parameters()
+        of_tables = self.optimizer._group_of(tables[0])
+        if dense and (self.opt_shard is not None or len(dense) > DENSE_IN_LAUNCH or not group.get("fused")
+                      or (group["betas"], group["eps"]) != (of_tables["betas"], of_tables["eps"])):
+            dense = []
+        self.optimizer.step_shared_sel(tables, msg, self.sink.G, self.lr_dev, scale_cb, next_message_dev=msg_next, S_next=S, dense=dense, dense_grad_scale=scale)
+        if not dense:
+            self.optimizer.step_dense(self.lr_dev, scale)      # the decoder's parameters: opt_adam_dense
         if self.opt_shard is None:
             return None
         import torch.distributed as dist      # the ranks' partial pre-sums of the next message add up to the whole one
@@ -803,12 +813,12 @@ class GraphedWatermarkLoop:
             post()                                  # (a collective: only after the streams have joined)
 
     def _warm_tables(self):
-        """The frozen base tables read once, each through the XCD that will gather from it (hg_warm_tables), behind the march of the next step's
-        block samples and beside the optimiser: the next step's block encoder -- the step's longest kernel, at its head -- otherwise starts on
-        caches the optimiser's 836 MiB stream has flushed (282-290 us; 258-270 us behind this pass, which takes ~20 us alone).  Same-box A/B of
-        the bench step: 1.026-1.031 -> 1.005-1.019 ms (profiles/r03_warm_tables.txt).  Only where the optimiser outlasts it: with the codebook
-        optimiser sharded over >= 4 ranks (a 22 us pass over D/R tables) the warm-up would end the step (emulated rank of 4 / 8: +1.5 / +2 %).
-        Hence off there."""
+        """The finest table each XCD will gather from (hg_warm_tables: seven frozen base tables and the next step's pre-summed codebook, 4 MiB per XCD) read once, behind
+        the march of the next step's block samples and beside the optimiser: the next step's block encoder -- the step's longest kernel, at its head -- otherwise
+        starts on caches the optimiser's 836 MiB stream has flushed (282-290 us; 258-270 us behind this pass).  Same-box A/B of the bench step with the pass over all
+        17 tables (~20 us): 1.026-1.031 -> 1.005-1.019 ms (profiles/r03_warm_tables.txt); over the eight finest only (~7 us, what is left at the step's end):
+        profiles/optimiser_tail_ab.txt.  Only where the optimiser outlasts it: with the codebook optimiser sharded over >= 4 ranks (a 22 us pass over D/R tables) the
+        warm-up would end the step (emulated rank of 4 / 8: +1.5 / +2 %).  Hence off there."""
         if self.opt_shard is not None or self.fixed_blocks or getattr(self.model, "_presum_cache", None) is None:
             return
         tables = nv.ptr_array([t.detach() for t in self.model.encoder.tables()])
