@@ -31,6 +31,7 @@
 #include <type_traits>
 #include <unordered_set>
 #include "fieldmlp.h"
+#include "packed.h"
 #include "wave.h"
 
 #include <stdlib.h>
@@ -232,6 +233,88 @@ __global__ void __launch_bounds__(256) k_encode_planes(const float *__restrict__
             float2 *out = !mixed ? planes + (size_t)l * stride + m
                                  : (half_out ? reinterpret_cast<float2 *>(reinterpret_cast<uint32_t *>(planes) + (size_t)l * stride + m) : mixed_f32_plane(planes, stride, l) + m);
             encode_tile_level(reinterpret_cast<const float2 *>(l == NSIG_BASE_LEVELS ? S : base.p[l]), geom.cell[l], xs, x, y, z, out, half_out, /*streaming=*/mixed);
+        }
+    }
+}
+
+// ---- the encoder over PACKED tables (hg_encode_planes_packed; formats and decode: include/nerfsig.h "packed released model", csrc/packed.h).  The fp32 functions
+// above are left exactly as they are; these stand beside them.  Same slot table, same lane-pair gather, same axis_cell / trilerp: the one difference is the row load,
+// which fetches a 4-, 2- or 1-byte row word.  The lane pair exchanges the RAW row words by DPP (one exchange per corner instead of two) and every lane decodes the
+// eight corners of its own point once; decode(word) is a pure function of the word, so the floats are those the fp32 encoder gathers from the decoded table.
+template <int FMT>
+__device__ inline void encode_tile_level_packed(const void *__restrict__ table, float lo, float step, float cell, uint32_t xs, float x, float y, float z,
+                                                float2 *__restrict__ out, bool half_out, bool streaming) {
+    uint32_t ix, iy, iz;
+    float wx, wy, wz;
+    axis_cell(x, cell, ix, wx);
+    axis_cell(y, cell, iy, wy);
+    axis_cell(z, cell, iz, wz);
+    const uint32_t hy0 = iy * kPrimeY, hy1 = (iy + 1u) * kPrimeY, hz0 = iz * kPrimeZ, hz1 = (iz + 1u) * kPrimeZ;   // corner_rows()
+    uint32_t v[2][4];   // v[P][q]: the row word of this lane's x side of point P of the pair, corner (dy, dz) = (q >> 1, q & 1)
+#pragma unroll
+    for (int P = 0; P < 2; ++P) {
+        const uint32_t hx = dpp_u(ix, P) + xs;
+        const uint32_t a0 = dpp_u(hy0, P), a1 = dpp_u(hy1, P), b0 = dpp_u(hz0, P), b1 = dpp_u(hz1, P);
+        v[P][0] = pk_load_row<FMT>(table, (hx ^ a0 ^ b0) & kRowMask);      // (a row index is < NSIG_TABLE_ROWS: inside the table's pk_table_bytes)
+        v[P][1] = pk_load_row<FMT>(table, (hx ^ a0 ^ b1) & kRowMask);
+        v[P][2] = pk_load_row<FMT>(table, (hx ^ a1 ^ b0) & kRowMask);
+        v[P][3] = pk_load_row<FMT>(table, (hx ^ a1 ^ b1) & kRowMask);
+    }
+    float2 e[8];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const uint32_t mine = xs ? v[1][q] : v[0][q];      // my own point, my x side
+        const uint32_t give = xs ? v[0][q] : v[1][q];      // the neighbour's point, my x side
+        const uint32_t got = dpp_u(give, 2);               // my own point, the other x side (fetched by the neighbour)
+        e[q] = pk_decode_row<FMT>(xs ? got : mine, lo, step);          // corner k = 4*dx + q
+        e[4 + q] = pk_decode_row<FMT>(xs ? mine : got, lo, step);
+    }
+    const float2 val = trilerp(e, wx, wy, wz);
+    if (half_out) {
+        __builtin_nontemporal_store(cvt_pk_f16(val.x, val.y), reinterpret_cast<uint32_t *>(out));
+        return;
+    }
+    typedef float f32x2_t __attribute__((ext_vector_type(2)));
+    const f32x2_t vv = {val.x, val.y};
+    if (streaming) __builtin_nontemporal_store(vv, reinterpret_cast<f32x2_t *>(out));
+    else *reinterpret_cast<f32x2_t *>(out) = vv;
+}
+
+struct PackedTablePtrs {
+    const void *p[NSIG_BASE_LEVELS + 1];      // [16]: the signature table (level 16), NULL without one
+};
+
+// k_encode_planes over packed tables: the same walk (tiles, slots, rows_dev, the replicated last row), the same destinations; params[l] = {lo, step} of table l.
+template <int FMT, bool mixed>
+__global__ void __launch_bounds__(256) k_encode_planes_packed(const float *__restrict__ xyzs, uint32_t M, float bound, PackedTablePtrs tabs, LevelGeom geom,
+                                                              const float2 *__restrict__ params, float2 *__restrict__ planes, uint32_t stride, SlotTable tab,
+                                                              const uint32_t *__restrict__ rows_dev) {
+    uint32_t lim = stride;
+    if (rows_dev != nullptr) {
+        const uint32_t r = *rows_dev;
+        if (r == 0) return;
+        M = min(M, r);
+        lim = min(stride, ceil_div(M, 32u) * 32u);
+    }
+    const uint32_t slot = blockIdx.x & 7u;
+    const uint32_t n_tiles = ceil_div(stride, 256u);
+    const int n_levels = tab.n[slot];
+    const float two_b = 2.0f * bound;
+    const uint32_t xs = threadIdx.x & 1u;
+    for (uint32_t tile = blockIdx.x >> 3; tile < n_tiles; tile += gridDim.x >> 3) {
+        const uint32_t m = tile * 256 + threadIdx.x;
+        if (m >= lim) continue;             // a multiple of 32: lane pairs (and DPP quads) are in or out together
+        const uint32_t ml = min(m, M - 1);  // rows in [M, stride) replicate the last point (never consumed)
+        const float3 pt = *reinterpret_cast<const float3 *>(xyzs + 3 * (size_t)ml);
+        const float x = (pt.x + bound) / two_b, y = (pt.y + bound) / two_b, z = (pt.z + bound) / two_b;
+        for (int i = 0; i < n_levels; ++i) {
+            const int l = tab.level[slot][i];
+            const bool half_out = mixed && l < kHalfLevels;
+            float2 *out = !mixed ? planes + (size_t)l * stride + m
+                                 : (half_out ? reinterpret_cast<float2 *>(reinterpret_cast<uint32_t *>(planes) + (size_t)l * stride + m) : mixed_f32_plane(planes, stride, l) + m);
+            float2 ps = make_float2(0.0f, 0.0f);
+            if (FMT != NSIG_PACK_F16) ps = params[l];      // (uniform: one scalar load per level)
+            encode_tile_level_packed<FMT>(tabs.p[l], ps.x, ps.y, geom.cell[l], xs, x, y, z, out, half_out, /*streaming=*/mixed);
         }
     }
 }
@@ -1159,6 +1242,38 @@ NSIG_EXPORT int hg_encode_planes_rows(const float *xyzs, uint32_t M_capacity, co
     return encode_planes_impl(xyzs, M_capacity, bound, base_tables_host, S, planes, rows_dev, stream);
 }
 
+// hg_encode_planes[_rows|_mixed] over packed tables: encode_planes_impl's launch shape (one tile per workgroup and slot up to 8192 tiles), default_slots(signature present).
+NSIG_EXPORT int hg_encode_planes_packed(const float *xyzs, uint32_t M_capacity, const uint32_t *rows_dev, float bound, const void *const *tables_host, int format,
+                                        const float *params, void *planes, int planes_layout, nsig_stream_t stream) {
+    NSIG_REQUIRE(pk_row_bytes(format) != 0, "hg_encode_planes_packed: unknown format %d (0 f16, 1 q8, 2 q4)", format);
+    if (int e = check_layout(planes_layout, "hg_encode_planes_packed")) return e;
+    const bool mixed = planes_layout == NSIG_PLANES_MIXED;
+    NSIG_REQUIRE(!mixed || mlp_precision() == 1, "hg_encode_planes_packed: the mixed layout carries the fp16 MLP's operands (mlp_set_precision(1))");
+    NSIG_REQUIRE(xyzs && planes && tables_host, "hg_encode_planes_packed: null pointer");
+    NSIG_REQUIRE(format == NSIG_PACK_F16 || params != nullptr, "hg_encode_planes_packed: the q8 and q4 formats need the per-table parameters (params, pk_pack_tables')");
+    NSIG_REQUIRE(bound > 0.0f, "hg_encode_planes_packed: bound must be positive");
+    NSIG_REQUIRE(aligned8(planes) && aligned8(params), "hg_encode_planes_packed: planes and params must be 8-byte aligned");
+    PackedTablePtrs tabs{};
+    for (uint32_t i = 0; i <= NSIG_BASE_LEVELS; ++i) {
+        NSIG_REQUIRE((tables_host[i] != nullptr || i == NSIG_BASE_LEVELS) && aligned16(tables_host[i]), "hg_encode_planes_packed: table %u is null or not 16-byte aligned", i);
+        tabs.p[i] = tables_host[i];
+    }
+    if (M_capacity == 0) return NSIG_OK;
+    const uint32_t stride = ceil_div(M_capacity, 32u) * 32u;
+    const SlotTable tab = default_slots(tabs.p[NSIG_BASE_LEVELS] != nullptr);
+    const uint32_t tiles = ceil_div(stride, 256u), per_slot = tiles < 8192u ? tiles : 8192u;
+    const float2 *ps = reinterpret_cast<const float2 *>(params);
+    float2 *pl = reinterpret_cast<float2 *>(planes);
+    hipStream_t st = as_stream(stream);
+    with_flag(mixed, [&](auto kMixed) {
+        constexpr bool kM = decltype(kMixed)::value;
+        if (format == NSIG_PACK_F16) k_encode_planes_packed<NSIG_PACK_F16, kM><<<per_slot * 8, 256, 0, st>>>(xyzs, M_capacity, bound, tabs, make_level_geom(), ps, pl, stride, tab, rows_dev);
+        else if (format == NSIG_PACK_Q8) k_encode_planes_packed<NSIG_PACK_Q8, kM><<<per_slot * 8, 256, 0, st>>>(xyzs, M_capacity, bound, tabs, make_level_geom(), ps, pl, stride, tab, rows_dev);
+        else k_encode_planes_packed<NSIG_PACK_Q4, kM><<<per_slot * 8, 256, 0, st>>>(xyzs, M_capacity, bound, tabs, make_level_geom(), ps, pl, stride, tab, rows_dev);
+    });
+    return check_launch("hg_encode_planes_packed");
+}
+
 NSIG_EXPORT int hg_encode_codebook_plane(const float *xyzs, uint32_t M, float bound, const float *S, void *planes, int planes_layout, void *plan_to_reset,
                                          nsig_stream_t stream) {
     if (M == 0) return NSIG_OK;
@@ -1297,6 +1412,36 @@ NSIG_EXPORT int field_fwd_rows(const float *xyzs, const float *dirs, uint32_t M_
                                int planes_layout, nsig_stream_t stream) {
     NSIG_REQUIRE(rows_dev != nullptr, "field_fwd_rows: null row count");
     return field_fwd_impl(xyzs, dirs, M_capacity, bound, base_tables_host, S, packed, sigmas, rgbs, nullptr, nullptr, planes, planes_layout, rows_dev, stream);
+}
+
+// The MLP over a finished plane set, without a table list: the kernels of field_fwd_impl's planes route read nothing but the set (k_field_fwd<P, 1> takes S only as
+// the flag "plane 16 is there"), so this launcher hands them no tables, no points and -- as the flag -- the plane set's own address.  Same choice of loop as there.
+NSIG_EXPORT int field_fwd_planes(const float *dirs, uint32_t M_capacity, const uint32_t *rows_dev, const void *packed, const void *planes, int planes_layout,
+                                 int with_codebook, float *sigmas, float *rgbs, float *geo_feat, nsig_stream_t stream) {
+    NSIG_REQUIRE(packed && planes && sigmas, "field_fwd_planes: null pointer");
+    NSIG_REQUIRE(rgbs == nullptr || dirs != nullptr, "field_fwd_planes: dirs is required when rgbs is requested");
+    NSIG_REQUIRE(aligned16(packed), "field_fwd_planes: packed must be 16-byte aligned");
+    NSIG_REQUIRE(aligned8(planes), "field_fwd_planes: planes must be 8-byte aligned");
+    if (int e = check_layout(planes_layout, "field_fwd_planes")) return e;
+    const bool f16 = mlp_precision() == 1, mixed = planes_layout == NSIG_PLANES_MIXED;
+    NSIG_REQUIRE(!mixed || f16, "field_fwd_planes: this plane set was written in the mixed (fp16) layout; the split-bf16 MLP needs an fp32 set (NSIG_PLANES_F32)");
+    if (M_capacity == 0) return NSIG_OK;
+    const uint32_t M = M_capacity, stride = ceil_div(M, 32u) * 32u;
+    const float2 *pl = reinterpret_cast<const float2 *>(planes);
+    const char *pk = reinterpret_cast<const char *>(packed);
+    const float *flag = with_codebook ? reinterpret_cast<const float *>(planes) : nullptr;      // (never dereferenced by the planes route)
+    hipStream_t st = as_stream(stream);
+    if (f16 && fwd_pipelined() && dirs != nullptr && rgbs != nullptr && geo_feat == nullptr) {
+        with_flag(mixed, [&](auto kMixed) {
+            k_field_fwd_train<F16, decltype(kMixed)::value><<<field_grid(M, true, 2), 256, F16::kFwdLds, st>>>(dirs, M, flag != nullptr, pl, stride, pk, sigmas, rgbs, nullptr, rows_dev);
+        });
+        return check_launch("field_fwd_planes");
+    }
+    with_mlp([&](auto tag) {
+        using P = decltype(tag);
+        k_field_fwd<P, 1><<<field_grid(M, true), 256, P::kFwdLds, st>>>(nullptr, dirs, M, 1.0f, TablePtrs{}, make_level_geom(), flag, pl, stride, pk, sigmas, rgbs, geo_feat, nullptr, ActTrace{}, rows_dev, mixed);
+    });
+    return check_launch("field_fwd_planes");
 }
 
 NSIG_EXPORT int field_color_fwd(const float *dirs, const float *geo_feat, uint32_t M, const void *packed, float *rgbs, nsig_stream_t stream) {

@@ -205,6 +205,153 @@ def field_rows_runner(capacity, bound, base_tables, S, packed):
     return run
 
 
+# ---- packed tables (include/nerfsig.h "packed released model"; release.PackedReleasedModel): fp16 pairs, 8-bit or 4-bit codes, one flat uint8 tensor per table
+
+PACK_FORMATS = {"f16": 0, "q8": 1, "q4": 2}      # include/nerfsig.h NSIG_PACK_*
+_PACK_BITS = {"q8": 8, "q4": 4}
+
+
+def pack_format(format):
+    """The format's name ("f16" | "q8" | "q4") for a name or its NSIG_PACK_* number."""
+    for name, code in PACK_FORMATS.items():
+        if format == name or (isinstance(format, int) and not isinstance(format, bool) and format == code):
+            return name
+    raise ValueError(f"unknown packed format {format!r} (f16 | q8 | q4)")
+
+
+def pk_table_bytes(format):
+    """Bytes of one packed table -> pk_table_bytes (2 MiB, 1 MiB, 512 KiB)."""
+    return int(nv.fn("pk_table_bytes")(PACK_FORMATS[pack_format(format)]))
+
+
+def _check_codes(c, format, name):
+    n = pk_table_bytes(format)
+    if c.dtype != torch.uint8 or c.dim() != 1 or c.numel() != n or not c.is_contiguous():
+        raise ValueError(f"{name}: expected a flat uint8 tensor of {n} bytes ({pack_format(format)}), got {c.dtype} {tuple(c.shape)}")
+    return c
+
+
+def pack_tables_cpu(tables, format):
+    """(codes, params [n, 2] float32, non-finite count) of fp32 [T_ROWS, 2] host tables: the arithmetic of pk_pack_tables with torch operators, every operation
+    float32 and rounded on its own -- bit for bit the device's codes and parameters."""
+    format = pack_format(format)
+    codes, params, bad = [], torch.zeros(len(tables), 2, dtype=torch.float32), 0
+    for i, t in enumerate(tables):
+        x = _check_table(t.detach(), f"table {i}").reshape(-1)
+        if format == "f16":
+            codes.append(x.to(torch.float16).view(torch.uint8).clone())
+            continue
+        fin = torch.isfinite(x)
+        bad += int((~fin).sum())
+        L = torch.tensor(float((1 << _PACK_BITS[format]) - 1), dtype=torch.float32)
+        lo = x[fin].min() if bool(fin.any()) else torch.zeros((), dtype=torch.float32)
+        hi = x[fin].max() if bool(fin.any()) else torch.zeros((), dtype=torch.float32)
+        step = (hi - lo) / L
+        if bool(hi == lo):
+            q = torch.zeros_like(x)
+        else:
+            q = torch.clamp(torch.round((torch.where(fin, x, lo) - lo) / step), min=0.0).clamp(max=float(L))      # (torch.round: half to even, rintf)
+        q = torch.where(fin, q, torch.zeros_like(q)).to(torch.uint8).view(T_ROWS, 2)
+        codes.append(q.reshape(-1).clone() if format == "q8" else (q[:, 0] | (q[:, 1] << 4)).contiguous())
+        params[i, 0], params[i, 1] = lo, step
+    return codes, params, bad
+
+
+def unpack_tables_cpu(codes, format, params):
+    """The decoded fp32 [T_ROWS, 2] tables of host codes: lo + float(q) * step as a product and a sum (two torch operators: two roundings)."""
+    format = pack_format(format)
+    out = []
+    for i, c in enumerate(codes):
+        c = _check_codes(c, format, f"codes {i}")
+        if format == "f16":
+            out.append(c.view(torch.float16).to(torch.float32).view(T_ROWS, 2))
+            continue
+        q = c.view(T_ROWS, 2) if format == "q8" else torch.stack([c & 0xF, c >> 4], dim=1)
+        prod = q.to(torch.float32) * params[i, 1]
+        out.append(params[i, 0] + prod)
+    return out
+
+
+def pack_tables(tables, format):
+    """(codes, params [n, 2] float32, nonfinite [1] int32) on the tables' device -> tm_stats, pk_pack_tables.  Nothing is read back here."""
+    from . import tamper
+    format = pack_format(format)
+    tabs = [_check_table(t.detach(), f"table {i}") for i, t in enumerate(tables)]
+    dev = tabs[0].device
+    nbytes = pk_table_bytes(format)
+    codes = [torch.empty(nbytes, dtype=torch.uint8, device=dev) for _ in tabs]
+    params = torch.zeros(len(tabs), 2, dtype=torch.float32, device=dev)
+    bad = torch.zeros(1, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        stats = tamper.stats(tabs) if format != "f16" else None
+        nv.call("pk_pack_tables", nv.ptr_array(tabs), len(tabs), PACK_FORMATS[format], nv.ptr(stats), nv.ptr_array(codes), nv.ptr(params), nv.ptr(bad), nv.stream())
+    return codes, params, bad
+
+
+def unpack_tables(codes, format, params):
+    """The decoded fp32 tables on the codes' device -> pk_unpack_tables."""
+    format = pack_format(format)
+    codes = [_check_codes(c, format, f"codes {i}") for i, c in enumerate(codes)]
+    out = [torch.empty(T_ROWS, 2, dtype=torch.float32, device=codes[0].device) for _ in codes]
+    with torch.cuda.device(codes[0].device):
+        nv.call("pk_unpack_tables", nv.ptr_array(codes), len(codes), PACK_FORMATS[format], nv.ptr(params), nv.ptr_array(out), nv.stream())
+    return out
+
+
+def packed_ptrs(codes, signature, format):
+    """Host array of the 17 table pointers hg_encode_planes_packed takes: the 16 base tables' codes, then the signature's (None: no codebook level)."""
+    if len(codes) != 16:
+        raise ValueError(f"a packed model has the 16 base tables, got {len(codes)}")
+    return nv.ptr_array([_check_codes(c, format, f"codes {i}") for i, c in enumerate(codes)] + [None if signature is None else _check_codes(signature, format, "signature codes")])
+
+
+def encode_planes_packed(xyzs, M, bound, table_ptrs, format, params, planes, rows_dev=None):
+    """encode_planes over packed tables (hg_encode_planes_packed): the same plane set, in the layout the MLP that follows will read (mixed_planes); returns that layout."""
+    layout = PLANES_MIXED if mixed_planes() else PLANES_F32
+    nv.call("hg_encode_planes_packed", nv.ptr(xyzs), M, nv.ptr(rows_dev), float(bound), table_ptrs, PACK_FORMATS[pack_format(format)], nv.ptr(params), nv.ptr(planes),
+            layout, nv.stream())
+    return layout
+
+
+def field_planes(dirs, M, packed, planes, layout, with_codebook, want_rgb=True, want_geo=False, rows_dev=None, sigmas=None, rgbs=None):
+    """sigma [M], rgb [M,3] | None, geo_feat [M,15] | None from a finished plane set -> field_fwd_planes (the MLP launches of field_fwd, no table list)."""
+    dev = packed.device
+    sigmas = torch.empty(M, dtype=torch.float32, device=dev) if sigmas is None else sigmas
+    rgbs = (torch.empty(M, 3, dtype=torch.float32, device=dev) if rgbs is None else rgbs) if want_rgb else None
+    geo = torch.empty(M, 15, dtype=torch.float32, device=dev) if want_geo else None
+    nv.call("field_fwd_planes", nv.ptr(dirs) if want_rgb else None, M, nv.ptr(rows_dev), nv.ptr(packed), nv.ptr(planes), layout, int(bool(with_codebook)),
+            nv.ptr(sigmas), nv.ptr(rgbs), nv.ptr(geo), nv.stream())
+    return sigmas, rgbs, geo
+
+
+@torch.no_grad()
+def field_forward_packed(xyzs, dirs, bound, codes, signature, format, params, packed):
+    """(sigma [M], rgb [M,3]) of the field over packed tables: always the two-launch route (packed encoder, then the MLP over its plane set)."""
+    xyzs, dirs = xyzs.contiguous().float(), dirs.contiguous().float()
+    M, dev = xyzs.shape[0], xyzs.device
+    if M == 0:
+        return torch.empty(0, dtype=torch.float32, device=dev), torch.empty(0, 3, dtype=torch.float32, device=dev)
+    ws = torch.empty(int(nv.fn("hg_planes_bytes")(M)), dtype=torch.uint8, device=dev)
+    layout = encode_planes_packed(xyzs, M, bound, packed_ptrs(codes, signature, format), format, params, ws)
+    sigmas, rgbs, _ = field_planes(dirs, M, packed, ws, layout, signature is not None)
+    return sigmas, rgbs
+
+
+@torch.no_grad()
+def field_rows_runner_packed(capacity, bound, codes, signature, format, params, packed):
+    """field_rows_runner over packed tables: fn(xyzs, dirs, rows_dev, sigmas, rgbs) evaluates the first *rows_dev rows with launches sized for `capacity`."""
+    ptrs = packed_ptrs(codes, signature, format)
+    ws = torch.empty(int(nv.fn("hg_planes_bytes")(capacity)), dtype=torch.uint8, device=packed.device)
+    bound = float(bound)
+
+    def run(xyzs, dirs, rows_dev, sigmas, rgbs):
+        layout = encode_planes_packed(xyzs, capacity, bound, ptrs, format, params, ws, rows_dev)
+        field_planes(dirs, capacity, packed, ws, layout, signature is not None, rows_dev=rows_dev, sigmas=sigmas, rgbs=rgbs)
+        run.keep = (codes, signature, params, packed, ws)      # (the launches above hold raw addresses)
+
+    return run
+
+
 MULTI_MAX_MESSAGES = 16      # include/nerfsig.h NSIG_MULTI_MAX_MESSAGES: the largest K of one multi-message launch
 
 

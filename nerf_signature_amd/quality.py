@@ -254,6 +254,50 @@ def model_robustness(stage, message, attacks=MODEL_ATTACKS, seeds=(0,), view=0):
     return out
 
 
+def _timed_ms(fn, warmup=2, repeats=5):
+    """[ms] of `repeats` runs of fn() after `warmup` untimed ones, each between device synchronisations (wall clock around a drained queue)."""
+    for _ in range(warmup):
+        fn()
+    out = []
+    for _ in range(repeats):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        out.append((time.perf_counter() - t0) * 1e3)
+    return out
+
+
+@torch.no_grad()
+def packed_report(stage, message, formats=("f16", "q8", "q4"), view=0, repeats=5, directory=None):
+    """What the packed forms of stage['model'] released under `message` cost and keep (release.pack).  Per format, and under "fp32" for the
+    fp32 release measured the same way in the same process (the yardstick):
+      "bytes"             the saved checkpoint's size (written to `directory`, a temporary one by default, and removed)
+      "verify"            release.verify's dict against the key of the stage's block rays (whether q4 keeps every bit is REPORTED here, asserted nowhere)
+      "psnr"              held-out view `view` against the fp32 release's render of it (metrics.psnr; +inf where bit-equal: the "fp32" entry)
+      "render_ms"         median milliseconds of one staged full-view render; "render_ms_all": the `repeats` timings behind it (the spread)"""
+    import os
+    import tempfile
+    from . import metrics, release as rel
+    model, H, W = stage["model"], stage["H"], stage["W"]
+    released = rel.release(model, message)
+    key = rel.SignatureKey.from_block_rays(message, model.msg_decoder, stage["block_o"], stage["block_d"], stage["render_kwargs"])
+    r = rays.get_rays(stage["test_poses"][view:view + 1], stage["intr"], H, W, -1)
+    full = lambda m: m.render(r["rays_o"], r["rays_d"], staged=True, bg_color=1, perturb=False, force_all_rays=True, **stage["render_kwargs"])["image"] \
+        .reshape(1, H, W, 3).clamp(0, 1)
+    truth = full(released)
+    out = {}
+    with tempfile.TemporaryDirectory(dir=directory) as tmp:
+        for name in ("fp32", *formats):
+            m = released if name == "fp32" else rel.pack(released, name)
+            path = m.save(os.path.join(tmp, f"{name}.pth"))
+            times = _timed_ms(lambda: full(m), repeats=repeats)
+            out[name] = {"bytes": os.path.getsize(path), "verify": rel.verify(m, key), "psnr": float(metrics.psnr(full(m), truth)),
+                         "render_ms": float(np.median(times)), "render_ms_all": [round(t, 3) for t in times]}
+            os.remove(path)
+    return out
+
+
 def test_views(stage, seed=9876, max_ray_batch=4096):
     """Trainer.test_image's loop (:816-933) as a generator of (pred, truth) [1, H, W, 3]: per test view a random message and
     eval_step(render_whole=True) -- the full view staged in max_ray_batch chunks -- beside the clean view."""

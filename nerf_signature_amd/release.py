@@ -9,6 +9,9 @@ the pre-sum S = sum_i table[2 i + bit_i] (network._presum), ONE [T, 2] table, so
     SignatureKey                                 the secret: key pose(s) and block coordinates (the reference's --keyposes_dir / --keyblocks_dir files,
                                                  provider_wtmk.py:451,453,475,477, interchangeable with ours), intrinsics, render keywords, message, decoder
     verify(render, key) -> dict                  bits, matches, bit_accuracy and the exact p-value of that many matches under a fair coin
+    pack(released, format) -> PackedReleasedModel   the same model with its 17 tables stored as fp16 pairs, 8-bit or 4-bit codes ("f16" | "q8" | "q4": 34, 17 or 8.5 MiB
+                                                 of tables instead of 68) and rendered from that storage; its bits are those of the fp32 release whose tables went
+                                                 through Tamper.apply("half" | "quantize", 8 | 4)
 
 A released checkpoint uses the clean checkpoint's key names plus `signature.weight`: loaded with
 checkpoint.load_checkpoint(path, clean_network, model_only=True) it gives the CLEAN model (strict=False reports `signature.weight` as unexpected and
@@ -135,6 +138,8 @@ class ReleasedModel(NeRFRenderer):
     def load(cls, path_or_dict, device=None):
         ckpt = torch.load(path_or_dict, map_location="cpu", weights_only=False) if isinstance(path_or_dict, (str, os.PathLike)) else path_or_dict
         sd = ckpt["model"]
+        if SIGNATURE_CODES_KEY in sd or "format" in ckpt.get("release", {}):
+            raise ValueError("this is a packed released model: load it with PackedReleasedModel.load (and unpack() it for fp32 tables)")
         if SIGNATURE_KEY not in sd:
             raise ValueError(f"not a released model: the checkpoint has no '{SIGNATURE_KEY}'")
         to = (lambda t: t.to(device)) if device is not None else (lambda t: t)
@@ -190,6 +195,177 @@ def release(model, message, copy=False):
                         {k: getattr(model, k) for k in _SCALARS}, buffers, mean_count=model.mean_count, mean_density=model.mean_density)
     out.iter_density, out.local_step = model.iter_density, model.local_step
     out.train(model.training)
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------- the packed form
+
+SIGNATURE_CODES_KEY, TABLE_PARAMS_KEY = "signature.codes", "table_params"
+
+
+class _Codes(nn.Module):
+    def __init__(self, codes):
+        super().__init__()
+        self.register_buffer("codes", codes)
+
+
+class _CodesList(nn.Module):
+    def __init__(self, codes):
+        super().__init__()
+        self.embeddings = nn.ModuleList([_Codes(c) for c in codes])
+
+    def codes(self):
+        return [m._buffers["codes"] for m in self.embeddings._modules.values()]
+
+
+class PackedReleasedModel(NeRFRenderer):
+    """A released model whose 17 tables are stored as fp16 pairs ("f16"), 8-bit ("q8") or 4-bit ("q4") codes (include/nerfsig.h "packed released model";
+    DESIGN.md section 22) and gathered from in that form: 34, 17 or 8.5 MiB of tables instead of 68.  Every table is one flat uint8 tensor
+    (`encoder.embeddings.{i}.codes`, `signature.codes`); `table_params` [17, 2] holds each table's (lo, step) (zeros for f16); the MLP vectors stay fp32.
+    render() has ReleasedModel.render's contract and the bits of the fp32 release whose 17 tables went through Tamper.apply("half") / ("quantize", 8) /
+    ("quantize", 4): the decode restores exactly those floats.  Always the two-launch route (packed encoder, MLP over the plane set) -- the header guarantees
+    the fused small-batch route gives the same bits.  Inference only; the fp32 density grid is not carried (the render path reads the bitfield): the model keeps
+    the constructor's zero grid and refuses to refresh it."""
+
+    def __init__(self, base_codes, signature_codes, table_params, format, sigma_params, color_params, scalars, buffers=None, mean_count=0, mean_density=0):
+        super().__init__(bound=scalars["bound"], cuda_ray=True, density_scale=scalars["density_scale"], min_near=scalars["min_near"],
+                         density_thresh=scalars["density_thresh"], bg_radius=scalars["bg_radius"])
+        self.format = fo.pack_format(format)
+        if len(base_codes) != 16:
+            raise ValueError(f"a packed released model has the 16 base tables, got {len(base_codes)}")
+        for i, c in enumerate([*base_codes, signature_codes]):
+            fo._check_codes(c, self.format, f"codes {i}" if i < 16 else SIGNATURE_CODES_KEY)
+        if table_params.dtype != torch.float32 or tuple(table_params.shape) != (17, 2):
+            raise ValueError(f"{TABLE_PARAMS_KEY}: expected a float32 [17, 2] tensor, got {table_params.dtype} {tuple(table_params.shape)}")
+        grid = self._buffers.pop("density_grid")                       # not part of the checkpoint: kept as a plain zero buffer
+        self.register_buffer("density_grid", grid, persistent=False)
+        self.encoder = _CodesList(base_codes)
+        self.signature = _Codes(signature_codes)
+        self.register_buffer(TABLE_PARAMS_KEY, table_params.contiguous())
+        self.sigma_net = _Params(sigma_params)
+        self.color_net = _Params(color_params)
+        for name, value in (buffers or {}).items():
+            setattr(self, name, value)
+        self.mean_count, self.mean_density = mean_count, mean_density
+        self._packed_cache = None
+
+    def _packed(self):
+        sp, cp = self.sigma_net.params, self.color_net.params
+        key = (sp.data_ptr(), sp._version, cp.data_ptr(), cp._version)
+        if self._packed_cache is None or self._packed_cache[0] != key:
+            self._packed_cache = (key, fo.pack_weights(sp, cp))
+        return self._packed_cache[1]
+
+    # ------------------------------------------------------------------ the field (packed encoder, then the MLP launches over its plane set)
+
+    def forward(self, x, d, message=None, fixed=None, twin=False):
+        if twin:
+            raise NotImplementedError("clean_twin on a released model: it holds no clean field apart from the signed one (render the source model)")
+        if fixed is not None:
+            raise NotImplementedError("fixed= points on a packed released model: kept base planes belong to the training step (render the fp32 model, or unpack())")
+        return fo.field_forward_packed(x, d, self.bound, self.encoder.codes(), self.signature.codes, self.format, self.table_params, self._packed())
+
+    def _eval_field_rows(self, capacity, message):
+        return fo.field_rows_runner_packed(capacity, self.bound, self.encoder.codes(), self.signature.codes, self.format, self.table_params, self._packed())
+
+    def run(self, *args, **kwargs):
+        raise NotImplementedError("a released model on the uniform-sample `run` path (cuda_ray=False): its re-sampled points are evaluated without the message "
+                                  "(renderer_wtmk.py:187), which needs the clean field a released model does not hold; it renders on the occupancy-grid path")
+
+    def render(self, rays_o, rays_d, staged=False, max_ray_batch=4096, **kwargs):
+        """{"image", "depth"(, "weights_sum")}: ReleasedModel.render's contract.  Takes no message."""
+        message = kwargs.get("message")
+        if (torch.is_tensor(staged) and staged.dim() == 2) or (message is not None and is_multi_message(message)):
+            raise NotImplementedError("a render under K messages [K, D] on a packed released model: it carries ONE signature and takes no message")
+        if "message" in kwargs or torch.is_tensor(staged) or staged not in (False, True):
+            raise TypeError("PackedReleasedModel.render takes no message: the model carries one signature (release(model, message))")
+        if kwargs.get("clean_twin"):
+            raise NotImplementedError("clean_twin on a released model: it holds no clean field apart from the signed one (render the source model)")
+        if torch.is_grad_enabled():
+            raise RuntimeError("a released model is inference only (forward, no gradients): call render under torch.no_grad()")
+        return super().render(rays_o, rays_d, None, staged=staged, max_ray_batch=max_ray_batch, **kwargs)
+
+    def tamper(self):
+        raise NotImplementedError("tamper() on a packed released model: the tampering kernels rewrite fp32 tensors -- unpack() it and tamper the ReleasedModel")
+
+    def update_extra_state(self, *args, **kwargs):
+        raise NotImplementedError("update_extra_state on a packed released model: it does not carry the fp32 density grid (only the bitfield the render reads)")
+
+    def mark_untrained_grid(self, *args, **kwargs):
+        raise NotImplementedError("mark_untrained_grid on a packed released model: it does not carry the fp32 density grid (only the bitfield the render reads)")
+
+    # ------------------------------------------------------------------ back to fp32, checkpoint
+
+    def _all_codes(self):
+        return [*self.encoder.codes(), self.signature.codes]
+
+    def unpack(self):
+        """The ReleasedModel with the decoded fp32 tables (pk_unpack_tables; a CPU model: the same arithmetic with torch operators) and this model's own MLP vectors
+        and buffers; its density grid is the zero grid."""
+        codes = self._all_codes()
+        with torch.no_grad():
+            tables = fo.unpack_tables(codes, self.format, self.table_params) if codes[0].is_cuda else fo.unpack_tables_cpu(codes, self.format, self.table_params)
+        buffers = {"aabb_train": self.aabb_train, "aabb_infer": self.aabb_infer, "density_grid": self.density_grid, "density_bitfield": self.density_bitfield,
+                   "step_counter": self.step_counter.detach().clone()}
+        out = ReleasedModel(tables[:16], tables[16], self.sigma_net.params.detach(), self.color_net.params.detach(), {k: getattr(self, k) for k in _SCALARS}, buffers,
+                            mean_count=self.mean_count, mean_density=self.mean_density)
+        out.iter_density, out.local_step = self.iter_density, self.local_step
+        out.train(self.training)
+        return out
+
+    def save(self, path):
+        """ReleasedModel.save's dict with the packed keys; 'release' gains 'format'.  No fp32 density grid."""
+        os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+        torch.save({"model": {k: v.detach().cpu() for k, v in self.state_dict().items()}, "mean_count": self.mean_count, "mean_density": self.mean_density,
+                    "release": {**{k: getattr(self, k) for k in _SCALARS}, "format": self.format}}, path)
+        return path
+
+    @classmethod
+    def load(cls, path_or_dict, device=None):
+        ckpt = torch.load(path_or_dict, map_location="cpu", weights_only=False) if isinstance(path_or_dict, (str, os.PathLike)) else path_or_dict
+        sd, rel = ckpt["model"], ckpt.get("release", {})
+        if SIGNATURE_CODES_KEY not in sd or "format" not in rel:
+            raise ValueError("not a packed released model" + (": this is an fp32 release, load it with ReleasedModel.load (and pack() it)" if SIGNATURE_KEY in sd else
+                                                              f": the checkpoint has no '{SIGNATURE_CODES_KEY}'"))
+        to = (lambda t: t.to(device)) if device is not None else (lambda t: t)
+        base = [to(sd[f"encoder.embeddings.{i}.codes"]) for i in range(16)]
+        model = cls(base, to(sd[SIGNATURE_CODES_KEY]), to(sd[TABLE_PARAMS_KEY].float()), rel["format"], to(sd["sigma_net.params"].float()),
+                    to(sd["color_net.params"].float()), rel, mean_count=ckpt.get("mean_count", 0), mean_density=ckpt.get("mean_density", 0))
+        if device is not None:
+            model.to(device)
+        missing, unexpected = model.load_state_dict({k: to(v) for k, v in sd.items()}, strict=False)
+        if unexpected or missing:
+            raise ValueError(f"packed released checkpoint with unexpected keys {list(unexpected)} or missing keys {list(missing)}")
+        return model.train()
+
+
+def pack(released, format):
+    """The packed form of a ReleasedModel (see PackedReleasedModel): format "f16" | "q8" | "q4".  A CUDA model: tm_stats, then ONE pk_pack_tables pass over the 17
+    tables, then one host read of the non-finite word; a CPU model (format conversion without a GPU, the CPU tests): the same arithmetic with torch operators, bit
+    for bit.  The MLP vectors, the bitfield and the other buffers are the release's own tensors; the fp32 density grid is not carried.  A table with a value
+    that is not finite cannot be coded by the q formats: ValueError."""
+    if isinstance(released, PackedReleasedModel):
+        raise ValueError("pack: the model is packed already (unpack() it to change the format)")
+    if not isinstance(released, ReleasedModel):
+        raise TypeError("pack takes a ReleasedModel (release(model, message)): the unreleased model carries 2 D codebook tables, not one signature")
+    format = fo.pack_format(format)
+    tables = [*released.encoder.tables(), released.signature.weight]
+    with torch.no_grad():
+        if tables[0].is_cuda:
+            codes, params, bad = fo.pack_tables(tables, format)
+            bad = int(bad.item())                                     # (the one host read)
+        else:
+            codes, params, bad = fo.pack_tables_cpu(tables, format)
+    if bad:
+        raise ValueError(f"pack: {bad} table value(s) are not finite and have no {format} code (f16 stores them; q8 / q4 cannot)")
+    buffers = {"aabb_train": released.aabb_train, "aabb_infer": released.aabb_infer, "density_bitfield": released.density_bitfield,
+               "step_counter": released.step_counter.detach().clone()}
+    out = PackedReleasedModel(codes[:16], codes[16], params, format, released.sigma_net.params.detach(), released.color_net.params.detach(),
+                              {k: getattr(released, k) for k in _SCALARS}, buffers, mean_count=released.mean_count, mean_density=released.mean_density)
+    if released.density_grid.device != out.density_grid.device:
+        out.density_grid = out.density_grid.to(released.density_grid.device)
+    out.iter_density, out.local_step = released.iter_density, released.local_step
+    out.train(released.training)
     return out
 
 
@@ -300,13 +476,13 @@ def p_value(D, k):
 
 @torch.no_grad()
 def verify(render, key):
-    """Does the model behind `render` carry the key's message?  render: a ReleasedModel, or ANY callable (rays_o, rays_d) -> image [..., 3] over the key's block
+    """Does the model behind `render` carry the key's message?  render: a ReleasedModel, a PackedReleasedModel, or ANY callable (rays_o, rays_d) -> image [..., 3] over the key's block
     rays [D, bh, bw, 3] (black-box verification of a suspect model).  The image is clamped to [0, 1] and goes through the decoder path of every evaluation
     (trainer.eval_step); bits = sign of the logits.  One host read.
     -> {"bits": [D] of 0/1, "matches": k, "bit_accuracy": k / D, "p_value": the chance of >= k matches from a model that knows nothing of the message}"""
     device = next(render.parameters()).device if isinstance(render, nn.Module) else None
     o, d = key.block_rays(device if device is not None else "cuda")
-    if isinstance(render, ReleasedModel):
+    if isinstance(render, (ReleasedModel, PackedReleasedModel)):
         image = render.render(o, d, staged=False, perturb=False, force_all_rays=True, **key.render_kwargs)["image"]
     else:
         image = render(o, d)
