@@ -238,6 +238,21 @@ int rg_sample_rays_weighted_rgba(const float *poses, uint32_t P, const float *im
                                  float *rays_o, float *rays_d, float *gt, float *bg_out, int64_t *inds_out, int32_t *pose_out, int64_t *inds_coarse_out,
                                  float *keys_out, nsig_stream_t stream);
 
+/* rg_sample_rays / rg_sample_rays_weighted over a uint8 store: images [P,H*W,channels] uint8 as the image files hold them (channels 3 or 4: a quarter of the
+ * float store's bytes), decoded on the drawn pixels only.  A colour code q becomes decode ? decode[q] : (float)q / 255.0f (decode: a DEVICE float[256], e.g. an
+ * sRGB -> linear table, or NULL); alpha is always (float)q / 255.0f.  The division is the IEEE one the reference's loader does up front (nerf/provider.py:221);
+ * q * (1/255) has other bits for 126 of the 256 codes.  Every output -- rays, inds_out, pose_out, inds_coarse_out, keys_out, bg_out, gt -- has the bits the float
+ * entry points write from the store that division yields (or decode[images]) for the same (seed, step).  channels == 4: bg_out [N,3] is required, gt is the blend,
+ * a pixel is one aligned 4-byte load (images must be 4-byte aligned).  channels == 3: bg_out must be NULL; a pixel is three byte loads at any address.  No load
+ * leaves [images, images + P*H*W*channels). */
+int rg_sample_rays_u8(const float *poses, uint32_t P, const uint8_t *images, uint32_t channels, const float *decode, float fx, float fy, float cx, float cy,
+                      uint32_t H, uint32_t W, uint32_t N, const int32_t *step_counter, uint32_t stride, uint32_t offset, uint64_t seed, float *rays_o,
+                      float *rays_d, float *gt, float *bg_out, int64_t *inds_out, int32_t *pose_out, nsig_stream_t stream);
+int rg_sample_rays_weighted_u8(const float *poses, uint32_t P, const uint8_t *images, uint32_t channels, const float *decode, float fx, float fy, float cx,
+                               float cy, uint32_t H, uint32_t W, uint32_t N, const int32_t *step_counter, uint32_t stride, uint32_t offset, uint64_t seed,
+                               const float *error_map, uint32_t grid, float *rays_o, float *rays_d, float *gt, float *bg_out, int64_t *inds_out,
+                               int32_t *pose_out, int64_t *inds_coarse_out, float *keys_out, nsig_stream_t stream);
+
 /* The map's update behind a step's loss (nerf/utils.py:534-556): error_map[*pose_dev][inds_coarse[n]] = 0.1 * old + 0.9 * e_n with
  * e_n = mean over the 3 channels of (pred[n] - gt[n])^2; pred, gt [N,3]; pose_dev: the DEVICE word rg_sample_rays_weighted wrote.  The cells of one draw
  * are distinct (plain stores); a non-finite e_n leaves its cell unchanged. */

@@ -174,27 +174,62 @@ __global__ void k_blend_random_background(const float4 *__restrict__ rgba, uint3
     blend_random_background(rgba[n], draw_base(seed_lo, seed_hi, step, kBackgroundStream), n, bg_out, gt_out);
 }
 
+// The image store a sampler draws from, as the pixel fetch of write_sampled_ray: float32 pixels as they are stored, or uint8 codes decoded on the fetch
+// (the reference decodes a whole dataset up front, nerf/provider.py:221 image.astype(np.float32) / 255: the same IEEE division, here on the drawn pixels only,
+// so a sampler over a u8 store writes the bits of the float sampler over store.float() / 255).  pixel < P * H * W: no fetch leaves [px, px + P*H*W*channels).
+struct FloatStore {
+    static constexpr uint32_t kRgbaAlign = 16;                    // one 16-byte load per RGBA pixel
+    const float *__restrict__ px;
+    __device__ float4 rgba(size_t pixel) const { return reinterpret_cast<const float4 *>(px)[pixel]; }
+    __device__ void rgb(size_t pixel, float (&c)[3]) const { c[0] = px[3 * pixel]; c[1] = px[3 * pixel + 1]; c[2] = px[3 * pixel + 2]; }
+};
+struct U8Store {
+    static constexpr uint32_t kRgbaAlign = 4;                     // one 4-byte load per RGBA pixel
+    const uint8_t *__restrict__ px;
+    const float *__restrict__ decode;                             // float[256] for the colour codes (a colour-space table), or NULL: q / 255
+    __device__ static float unit(uint32_t q) { return __fdiv_rn((float)q, 255.0f); }           // (q * (1/255) has other bits for 126 of the 256 codes)
+    // the three colour codes of a pixel at once: one uniform branch, the table's three loads (or the three divisions) side by side
+    __device__ void colours(uint32_t q0, uint32_t q1, uint32_t q2, float (&c)[3]) const {
+        if (decode != nullptr) { c[0] = decode[q0]; c[1] = decode[q1]; c[2] = decode[q2]; }
+        else { c[0] = unit(q0); c[1] = unit(q1); c[2] = unit(q2); }
+    }
+    __device__ float4 rgba(size_t pixel) const {
+        const uint32_t w = reinterpret_cast<const uint32_t *>(px)[pixel];
+        float c[3];
+        colours(w & 255u, (w >> 8) & 255u, (w >> 16) & 255u, c);
+        return make_float4(c[0], c[1], c[2], unit(w >> 24));
+    }
+    // three byte loads at any of the four byte phases of 3 * pixel, issued together: the words around a pixel reach past both ends of the store (its first and its
+    // last pixel), and the launch is bound by its latency, not by its loads (tools/store_bench.py)
+    __device__ void rgb(size_t pixel, float (&c)[3]) const {
+        const uint8_t *b = px + 3 * pixel;
+        const uint32_t q0 = b[0], q1 = b[1], q2 = b[2];
+        colours(q0, q1, q2, c);
+    }
+};
+
 // Ray n of a drawn batch: pixel `ind` of pose p -- the ray arithmetic of k_get_rays, the stored pixel as ground truth.  Shared by both samplers.
-// RGBA: the store holds [P, H*W, 4] (one 16-byte load per pixel); the ray's background colour goes to bg_out and the ground truth is the blend against it.
-template <bool RGBA>
-__device__ inline void write_sampled_ray(const float *__restrict__ poses, const float *__restrict__ images, float fx, float fy, float cx, float cy, uint32_t H,
+// RGBA: the store holds [P, H*W, 4] (one load per pixel); the ray's background colour goes to bg_out and the ground truth is the blend against it.
+template <bool RGBA, class Store>
+__device__ inline void write_sampled_ray(const float *__restrict__ poses, Store store, float fx, float fy, float cx, float cy, uint32_t H,
                                          uint32_t W, uint32_t p, uint32_t ind, uint32_t n, float *__restrict__ rays_o, float *__restrict__ rays_d,
                                          float *__restrict__ gt, int64_t *__restrict__ inds_out, uint32_t bg_base, float *__restrict__ bg_out) {
     const float i = (float)(ind % W) + 0.5f, j = (float)(ind / W) + 0.5f;                      // as k_get_rays
     pixel_ray(poses + 16 * (size_t)p, fx, fy, cx, cy, i, j, rays_o + 3 * (size_t)n, rays_d + 3 * (size_t)n);
     if constexpr (RGBA) {
-        blend_random_background(reinterpret_cast<const float4 *>(images)[(size_t)p * H * W + ind], bg_base, n, bg_out, gt);
+        blend_random_background(store.rgba((size_t)p * H * W + ind), bg_base, n, bg_out, gt);
     } else {
         if (gt != nullptr) {
-            const float *px = images + 3 * ((size_t)p * H * W + ind);
-            gt[3 * (size_t)n] = px[0]; gt[3 * (size_t)n + 1] = px[1]; gt[3 * (size_t)n + 2] = px[2];
+            float c[3];
+            store.rgb((size_t)p * H * W + ind, c);
+            gt[3 * (size_t)n] = c[0]; gt[3 * (size_t)n + 1] = c[1]; gt[3 * (size_t)n + 2] = c[2];
         }
     }
     if (inds_out != nullptr) inds_out[n] = (int64_t)ind;
 }
 
-template <bool RGBA>
-__global__ void k_sample_rays(const float *__restrict__ poses, uint32_t P, const float *__restrict__ images, float fx, float fy, float cx, float cy,
+template <bool RGBA, class Store>
+__global__ void k_sample_rays(const float *__restrict__ poses, uint32_t P, Store store, float fx, float fy, float cx, float cy,
                               uint32_t H, uint32_t W, uint32_t N, const int32_t *__restrict__ step_counter, uint32_t stride, uint32_t offset,
                               uint32_t seed_lo, uint32_t seed_hi, float *__restrict__ rays_o, float *__restrict__ rays_d, float *__restrict__ gt,
                               int64_t *__restrict__ inds_out, int32_t *__restrict__ pose_out, float *__restrict__ bg_out) {
@@ -204,7 +239,7 @@ __global__ void k_sample_rays(const float *__restrict__ poses, uint32_t P, const
     const uint32_t p = (uint32_t)(((uint64_t)step * stride + offset) % P);
     const uint32_t r = draw_word(draw_base(seed_lo, seed_hi, step, 0u), n);
     const uint32_t ind = (uint32_t)(((uint64_t)r * ((uint64_t)H * W)) >> 32);                  // uniform in [0, H*W)
-    write_sampled_ray<RGBA>(poses, images, fx, fy, cx, cy, H, W, p, ind, n, rays_o, rays_d, gt, inds_out,
+    write_sampled_ray<RGBA>(poses, store, fx, fy, cx, cy, H, W, p, ind, n, rays_o, rays_d, gt, inds_out,
                             RGBA ? draw_base(seed_lo, seed_hi, step, kBackgroundStream) : 0u, bg_out);
     if (pose_out != nullptr && n == 0) pose_out[0] = (int32_t)p;
 }
@@ -263,9 +298,9 @@ __global__ void k_sample_rays_orbit(float fx, float fy, float cx, float cy, uint
 constexpr uint32_t kWeightedThreads = 1024, kWeightedWaves = kWeightedThreads / 64, kMaxErrorGrid = 128, kMaxKeysPerLane = kMaxErrorGrid * kMaxErrorGrid / kWeightedThreads;
 constexpr uint32_t kHistCopies = 32;
 
-template <bool RGBA>
+template <bool RGBA, class Store>
 __global__ __launch_bounds__(kWeightedThreads) void k_sample_rays_weighted(
-    const float *__restrict__ poses, uint32_t P, const float *__restrict__ images, float fx, float fy, float cx, float cy, uint32_t H, uint32_t W, uint32_t N,
+    const float *__restrict__ poses, uint32_t P, Store store, float fx, float fy, float cx, float cy, uint32_t H, uint32_t W, uint32_t N,
     const int32_t *__restrict__ step_counter, uint32_t stride, uint32_t offset, uint32_t seed_lo, uint32_t seed_hi, const float *__restrict__ error_map, uint32_t G,
     float *__restrict__ rays_o, float *__restrict__ rays_d, float *__restrict__ gt, int64_t *__restrict__ inds_out, int32_t *__restrict__ pose_out,
     int64_t *__restrict__ inds_coarse_out, float *__restrict__ keys_out, float *__restrict__ bg_out) {
@@ -371,7 +406,7 @@ __global__ __launch_bounds__(kWeightedThreads) void k_sample_rays_weighted(
         const uint32_t c = drawn[n];
         const float u1 = (float)(draw_word(row_base, n) >> 8) * (1.0f / 16777216.0f), u2 = (float)(draw_word(col_base, n) >> 8) * (1.0f / 16777216.0f);   // [0, 1)
         const uint32_t row = min(H - 1u, (uint32_t)((float)(c / G) * sx + u1 * sx)), col = min(W - 1u, (uint32_t)((float)(c % G) * sy + u2 * sy));
-        write_sampled_ray<RGBA>(poses, images, fx, fy, cx, cy, H, W, p, row * W + col, n, rays_o, rays_d, gt, inds_out, bg_base, bg_out);
+        write_sampled_ray<RGBA>(poses, store, fx, fy, cx, cy, H, W, p, row * W + col, n, rays_o, rays_d, gt, inds_out, bg_base, bg_out);
     }
     if (pose_out != nullptr && tid == 0u) pose_out[0] = (int32_t)p;
 }
@@ -1604,18 +1639,18 @@ NSIG_EXPORT int rm_eval_compact(uint32_t *ctl, uint32_t N, uint32_t max_steps, c
     return check_launch("rm_eval_compact");
 }
 
-// rg_sample_rays / rg_sample_rays_rgba: one body, the store's channel count as the kernel's template argument
-template <bool RGBA>
-static int sample_rays(const char *name, const float *poses, uint32_t P, const float *images, float fx, float fy, float cx, float cy, uint32_t H, uint32_t W, uint32_t N,
+// rg_sample_rays / rg_sample_rays_rgba / rg_sample_rays_u8: one body, the store's channel count and its pixel fetch as the kernel's template arguments
+template <bool RGBA, class Store>
+static int sample_rays(const char *name, const float *poses, uint32_t P, Store store, float fx, float fy, float cx, float cy, uint32_t H, uint32_t W, uint32_t N,
                        const int32_t *step_counter, uint32_t stride, uint32_t offset, uint64_t seed, float *rays_o, float *rays_d, float *gt, int64_t *inds_out,
                        int32_t *pose_out, float *bg_out, nsig_stream_t stream) {
     if (N == 0) return NSIG_OK;
-    NSIG_REQUIRE(poses && rays_o && rays_d && (!RGBA || (images && bg_out)), "%s: null pointer", name);
+    NSIG_REQUIRE(poses && rays_o && rays_d && (!RGBA || (store.px && bg_out)), "%s: null pointer", name);
     NSIG_REQUIRE(P > 0 && H > 0 && W > 0 && fx != 0.0f && fy != 0.0f, "%s: empty pose store, bad image size or focal length", name);
-    NSIG_REQUIRE(gt == nullptr || images != nullptr, "%s: ground truth requested without an image store", name);
+    NSIG_REQUIRE(gt == nullptr || store.px != nullptr, "%s: ground truth requested without an image store", name);
     NSIG_REQUIRE((uint64_t)H * W < (1ull << 32), "%s: image too large", name);
-    NSIG_REQUIRE(!RGBA || aligned16(images), "%s: the RGBA store must be 16-byte aligned", name);
-    k_sample_rays<RGBA><<<ceil_div(N, 256u), 256, 0, as_stream(stream)>>>(poses, P, images, fx, fy, cx, cy, H, W, N, step_counter, stride, offset, (uint32_t)seed,
+    NSIG_REQUIRE(!RGBA || (Store::kRgbaAlign == 16 ? aligned16(store.px) : aligned4(store.px)), "%s: the RGBA store must be %u-byte aligned", name, Store::kRgbaAlign);
+    k_sample_rays<RGBA><<<ceil_div(N, 256u), 256, 0, as_stream(stream)>>>(poses, P, store, fx, fy, cx, cy, H, W, N, step_counter, stride, offset, (uint32_t)seed,
                                                                           (uint32_t)(seed >> 32), rays_o, rays_d, gt, inds_out, pose_out, bg_out);
     return check_launch(name);
 }
@@ -1623,15 +1658,31 @@ static int sample_rays(const char *name, const float *poses, uint32_t P, const f
 NSIG_EXPORT int rg_sample_rays(const float *poses, uint32_t P, const float *images, float fx, float fy, float cx, float cy, uint32_t H, uint32_t W,
                                uint32_t N, const int32_t *step_counter, uint32_t stride, uint32_t offset, uint64_t seed, float *rays_o, float *rays_d,
                                float *gt, int64_t *inds_out, int32_t *pose_out, nsig_stream_t stream) {
-    return sample_rays<false>("rg_sample_rays", poses, P, images, fx, fy, cx, cy, H, W, N, step_counter, stride, offset, seed, rays_o, rays_d, gt, inds_out, pose_out,
-                              nullptr, stream);
+    return sample_rays<false>("rg_sample_rays", poses, P, FloatStore{images}, fx, fy, cx, cy, H, W, N, step_counter, stride, offset, seed, rays_o, rays_d, gt, inds_out,
+                              pose_out, nullptr, stream);
 }
 
 NSIG_EXPORT int rg_sample_rays_rgba(const float *poses, uint32_t P, const float *images, float fx, float fy, float cx, float cy, uint32_t H, uint32_t W,
                                     uint32_t N, const int32_t *step_counter, uint32_t stride, uint32_t offset, uint64_t seed, float *rays_o, float *rays_d,
                                     float *gt, float *bg_out, int64_t *inds_out, int32_t *pose_out, nsig_stream_t stream) {
-    return sample_rays<true>("rg_sample_rays_rgba", poses, P, images, fx, fy, cx, cy, H, W, N, step_counter, stride, offset, seed, rays_o, rays_d, gt, inds_out,
-                             pose_out, bg_out, stream);
+    return sample_rays<true>("rg_sample_rays_rgba", poses, P, FloatStore{images}, fx, fy, cx, cy, H, W, N, step_counter, stride, offset, seed, rays_o, rays_d, gt,
+                             inds_out, pose_out, bg_out, stream);
+}
+
+// the u8 entry points: `channels` picks the template argument the float entry points carry in their names; bg_out goes with an alpha channel, and only with one
+#define NSIG_REQUIRE_U8_STORE(name)                                                                                                        \
+    NSIG_REQUIRE(channels == 3 || channels == 4, name ": a u8 store holds 3 or 4 channels, not %u", channels);                             \
+    NSIG_REQUIRE((channels == 4) == (bg_out != nullptr), name ": bg_out belongs to a 4-channel store, and is required there")
+
+NSIG_EXPORT int rg_sample_rays_u8(const float *poses, uint32_t P, const uint8_t *images, uint32_t channels, const float *decode, float fx, float fy, float cx, float cy,
+                                  uint32_t H, uint32_t W, uint32_t N, const int32_t *step_counter, uint32_t stride, uint32_t offset, uint64_t seed, float *rays_o,
+                                  float *rays_d, float *gt, float *bg_out, int64_t *inds_out, int32_t *pose_out, nsig_stream_t stream) {
+    NSIG_REQUIRE_U8_STORE("rg_sample_rays_u8");
+    const U8Store store{images, decode};
+    return channels == 4 ? sample_rays<true>("rg_sample_rays_u8", poses, P, store, fx, fy, cx, cy, H, W, N, step_counter, stride, offset, seed, rays_o, rays_d, gt, inds_out,
+                                             pose_out, bg_out, stream)
+                         : sample_rays<false>("rg_sample_rays_u8", poses, P, store, fx, fy, cx, cy, H, W, N, step_counter, stride, offset, seed, rays_o, rays_d, gt, inds_out,
+                                              pose_out, nullptr, stream);
 }
 
 NSIG_EXPORT int rg_sample_rays_orbit(float fx, float fy, float cx, float cy, uint32_t H, uint32_t W, uint32_t N, const int32_t *step_counter, uint32_t stride,
@@ -1648,19 +1699,19 @@ NSIG_EXPORT int rg_sample_rays_orbit(float fx, float fy, float cx, float cy, uin
     return check_launch("rg_sample_rays_orbit");
 }
 
-template <bool RGBA>
-static int sample_rays_weighted(const char *name, const float *poses, uint32_t P, const float *images, float fx, float fy, float cx, float cy, uint32_t H, uint32_t W,
+template <bool RGBA, class Store>
+static int sample_rays_weighted(const char *name, const float *poses, uint32_t P, Store store, float fx, float fy, float cx, float cy, uint32_t H, uint32_t W,
                                 uint32_t N, const int32_t *step_counter, uint32_t stride, uint32_t offset, uint64_t seed, const float *error_map, uint32_t grid,
                                 float *rays_o, float *rays_d, float *gt, int64_t *inds_out, int32_t *pose_out, int64_t *inds_coarse_out, float *keys_out,
                                 float *bg_out, nsig_stream_t stream) {
-    NSIG_REQUIRE(poses && rays_o && rays_d && error_map && inds_coarse_out && (!RGBA || (images && bg_out)), "%s: null pointer", name);
+    NSIG_REQUIRE(poses && rays_o && rays_d && error_map && inds_coarse_out && (!RGBA || (store.px && bg_out)), "%s: null pointer", name);
     NSIG_REQUIRE(P > 0 && H > 0 && W > 0 && fx != 0.0f && fy != 0.0f, "%s: empty pose store, bad image size or focal length", name);
-    NSIG_REQUIRE(gt == nullptr || images != nullptr, "%s: ground truth requested without an image store", name);
+    NSIG_REQUIRE(gt == nullptr || store.px != nullptr, "%s: ground truth requested without an image store", name);
     NSIG_REQUIRE((uint64_t)H * W < (1ull << 32), "%s: image too large", name);
-    NSIG_REQUIRE(!RGBA || aligned16(images), "%s: the RGBA store must be 16-byte aligned", name);
+    NSIG_REQUIRE(!RGBA || (Store::kRgbaAlign == 16 ? aligned16(store.px) : aligned4(store.px)), "%s: the RGBA store must be %u-byte aligned", name, Store::kRgbaAlign);
     NSIG_REQUIRE(grid >= 1 && grid <= kMaxErrorGrid, "%s: grid %u out of range (1..%u)", name, grid, kMaxErrorGrid);
     NSIG_REQUIRE(N >= 1 && N <= grid * grid, "%s: N %u out of range (1..grid * grid = %u: a draw without replacement)", name, N, grid * grid);
-    k_sample_rays_weighted<RGBA><<<1, kWeightedThreads, 0, as_stream(stream)>>>(poses, P, images, fx, fy, cx, cy, H, W, N, step_counter, stride, offset, (uint32_t)seed,
+    k_sample_rays_weighted<RGBA><<<1, kWeightedThreads, 0, as_stream(stream)>>>(poses, P, store, fx, fy, cx, cy, H, W, N, step_counter, stride, offset, (uint32_t)seed,
                                                                                 (uint32_t)(seed >> 32), error_map, grid, rays_o, rays_d, gt, inds_out, pose_out,
                                                                                 inds_coarse_out, keys_out, bg_out);
     return check_launch(name);
@@ -1670,17 +1721,30 @@ NSIG_EXPORT int rg_sample_rays_weighted(const float *poses, uint32_t P, const fl
                                         uint32_t N, const int32_t *step_counter, uint32_t stride, uint32_t offset, uint64_t seed, const float *error_map, uint32_t grid,
                                         float *rays_o, float *rays_d, float *gt, int64_t *inds_out, int32_t *pose_out, int64_t *inds_coarse_out, float *keys_out,
                                         nsig_stream_t stream) {
-    return sample_rays_weighted<false>("rg_sample_rays_weighted", poses, P, images, fx, fy, cx, cy, H, W, N, step_counter, stride, offset, seed, error_map, grid, rays_o,
-                                       rays_d, gt, inds_out, pose_out, inds_coarse_out, keys_out, nullptr, stream);
+    return sample_rays_weighted<false>("rg_sample_rays_weighted", poses, P, FloatStore{images}, fx, fy, cx, cy, H, W, N, step_counter, stride, offset, seed, error_map,
+                                       grid, rays_o, rays_d, gt, inds_out, pose_out, inds_coarse_out, keys_out, nullptr, stream);
 }
 
 NSIG_EXPORT int rg_sample_rays_weighted_rgba(const float *poses, uint32_t P, const float *images, float fx, float fy, float cx, float cy, uint32_t H, uint32_t W,
                                              uint32_t N, const int32_t *step_counter, uint32_t stride, uint32_t offset, uint64_t seed, const float *error_map,
                                              uint32_t grid, float *rays_o, float *rays_d, float *gt, float *bg_out, int64_t *inds_out, int32_t *pose_out,
                                              int64_t *inds_coarse_out, float *keys_out, nsig_stream_t stream) {
-    return sample_rays_weighted<true>("rg_sample_rays_weighted_rgba", poses, P, images, fx, fy, cx, cy, H, W, N, step_counter, stride, offset, seed, error_map, grid,
-                                      rays_o, rays_d, gt, inds_out, pose_out, inds_coarse_out, keys_out, bg_out, stream);
+    return sample_rays_weighted<true>("rg_sample_rays_weighted_rgba", poses, P, FloatStore{images}, fx, fy, cx, cy, H, W, N, step_counter, stride, offset, seed, error_map,
+                                      grid, rays_o, rays_d, gt, inds_out, pose_out, inds_coarse_out, keys_out, bg_out, stream);
 }
+
+NSIG_EXPORT int rg_sample_rays_weighted_u8(const float *poses, uint32_t P, const uint8_t *images, uint32_t channels, const float *decode, float fx, float fy, float cx,
+                                           float cy, uint32_t H, uint32_t W, uint32_t N, const int32_t *step_counter, uint32_t stride, uint32_t offset, uint64_t seed,
+                                           const float *error_map, uint32_t grid, float *rays_o, float *rays_d, float *gt, float *bg_out, int64_t *inds_out,
+                                           int32_t *pose_out, int64_t *inds_coarse_out, float *keys_out, nsig_stream_t stream) {
+    NSIG_REQUIRE_U8_STORE("rg_sample_rays_weighted_u8");
+    const U8Store store{images, decode};
+    return channels == 4 ? sample_rays_weighted<true>("rg_sample_rays_weighted_u8", poses, P, store, fx, fy, cx, cy, H, W, N, step_counter, stride, offset, seed, error_map,
+                                                      grid, rays_o, rays_d, gt, inds_out, pose_out, inds_coarse_out, keys_out, bg_out, stream)
+                         : sample_rays_weighted<false>("rg_sample_rays_weighted_u8", poses, P, store, fx, fy, cx, cy, H, W, N, step_counter, stride, offset, seed, error_map,
+                                                       grid, rays_o, rays_d, gt, inds_out, pose_out, inds_coarse_out, keys_out, nullptr, stream);
+}
+#undef NSIG_REQUIRE_U8_STORE
 
 NSIG_EXPORT int rg_blend_random_background(const float *rgba, uint32_t N, const int32_t *step_counter, uint64_t seed, float *bg_out, float *gt_out,
                                            nsig_stream_t stream) {

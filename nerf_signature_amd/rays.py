@@ -65,9 +65,15 @@ class DeviceRaySampler:
     error_map=: the pixels are drawn from a per-image map of recent errors instead (see __init__).
     RGBA images [P,H*W,4] (the Blender scenes): `channels` is 4, and every draw also writes one random background colour per ray (`bg`) and hands out the
     ground truth blended against it, gt = rgb * a + bg * (1 - a) (the reference's stage-1 train_step, nerf/utils.py:498-507) -- in the same launch
-    (rg_sample_rays_rgba / rg_sample_rays_weighted_rgba)."""
+    (rg_sample_rays_rgba / rg_sample_rays_weighted_rgba).
+    A torch.uint8 store [P,H,W,C] or [P,H*W,C] -- the bytes of the image files, a quarter of the float store -- is kept as it is and decoded on the drawn pixels
+    only (rg_sample_rays_u8 / rg_sample_rays_weighted_u8): code / 255 in IEEE division, the reference's loader (nerf/provider.py:221, numpy on the host), so every
+    draw has the bits of the draw from that loader's float store.  (On the GPU torch's `images.float() / 255` is NOT that store: a Python-scalar divisor becomes a
+    multiplication by 1/255, other bits for 126 of the 256 codes; dataset.decode_u8 divides by a tensor.)  decode= (u8 stores only): a float32 [256] table on the
+    store's device that replaces code / 255 for the colour channels (alpha stays code / 255) -- a colour space costs nothing per step: build it once with the
+    reference's own torch expression on dataset.decode_u8 of the 256 codes (Scene.linear_decode)."""
 
-    def __init__(self, poses, images, intrinsics, H, W, n_rays, stride=1, offset=0, seed=0, error_map=False, error_grid=128):
+    def __init__(self, poses, images, intrinsics, H, W, n_rays, stride=1, offset=0, seed=0, error_map=False, error_grid=128, decode=None):
         """error_map: the reference's --error_map loader (nerf/provider.py:234-238,300-321; nerf/utils.py:105-114,534-556) on the device.  True allocates a
         map of ones [P, error_grid^2]; a tensor of that shape is taken as given (and updated in place).  With a map, sample_into draws n_rays cells of the
         pose's row without replacement in proportion to their weight and one pixel inside each (rg_sample_rays_weighted), and update_error_map(pred, gt)
@@ -79,7 +85,22 @@ class DeviceRaySampler:
         if images is not None and images.shape[-1] not in (3, 4):
             raise ValueError(f"DeviceRaySampler: images must be RGB or RGBA, not {images.shape[-1]} channels")
         self.channels = 3 if images is None else int(images.shape[-1])
-        self.images = None if images is None else images.contiguous().float().view(self.poses.shape[0], H * W, self.channels)
+        if images is not None and images.dtype != torch.uint8 and not images.is_floating_point():
+            raise ValueError(f"DeviceRaySampler: images must be a float or a uint8 tensor, not {images.dtype}")
+        self.u8 = images is not None and images.dtype == torch.uint8
+        if self.u8:       # kept as stored: .float() would sample the codes as 0...255
+            self.images = images.contiguous().view(self.poses.shape[0], H * W, self.channels)
+            if self.channels == 4 and self.images.data_ptr() % 4:
+                raise ValueError("DeviceRaySampler: an RGBA uint8 store is read one 4-byte pixel at a time: its address must be 4-byte aligned")
+        else:
+            self.images = None if images is None else images.contiguous().float().view(self.poses.shape[0], H * W, self.channels)
+        if decode is not None:
+            if not self.u8:
+                raise ValueError("DeviceRaySampler: decode= belongs to a uint8 store (this one holds " + ("no images)" if images is None else "floats)"))
+            if not (torch.is_tensor(decode) and decode.dtype == torch.float32 and tuple(decode.shape) == (256,) and decode.device == self.images.device):
+                raise ValueError(f"DeviceRaySampler: decode must be a float32 tensor [256] on {self.images.device}")
+            decode = decode.contiguous()
+        self.decode = decode
         self.intr = tuple(float(v) for v in intrinsics)
         self.H, self.W, self.n_rays, self.stride, self.offset, self.seed = int(H), int(W), int(n_rays), int(stride), int(offset), int(seed)
         self.error_map, self.error_grid = None, int(error_grid)
@@ -108,6 +129,9 @@ class DeviceRaySampler:
         if self.channels != 4 and bg is not None:
             raise ValueError("DeviceRaySampler: bg= belongs to an RGBA store (this one holds RGB)")
         rgba = ("_rgba", (nv.ptr(bg),)) if self.channels == 4 else ("", ())
+        store = (nv.ptr(self.images),)
+        if self.u8:       # one entry point for both channel counts: bg_out is NULL for RGB
+            rgba, store = ("_u8", (nv.ptr(bg),)), (nv.ptr(self.images), self.channels, nv.ptr(self.decode))
         for t in (rays_o, rays_d, gt, bg):
             if t is not None and (t.numel() != self.n_rays * 3 or t.dtype != torch.float32):
                 raise ValueError(f"DeviceRaySampler: buffers must hold {self.n_rays} x 3 float32 values")
@@ -117,7 +141,7 @@ class DeviceRaySampler:
         if self.error_map is not None:
             if keys_out is not None and (keys_out.numel() != self.error_grid ** 2 or keys_out.dtype != torch.float32):
                 raise ValueError(f"DeviceRaySampler: keys_out must hold {self.error_grid ** 2} float32 values")
-            nv.call("rg_sample_rays_weighted" + rgba[0], nv.ptr(self.poses), self.poses.shape[0], nv.ptr(self.images), fx, fy, cx, cy, self.H, self.W, self.n_rays,
+            nv.call("rg_sample_rays_weighted" + rgba[0], nv.ptr(self.poses), self.poses.shape[0], *store, fx, fy, cx, cy, self.H, self.W, self.n_rays,
                     nv.ptr(step_counter), self.stride, self.offset, self.seed, nv.ptr(self.error_map), self.error_grid, nv.ptr(rays_o), nv.ptr(rays_d), nv.ptr(gt),
                     *rgba[1], nv.ptr(inds_out), nv.ptr(self.pose_word), nv.ptr(self.inds_coarse), nv.ptr(keys_out), nv.stream())
             if pose_out is not None:
@@ -125,7 +149,7 @@ class DeviceRaySampler:
             return
         if keys_out is not None:
             raise ValueError("DeviceRaySampler: keys_out belongs to the error-map draw")
-        nv.call("rg_sample_rays" + rgba[0], nv.ptr(self.poses), self.poses.shape[0], nv.ptr(self.images), fx, fy, cx, cy, self.H, self.W, self.n_rays,
+        nv.call("rg_sample_rays" + rgba[0], nv.ptr(self.poses), self.poses.shape[0], *store, fx, fy, cx, cy, self.H, self.W, self.n_rays,
                 nv.ptr(step_counter), self.stride, self.offset, self.seed, nv.ptr(rays_o), nv.ptr(rays_d), nv.ptr(gt), *rgba[1], nv.ptr(inds_out), nv.ptr(pose_out),
                 nv.stream())
 
