@@ -3,7 +3,9 @@
 The device-selected pass (opt_codebook_adam_sel / opt_codebook_adam_sel_next) resolves the message once per wave and walks the D selected tables through
 four register slots, two columns half a table apart per thread; opt_codebook_adam (k_codebook_adam) takes the selected tables and their two scalars from the host and walks them one by one.  Both
 apply adam_update4 to the same operands, so for the same tables and the same scalars every parameter and both moments must be EQUAL -- for every D % 4,
-for D below one trip, and at the workload's D = 32; the unselected tables must not be touched, the step counts advance for the selected tables only, and
+for D below one trip, at the workload's D = 32, for every shape of the walk's end (D = 9 .. 13: one full trip, then a tail that still issues requests and runs a
+second tail trip; D = 12: two full trips) and above 32 up to the limit of 64, where the selection uses lanes 32 .. 63 of the ballot masks, readlane indices from 32
+on and the upper half of the 64-bit masks; the unselected tables must not be touched, the step counts advance for the selected tables only, and
 S_next must equal opt_codebook_presum_sel over the updated tables.  A disagreement is a bug in the pipeline's body, not a tolerance question."""
 import ctypes
 
@@ -14,9 +16,9 @@ import torch
 pytestmark = pytest.mark.gpu
 
 T = 1 << 19                      # NSIG_TABLE_ROWS: the table size is the library's compile-time constant, so "small" means few tables
-D_MAX = 32
+D_MAX = 64                       # NSIG_MAX_MESSAGE_DIM
 BETA1, BETA2, EPS, LR, GRAD_SCALE = 0.9, 0.99, 1e-15, 1e-2, 0.5
-DS = (1, 2, 3, 4, 5, 7, 8, 32)
+DS = (1, 2, 3, 4, 5, 7, 8, 32, 6, 9, 11, 12, 13, 33, 48, 63, 64)
 KINDS = ("same", "complement", "alternating", "random")
 
 
@@ -44,8 +46,9 @@ def state():
     for it in (1, 2):
         G = torch.randn(T, 2, device="cuda", generator=gen) * (0.1 ** it)
         G[::5] = 0                                        # rows no ray touched
-        ss, ib = zip(*(_scalars(it) for _ in range(n)))
-        _host_adam(nv, G, p, m, v, ss, ib, 1.0)
+        for first in range(0, n, D_MAX):                  # (the host-selected pass takes at most D_MAX tables)
+            ss, ib = zip(*(_scalars(it) for _ in range(D_MAX)))
+            _host_adam(nv, G, p[first:first + D_MAX], m[first:first + D_MAX], v[first:first + D_MAX], ss, ib, 1.0)
     steps = [float(2 + (7 * t) % 11) for t in range(n)]   # the counts differ per table
     G = torch.randn(T, 2, device="cuda", generator=gen) * 1e-3
     G[::3] = 0
@@ -59,6 +62,8 @@ def _messages(D, kind):
         cur, nxt = rs.randint(0, 2, D), rs.randint(0, 2, D)
     else:
         cur = np.arange(D) % 2 if kind == "alternating" else np.random.RandomState(7 * D).randint(0, 2, D)
+        if D > 32:
+            cur[32] = 1                                   # (D = 33: the one bit of the masks' upper half is set)
         nxt = {"same": cur, "complement": 1 - cur, "alternating": (np.arange(D) // 2) % 2}[kind]     # alternating: 0101.. then 0011..: partner rows at bits 1, 2 of every 4
     return cur.astype(np.float32), nxt.astype(np.float32)
 
@@ -71,6 +76,8 @@ def test_device_selected_pipeline_equals_host_selected_pass(state, D, kind, with
     from nerf_signature_amd import fieldops as fo
     n = 2 * D
     cur, nxt = _messages(D, kind)
+    if D > 32:
+        assert cur[32:].any(), "no selected bit in the upper half of the 64-bit masks"
     p, m, v = ([t.clone() for t in state[k][:n]] for k in ("p", "m", "v"))
     steps = [torch.tensor(s, device="cuda") for s in state["steps"][:n]]
     msg, nmsg = torch.from_numpy(cur).cuda(), torch.from_numpy(nxt).cuda()
