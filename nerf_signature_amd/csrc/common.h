@@ -68,6 +68,9 @@ __host__ __device__ inline uint32_t ceil_div(uint32_t a, uint32_t b) { return (a
 
 __device__ inline float clampf(float v, float lo, float hi) { return fminf(hi, fmaxf(lo, v)); }
 
+// d (grad_scale * mean of n squared differences) / d difference, per unit of difference: the seed factor of clean_loss and of rm_composite_train_mse
+__host__ __device__ inline float mse_seed_factor(float grad_scale, uint32_t n) { return grad_scale * 2.0f / (float)n; }
+
 // 10-bit-per-axis bit interleave (x -> bit 0, y -> bit 1, z -> bit 2 of every triple).
 __host__ __device__ inline uint32_t spread3(uint32_t v) {
     v = (v * 0x00010001u) & 0xFF0000FFu;

@@ -1,36 +1,11 @@
-// The elementwise tails of the render and the losses of the watermark training step, each as one kernel per direction.
+// The losses of the watermark training step, one kernel per direction, and the opening kernel of a captured step.
 //
 // On this path a "tensor" is a few thousand rays, so every stock elementwise/reduction operator is a ~3 us launch and the
-// reference's op chains (renderer_wtmk.py:316-319: background mix and depth normalisation; utils_wtmk_disen.py:615-640:
+// reference's op chains (renderer_wtmk.py:316-319: background mix and depth normalisation, csrc/composite.hip; utils_wtmk_disen.py:615-640:
 // MSE + BCE-with-logits + weighted sum, and their autograd backward) come to ~60 launches per step: 0.2 ms of a 1.8 ms step.
 #include "wave.h"
 
 namespace nsig {
-
-// renderer_wtmk.py:316-319 / 369-372.
-__global__ void __launch_bounds__(256) k_finish_fwd(const float *__restrict__ image, const float *__restrict__ depth, const float *__restrict__ ws,
-                                                    const float *__restrict__ nears, const float *__restrict__ fars, const float *__restrict__ bg,
-                                                    uint32_t bg_stride, uint32_t N, float *__restrict__ image_out, float *__restrict__ depth_out) {
-    const uint32_t i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= N) return;
-    const float rest = 1.0f - ws[i];
-#pragma unroll
-    for (int c = 0; c < 3; ++c) image_out[i * 3 + c] = image[i * 3 + c] + rest * bg[i * bg_stride + c];
-    depth_out[i] = fmaxf(depth[i] - nears[i], 0.0f) / (fars[i] - nears[i]);   // NaN for rays that miss the box, as the reference
-}
-
-__global__ void __launch_bounds__(256) k_finish_bwd(const float *__restrict__ g_image, const float *__restrict__ g_depth, const float *__restrict__ depth,
-                                                    const float *__restrict__ nears, const float *__restrict__ fars, const float *__restrict__ bg,
-                                                    uint32_t bg_stride, uint32_t N, float *__restrict__ g_ws, float *__restrict__ g_depth_in) {
-    const uint32_t i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= N) return;
-    float s = 0.0f;
-    if (g_image)
-#pragma unroll
-        for (int c = 0; c < 3; ++c) s += g_image[i * 3 + c] * bg[i * bg_stride + c];
-    g_ws[i] = -s;
-    if (g_depth_in) g_depth_in[i] = (g_depth && depth[i] - nears[i] >= 0.0f) ? g_depth[i] / (fars[i] - nears[i]) : 0.0f;
-}
 
 // loss_i = mean((content - gt)^2); loss_w = mean BCE-with-logits(temp * decoded, message); loss = lambda_w*loss_w + lambda_i*loss_i.
 // One workgroup; also leaves the two gradient directions d(loss_i)/d(content), d(loss_w)/d(decoded) for the backward kernel.
@@ -111,24 +86,6 @@ NSIG_EXPORT int loop_step_begin(float *G, uint32_t n_floats, const float *ring_d
     k_step_begin<<<ceil_div(n4 > 0 ? n4 : 1u, 256u), 256, 0, as_stream(stream)>>>(reinterpret_cast<float4 *>(G), n4, ring_dev, slots,
                                                                                  width, counter, msg);
     return check_launch("loop_step_begin");
-}
-
-NSIG_EXPORT int rm_finish_fwd(const float *image, const float *depth, const float *weights_sum, const float *nears, const float *fars,
-                              const float *bg, uint32_t bg_stride, uint32_t N, float *image_out, float *depth_out, nsig_stream_t stream) {
-    if (N == 0) return NSIG_OK;
-    NSIG_REQUIRE(image && depth && weights_sum && nears && fars && bg && image_out && depth_out, "rm_finish_fwd: null pointer");
-    NSIG_REQUIRE(bg_stride == 0 || bg_stride == 3, "rm_finish_fwd: bg_stride is 0 (one colour) or 3 (per ray)");
-    k_finish_fwd<<<ceil_div(N, 256u), 256, 0, as_stream(stream)>>>(image, depth, weights_sum, nears, fars, bg, bg_stride, N, image_out, depth_out);
-    return check_launch("rm_finish_fwd");
-}
-
-NSIG_EXPORT int rm_finish_bwd(const float *grad_image, const float *grad_depth, const float *depth, const float *nears, const float *fars,
-                              const float *bg, uint32_t bg_stride, uint32_t N, float *grad_weights_sum, float *grad_depth_in, nsig_stream_t stream) {
-    if (N == 0) return NSIG_OK;
-    NSIG_REQUIRE(depth && nears && fars && bg && grad_weights_sum, "rm_finish_bwd: null pointer");
-    NSIG_REQUIRE(bg_stride == 0 || bg_stride == 3, "rm_finish_bwd: bg_stride is 0 (one colour) or 3 (per ray)");
-    k_finish_bwd<<<ceil_div(N, 256u), 256, 0, as_stream(stream)>>>(grad_image, grad_depth, depth, nears, fars, bg, bg_stride, N, grad_weights_sum, grad_depth_in);
-    return check_launch("rm_finish_bwd");
 }
 
 NSIG_EXPORT int wm_loss_fwd(const float *content, const float *gt, uint32_t n_content, const float *decoded, const float *message, uint32_t D,

@@ -1,6 +1,6 @@
 // Ray-marching kernels for gfx950: aabb intersection, morton / bitfield utilities, the occupancy-grid
 // marcher (training: count -> scan -> write; inference: burst march + device-side compaction) and the
-// front-to-back compositor (forward / backward).
+// evaluation loop's serial compositor (the training compositor is csrc/composite.hip).
 //
 // Behavioural reference: /root/reference/raymarching/src/raymarching.cu (cited per kernel).  The
 // structure is not the reference's: the training march is split so that the serial, divergent part
@@ -939,157 +939,6 @@ __global__ void __launch_bounds__(256) k_march_scan_write(const float *__restric
         write_sample_row(m, total, LdsOffsets{off}, rays_o, rays_d, g, max_steps, N, M, nears, noises, t_rec, xyzs, dirs, deltas);
 }
 
-// ----------------------------------------------------------------------------- compositing (training)
-//
-// One wave per ray.  The reference walks a ray's samples serially (raymarching.cu:540-567); here the 64 lanes take 64
-// consecutive samples (coalesced loads), the transmittance T_j = prod_{i<j} (1 - alpha_i) comes from a wave-level
-// prefix product, the running depth parameter and (backward) the running colour from prefix sums, and the early
-// exit `T < T_thresh` becomes a prefix mask: sample j is accumulated iff the transmittance after sample j-1 is still
-// >= T_thresh (the reference tests after accumulating, :557).  Products and sums associate differently from the
-// serial loop, so results agree to fp32 round-off, not bit for bit (they never could: the reference uses __expf).
-
-struct Chunk {
-    float alpha, w, T_after, c0, c1, c2, dt, dreal;
-    bool valid, live;
-};
-
-// loads 64 samples of a ray and derives alpha, weight and transmittance; T_carry = transmittance entering the chunk
-__device__ inline Chunk load_chunk(const float *__restrict__ sigmas, const float *__restrict__ rgbs, const float *__restrict__ deltas, size_t m0,
-                                   uint32_t base, uint32_t cnt, int lane, float T_carry, float T_thresh) {
-    Chunk c;
-    c.valid = base + (uint32_t)lane < cnt;
-    const size_t m = m0 + base + lane;
-    float sigma = 0.0f;
-    c.dt = c.dreal = c.c0 = c.c1 = c.c2 = 0.0f;
-    if (c.valid) {
-        sigma = sigmas[m];
-        const float2 dl = reinterpret_cast<const float2 *>(deltas)[m];
-        c.dt = dl.x; c.dreal = dl.y;
-        c.c0 = rgbs[3 * m]; c.c1 = rgbs[3 * m + 1]; c.c2 = rgbs[3 * m + 2];
-    }
-    c.alpha = c.valid ? 1.0f - __expf(-sigma * c.dt) : 0.0f;
-    const float P = wave_scan(1.0f - c.alpha, lane, [](float a, float b) { return a * b; });  // inclusive product
-    float P_excl = __shfl_up(P, 1, 64);
-    if (lane == 0) P_excl = 1.0f;
-    const float T_before = T_carry * P_excl;
-    c.T_after = T_carry * P;
-    c.live = c.valid && T_before >= T_thresh;   // every earlier sample left T >= T_thresh (T_carry itself did)
-    c.w = c.live ? c.alpha * T_before : 0.0f;
-    return c;
-}
-
-// Optional tail of the render (renderer_wtmk.py:316-319) done by the ray's wave instead of a separate launch: background mix
-// and depth normalisation in the forward, the weights_sum gradient of the background mix in the backward.
-struct FinishArgs {
-    const float *nears, *fars, *bg;   // bg == nullptr: no tail
-    uint32_t bg_stride;               // 0: one colour [3]; 3: per ray
-    float *image_out, *depth_out;     // forward outputs
-    uint32_t self_zero;               // backward: the kernel zero-fills every gradient row it does not write (no memsets before it)
-};
-
-__global__ void __launch_bounds__(256) k_composite_fwd(const float *__restrict__ sigmas, const float *__restrict__ rgbs,
-                                                       const float *__restrict__ deltas, const int32_t *__restrict__ rays, uint32_t M,
-                                                       uint32_t N, float T_thresh, float *__restrict__ weights_sum,
-                                                       float *__restrict__ depth, float *__restrict__ image, FinishArgs fin = FinishArgs{}) {
-    const int lane = threadIdx.x & 63;
-    const uint32_t n = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (n >= N) return;
-    const uint32_t id = (uint32_t)rays[3 * (size_t)n], off = (uint32_t)rays[3 * (size_t)n + 1], cnt = (uint32_t)rays[3 * (size_t)n + 2];
-    float r = 0, g = 0, b = 0, ws = 0, d = 0, T = 1.0f, tt = 0.0f;
-    if (cnt != 0 && off + cnt <= M) {
-        for (uint32_t base = 0; base < cnt; base += 64) {
-            const Chunk c = load_chunk(sigmas, rgbs, deltas, off, base, cnt, lane, T, T_thresh);
-            const float t_incl = tt + wave_scan(c.dreal, lane, [](float a, float b2) { return a + b2; });  // accumulated real deltas (:549)
-            r += c.w * c.c0; g += c.w * c.c1; b += c.w * c.c2; ws += c.w; d += c.w * t_incl;
-            T = __shfl(c.T_after, 63, 64);
-            tt = __shfl(t_incl, 63, 64);
-            if (T < T_thresh) break;  // some sample of this chunk ended the ray
-        }
-        r = wave_sum(r); g = wave_sum(g); b = wave_sum(b); ws = wave_sum(ws); d = wave_sum(d);
-    }
-    if (lane == 0) {
-        weights_sum[id] = ws;
-        depth[id] = d;
-        image[3 * (size_t)id] = r; image[3 * (size_t)id + 1] = g; image[3 * (size_t)id + 2] = b;
-        if (fin.bg != nullptr) {   // the arithmetic of k_finish_fwd, operation by operation
-            const float rest = 1.0f - ws;
-            const float *bgp = fin.bg + (size_t)id * fin.bg_stride;
-            fin.image_out[3 * (size_t)id] = r + rest * bgp[0];
-            fin.image_out[3 * (size_t)id + 1] = g + rest * bgp[1];
-            fin.image_out[3 * (size_t)id + 2] = b + rest * bgp[2];
-            fin.depth_out[id] = fmaxf(d - fin.nears[id], 0.0f) / (fin.fars[id] - fin.nears[id]);
-        }
-    }
-}
-
-// raymarching.cu:602-682 (grad_depth does not propagate, raymarching.py:275).  grad buffers are pre-zeroed by the host
-// wrapper; only live samples are written.
-__global__ void __launch_bounds__(256) k_composite_bwd(const float *__restrict__ grad_ws, const float *__restrict__ grad_image,
-                                                       const float *__restrict__ sigmas, const float *__restrict__ rgbs,
-                                                       const float *__restrict__ deltas, const int32_t *__restrict__ rays,
-                                                       const float *__restrict__ weights_sum, const float *__restrict__ image, uint32_t M,
-                                                       uint32_t N, float T_thresh, float *__restrict__ grad_sigmas,
-                                                       float *__restrict__ grad_rgbs, FinishArgs fin = FinishArgs{}) {
-    const int lane = threadIdx.x & 63;
-    if (fin.self_zero && blockIdx.x >= ceil_div(N, 4u)) {
-        // tail blocks: rows past the last ray's samples (padding / unused capacity).  Rays are in ascending, gapless offset order.
-        const uint32_t total = (uint32_t)rays[3 * (size_t)(N - 1) + 1] + (uint32_t)rays[3 * (size_t)(N - 1) + 2];
-        for (size_t m = (size_t)total + (size_t)(blockIdx.x - ceil_div(N, 4u)) * 256 + threadIdx.x; m < M; m += (size_t)(gridDim.x - ceil_div(N, 4u)) * 256) {
-            grad_sigmas[m] = 0.0f;
-            grad_rgbs[3 * m] = 0.0f; grad_rgbs[3 * m + 1] = 0.0f; grad_rgbs[3 * m + 2] = 0.0f;
-        }
-        return;
-    }
-    const uint32_t n = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (n >= N) return;
-    const uint32_t id = (uint32_t)rays[3 * (size_t)n], off = (uint32_t)rays[3 * (size_t)n + 1], cnt = (uint32_t)rays[3 * (size_t)n + 2];
-    auto zero_rows = [&](uint32_t first, uint32_t last) {   // [first, last) of this ray's range, clipped to M
-        for (size_t m = (size_t)off + first + lane; m < (size_t)off + last && m < M; m += 64) {
-            grad_sigmas[m] = 0.0f;
-            grad_rgbs[3 * m] = 0.0f; grad_rgbs[3 * m + 1] = 0.0f; grad_rgbs[3 * m + 2] = 0.0f;
-        }
-    };
-    if (cnt == 0) return;
-    if (off + cnt > M) {   // a ray that did not fit (bounded mode): no gradient, but its rows below M belong to nobody else
-        if (fin.self_zero) zero_rows(0, cnt);
-        return;
-    }
-    const float g0 = grad_image[3 * (size_t)id], g1 = grad_image[3 * (size_t)id + 1], g2 = grad_image[3 * (size_t)id + 2];
-    const float rf = image[3 * (size_t)id], gf = image[3 * (size_t)id + 1], bf = image[3 * (size_t)id + 2];
-    float gws = grad_ws != nullptr ? grad_ws[id] : 0.0f;
-    if (fin.bg != nullptr) {   // image_out = image + (1 - weights_sum) * bg  =>  d weights_sum -= sum_c grad_image_c * bg_c (k_finish_bwd)
-        const float *bgp = fin.bg + (size_t)id * fin.bg_stride;
-        float sgb = 0.0f;
-        sgb += g0 * bgp[0]; sgb += g1 * bgp[1]; sgb += g2 * bgp[2];
-        gws = gws + (-sgb);
-    }
-    const float tail = gws * (1.0f - weights_sum[id]);
-    float T = 1.0f, r = 0.0f, g = 0.0f, b = 0.0f;  // carries: transmittance and accumulated colour entering the chunk
-    auto add = [](float a, float c) { return a + c; };
-    for (uint32_t base = 0; base < cnt; base += 64) {
-        const Chunk c = load_chunk(sigmas, rgbs, deltas, off, base, cnt, lane, T, T_thresh);
-        const float r_incl = r + wave_scan(c.w * c.c0, lane, add);
-        const float g_incl = g + wave_scan(c.w * c.c1, lane, add);
-        const float b_incl = b + wave_scan(c.w * c.c2, lane, add);
-        if (c.live) {
-            const size_t m = (size_t)off + base + lane;
-            grad_rgbs[3 * m] = g0 * c.w; grad_rgbs[3 * m + 1] = g1 * c.w; grad_rgbs[3 * m + 2] = g2 * c.w;
-            grad_sigmas[m] = c.dt * (g0 * (c.T_after * c.c0 - (rf - r_incl)) + g1 * (c.T_after * c.c1 - (gf - g_incl)) +
-                                     g2 * (c.T_after * c.c2 - (bf - b_incl)) + tail);
-        } else if (fin.self_zero && base + lane < cnt) {
-            const size_t m = (size_t)off + base + lane;
-            grad_sigmas[m] = 0.0f;
-            grad_rgbs[3 * m] = 0.0f; grad_rgbs[3 * m + 1] = 0.0f; grad_rgbs[3 * m + 2] = 0.0f;
-        }
-        T = __shfl(c.T_after, 63, 64);
-        r = __shfl(r_incl, 63, 64); g = __shfl(g_incl, 63, 64); b = __shfl(b_incl, 63, 64);
-        if (T < T_thresh) {   // the ray ended in this chunk: later samples get no gradient
-            if (fin.self_zero) zero_rows(base + 64, cnt);
-            break;
-        }
-    }
-}
-
 // ----------------------------------------------------------------------------- inference
 
 // raymarching.cu:701-805: slot n of a burst marches up to n_step occupied samples of its ray from rays_t[id] into its n_step rows; returns the rows written.
@@ -1396,176 +1245,6 @@ NSIG_EXPORT int rm_march_train_scan_write(const float *rays_o, const float *rays
     k_march_scan_write<<<blocks, 256, (N + 1) * sizeof(int32_t), as_stream(stream)>>>(rays_o, rays_d, make_grid_view(nullptr, bound, dt_gamma, max_steps, C, H),
                                                                                       max_steps, N, M, nears, noises, t_rec, counts, rays, counter, xyzs, dirs, deltas);
     return check_launch("rm_march_train_scan_write");
-}
-
-NSIG_EXPORT int rm_composite_train_fwd(const float *sigmas, const float *rgbs, const float *deltas,
-                                       const int32_t *rays, uint32_t M, uint32_t N, float T_thresh, float *weights_sum,
-                                       float *depth, float *image, nsig_stream_t stream) {
-    if (N == 0) return NSIG_OK;
-    NSIG_REQUIRE(sigmas && rgbs && deltas && rays && weights_sum && depth && image, "rm_composite_train_fwd: null pointer");
-    k_composite_fwd<<<ceil_div(N, 4u), 256, 0, as_stream(stream)>>>(sigmas, rgbs, deltas, rays, M, N, T_thresh, weights_sum, depth, image);
-    return check_launch("rm_composite_train_fwd");
-}
-
-NSIG_EXPORT int rm_composite_train_finish_fwd(const float *sigmas, const float *rgbs, const float *deltas, const int32_t *rays, uint32_t M,
-                                              uint32_t N, float T_thresh, const float *nears, const float *fars, const float *bg,
-                                              uint32_t bg_stride, float *weights_sum, float *depth, float *image, float *image_out,
-                                              float *depth_out, nsig_stream_t stream) {
-    if (N == 0) return NSIG_OK;
-    NSIG_REQUIRE(sigmas && rgbs && deltas && rays && weights_sum && depth && image && nears && fars && bg && image_out && depth_out,
-                 "rm_composite_train_finish_fwd: null pointer");
-    NSIG_REQUIRE(bg_stride == 0 || bg_stride == 3, "rm_composite_train_finish_fwd: bg_stride is 0 (one colour) or 3 (per ray)");
-    const FinishArgs fin{nears, fars, bg, bg_stride, image_out, depth_out, 0u};
-    k_composite_fwd<<<ceil_div(N, 4u), 256, 0, as_stream(stream)>>>(sigmas, rgbs, deltas, rays, M, N, T_thresh, weights_sum, depth, image, fin);
-    return check_launch("rm_composite_train_finish_fwd");
-}
-
-NSIG_EXPORT int rm_composite_train_finish_bwd(const float *grad_weights_sum, const float *grad_image_out, const float *sigmas, const float *rgbs,
-                                              const float *deltas, const int32_t *rays, const float *weights_sum, const float *image,
-                                              const float *bg, uint32_t bg_stride, uint32_t M, uint32_t N, float T_thresh, uint32_t rays_in_order,
-                                              float *grad_sigmas, float *grad_rgbs, nsig_stream_t stream) {
-    if (M == 0) return NSIG_OK;
-    NSIG_REQUIRE(grad_image_out && sigmas && rgbs && deltas && rays && weights_sum && image && bg && grad_sigmas && grad_rgbs,
-                 "rm_composite_train_finish_bwd: null pointer");
-    NSIG_REQUIRE(bg_stride == 0 || bg_stride == 3, "rm_composite_train_finish_bwd: bg_stride is 0 (one colour) or 3 (per ray)");
-    const bool self_zero = rays_in_order != 0 && N != 0;
-    if (!self_zero && (hipMemsetAsync(grad_sigmas, 0, (size_t)M * sizeof(float), as_stream(stream)) != hipSuccess ||
-                       hipMemsetAsync(grad_rgbs, 0, (size_t)M * 3 * sizeof(float), as_stream(stream)) != hipSuccess)) {
-        set_error("rm_composite_train_finish_bwd: hipMemsetAsync failed");
-        return NSIG_ERR_LAUNCH;
-    }
-    if (N == 0) return NSIG_OK;
-    const FinishArgs fin{nullptr, nullptr, bg, bg_stride, nullptr, nullptr, self_zero ? 1u : 0u};
-    k_composite_bwd<<<ceil_div(N, 4u) + (self_zero ? 64u : 0u), 256, 0, as_stream(stream)>>>(grad_weights_sum, grad_image_out, sigmas, rgbs, deltas, rays, weights_sum, image, M, N,
-                                                                    T_thresh, grad_sigmas, grad_rgbs, fin);
-    return check_launch("rm_composite_train_finish_bwd");
-}
-
-// Stage 1's compositing in ONE launch (stage1.GraphedCleanLoop): k_composite_fwd with the render tail, the gradient half of k_clean_loss
-// (nerf/utils.py:503: d loss / d image = grad_k * (image - gt), grad_k = grad_scale * 2 / n_values) and k_composite_bwd with the tail's adjoint, for rays in
-// ascending gapless offset order.  A wave owns a ray in all three, so the ray's image never leaves its registers: forward over the ray's chunks, the three seed
-// values, backward over the same chunks (read again, from L2).  The same arithmetic, operation by operation, as the three launches: the same bits in every output
-// (tests/test_gpu_stage1.py).  The loss VALUE and the loop's books stay with clean_loss, launched behind this kernel: two launches in a row where there were three.
-__global__ void __launch_bounds__(256) k_composite_mse(const float *__restrict__ sigmas, const float *__restrict__ rgbs, const float *__restrict__ deltas,
-                                                       const int32_t *__restrict__ rays, uint32_t M, uint32_t N, float T_thresh, const float *__restrict__ gt,
-                                                       float grad_k, FinishArgs fin, float *__restrict__ weights_sum, float *__restrict__ depth,
-                                                       float *__restrict__ image, float *__restrict__ grad_image, float *__restrict__ grad_sigmas,
-                                                       float *__restrict__ grad_rgbs) {
-    const int lane = threadIdx.x & 63;
-    if (blockIdx.x >= ceil_div(N, 4u)) {      // tail blocks: rows past the last ray's samples (k_composite_bwd's self_zero)
-        const uint32_t total = (uint32_t)rays[3 * (size_t)(N - 1) + 1] + (uint32_t)rays[3 * (size_t)(N - 1) + 2];
-        for (size_t m = (size_t)total + (size_t)(blockIdx.x - ceil_div(N, 4u)) * 256 + threadIdx.x; m < M; m += (size_t)(gridDim.x - ceil_div(N, 4u)) * 256) {
-            grad_sigmas[m] = 0.0f;
-            grad_rgbs[3 * m] = 0.0f; grad_rgbs[3 * m + 1] = 0.0f; grad_rgbs[3 * m + 2] = 0.0f;
-        }
-        return;
-    }
-    const uint32_t n = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (n >= N) return;
-    const uint32_t id = (uint32_t)rays[3 * (size_t)n], off = (uint32_t)rays[3 * (size_t)n + 1], cnt = (uint32_t)rays[3 * (size_t)n + 2];
-    const bool fits = cnt != 0 && off + cnt <= M;
-    // ---- forward (k_composite_fwd)
-    float r = 0, g = 0, b = 0, ws = 0, d = 0, T = 1.0f, tt = 0.0f;
-    if (fits) {
-        for (uint32_t base = 0; base < cnt; base += 64) {
-            const Chunk c = load_chunk(sigmas, rgbs, deltas, off, base, cnt, lane, T, T_thresh);
-            const float t_incl = tt + wave_scan(c.dreal, lane, [](float a, float b2) { return a + b2; });
-            r += c.w * c.c0; g += c.w * c.c1; b += c.w * c.c2; ws += c.w; d += c.w * t_incl;
-            T = __shfl(c.T_after, 63, 64);
-            tt = __shfl(t_incl, 63, 64);
-            if (T < T_thresh) break;
-        }
-        r = wave_sum(r); g = wave_sum(g); b = wave_sum(b); ws = wave_sum(ws); d = wave_sum(d);
-    }
-    const float rest = 1.0f - ws;
-    const float *bgp = fin.bg + (size_t)id * fin.bg_stride;
-    const float bg0 = bgp[0], bg1 = bgp[1], bg2 = bgp[2];
-    const float o0 = r + rest * bg0, o1 = g + rest * bg1, o2 = b + rest * bg2;
-    // ---- the seed (k_clean_loss: g_image[i] = k * (image[i] - gt[i]))
-    const float g0 = grad_k * (o0 - gt[3 * (size_t)id]), g1 = grad_k * (o1 - gt[3 * (size_t)id + 1]), g2 = grad_k * (o2 - gt[3 * (size_t)id + 2]);
-    if (lane == 0) {
-        weights_sum[id] = ws;
-        depth[id] = d;
-        image[3 * (size_t)id] = r; image[3 * (size_t)id + 1] = g; image[3 * (size_t)id + 2] = b;
-        fin.image_out[3 * (size_t)id] = o0; fin.image_out[3 * (size_t)id + 1] = o1; fin.image_out[3 * (size_t)id + 2] = o2;
-        fin.depth_out[id] = fmaxf(d - fin.nears[id], 0.0f) / (fin.fars[id] - fin.nears[id]);
-        grad_image[3 * (size_t)id] = g0; grad_image[3 * (size_t)id + 1] = g1; grad_image[3 * (size_t)id + 2] = g2;
-    }
-    // ---- backward (k_composite_bwd with the tail's adjoint and self_zero)
-    auto zero_rows = [&](uint32_t first, uint32_t last) {
-        for (size_t m = (size_t)off + first + lane; m < (size_t)off + last && m < M; m += 64) {
-            grad_sigmas[m] = 0.0f;
-            grad_rgbs[3 * m] = 0.0f; grad_rgbs[3 * m + 1] = 0.0f; grad_rgbs[3 * m + 2] = 0.0f;
-        }
-    };
-    if (cnt == 0) return;
-    if (!fits) {
-        zero_rows(0, cnt);
-        return;
-    }
-    float sgb = 0.0f;
-    sgb += g0 * bg0; sgb += g1 * bg1; sgb += g2 * bg2;
-    const float gws = 0.0f + (-sgb);
-    const float tail = gws * (1.0f - ws);
-    const float rf = r, gf = g, bf = b;
-    T = 1.0f;
-    float ra = 0.0f, ga = 0.0f, ba = 0.0f;
-    auto add = [](float a, float c) { return a + c; };
-    for (uint32_t base = 0; base < cnt; base += 64) {
-        const Chunk c = load_chunk(sigmas, rgbs, deltas, off, base, cnt, lane, T, T_thresh);
-        const float r_incl = ra + wave_scan(c.w * c.c0, lane, add);
-        const float g_incl = ga + wave_scan(c.w * c.c1, lane, add);
-        const float b_incl = ba + wave_scan(c.w * c.c2, lane, add);
-        if (c.live) {
-            const size_t m = (size_t)off + base + lane;
-            grad_rgbs[3 * m] = g0 * c.w; grad_rgbs[3 * m + 1] = g1 * c.w; grad_rgbs[3 * m + 2] = g2 * c.w;
-            grad_sigmas[m] = c.dt * (g0 * (c.T_after * c.c0 - (rf - r_incl)) + g1 * (c.T_after * c.c1 - (gf - g_incl)) +
-                                     g2 * (c.T_after * c.c2 - (bf - b_incl)) + tail);
-        } else if (base + lane < cnt) {
-            const size_t m = (size_t)off + base + lane;
-            grad_sigmas[m] = 0.0f;
-            grad_rgbs[3 * m] = 0.0f; grad_rgbs[3 * m + 1] = 0.0f; grad_rgbs[3 * m + 2] = 0.0f;
-        }
-        T = __shfl(c.T_after, 63, 64);
-        ra = __shfl(r_incl, 63, 64); ga = __shfl(g_incl, 63, 64); ba = __shfl(b_incl, 63, 64);
-        if (T < T_thresh) {
-            zero_rows(base + 64, cnt);
-            break;
-        }
-    }
-}
-
-NSIG_EXPORT int rm_composite_train_mse(const float *sigmas, const float *rgbs, const float *deltas, const int32_t *rays, uint32_t M, uint32_t N, float T_thresh,
-                                       const float *nears, const float *fars, const float *bg, uint32_t bg_stride, const float *gt, uint32_t n_values,
-                                       float grad_scale, float *weights_sum, float *depth, float *image, float *image_out, float *depth_out, float *grad_image,
-                                       float *grad_sigmas, float *grad_rgbs, nsig_stream_t stream) {
-    if (N == 0) return NSIG_OK;
-    NSIG_REQUIRE(sigmas && rgbs && deltas && rays && nears && fars && bg && gt && weights_sum && depth && image && image_out && depth_out && grad_image &&
-                 grad_sigmas && grad_rgbs, "rm_composite_train_mse: null pointer");
-    NSIG_REQUIRE(bg_stride == 0 || bg_stride == 3, "rm_composite_train_mse: bg_stride is 0 (one colour) or 3 (per ray)");
-    NSIG_REQUIRE(n_values >= 1, "rm_composite_train_mse: n_values must be positive");
-    const FinishArgs fin{nears, fars, bg, bg_stride, image_out, depth_out, 1u};
-    k_composite_mse<<<ceil_div(N, 4u) + 64u, 256, 0, as_stream(stream)>>>(sigmas, rgbs, deltas, rays, M, N, T_thresh, gt, grad_scale * 2.0f / (float)n_values, fin,
-                                                                         weights_sum, depth, image, grad_image, grad_sigmas, grad_rgbs);
-    return check_launch("rm_composite_train_mse");
-}
-
-NSIG_EXPORT int rm_composite_train_bwd(const float *grad_weights_sum, const float *grad_image, const float *sigmas,
-                                       const float *rgbs, const float *deltas, const int32_t *rays,
-                                       const float *weights_sum, const float *image, uint32_t M, uint32_t N,
-                                       float T_thresh, float *grad_sigmas, float *grad_rgbs, nsig_stream_t stream) {
-    if (M == 0) return NSIG_OK;
-    NSIG_REQUIRE(grad_weights_sum && grad_image && sigmas && rgbs && deltas && rays && weights_sum && image && grad_sigmas && grad_rgbs,
-                 "rm_composite_train_bwd: null pointer");
-    if (hipMemsetAsync(grad_sigmas, 0, (size_t)M * sizeof(float), as_stream(stream)) != hipSuccess ||
-        hipMemsetAsync(grad_rgbs, 0, (size_t)M * 3 * sizeof(float), as_stream(stream)) != hipSuccess) {
-        set_error("rm_composite_train_bwd: hipMemsetAsync failed");
-        return NSIG_ERR_LAUNCH;
-    }
-    if (N == 0) return NSIG_OK;
-    k_composite_bwd<<<ceil_div(N, 4u), 256, 0, as_stream(stream)>>>(grad_weights_sum, grad_image, sigmas, rgbs, deltas, rays,
-                                                                        weights_sum, image, M, N, T_thresh, grad_sigmas, grad_rgbs);
-    return check_launch("rm_composite_train_bwd");
 }
 
 NSIG_EXPORT int rm_march(uint32_t n_alive, uint32_t n_step, const int32_t *rays_alive, const float *rays_t,

@@ -230,7 +230,7 @@ __global__ void __launch_bounds__(1024) k_clean_loss(const float *__restrict__ i
     }
     __syncthreads();      // (every thread has read the step count before thread 0 advances it)
     float s = 0.0f;
-    const float k = grad_scale * 2.0f / (float)n;
+    const float k = mse_seed_factor(grad_scale, n);
     for (uint32_t i = threadIdx.x; i < n; i += 1024u) {
         const float d = image[i] - gt[i];
         s += d * d;

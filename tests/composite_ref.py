@@ -1,4 +1,4 @@
-"""Float64 restatement of the compositing kernels (csrc/raymarch.hip), their error bound and the seeded case list
+"""Float64 restatement of the compositing kernels (csrc/composite.hip; the evaluation form in csrc/raymarch.hip), their error bound and the seeded case list
 (tests/test_composite_cpu.py, tests/test_gpu_raymarch.py).  Plain numpy; nothing of the package is imported.
 
 The kernels' inputs are taken as they are: sigmas[M], rgbs[M,3], deltas[M,2] = (dt, real dt), rays[N,3] = (id, offset, count), T_thresh,

@@ -432,19 +432,26 @@ def test_composite_train_fwd_bwd_against_float64():
 
 @pytest.mark.parametrize("bg_stride", [0, 3])
 def test_composite_train_finish_fwd_against_float64(bg_stride):
-    """The forward with the render tail: the three raw outputs bit-equal to rm_composite_train_fwd's, image_out and depth_out within the bound."""
+    """The forward with the render tail: the three raw outputs bit-equal to rm_composite_train_fwd's, image_out and depth_out within the bound and
+    bit-equal to what rm_finish_fwd makes of rm_composite_train_fwd's outputs."""
     from nerf_signature_amd import _native as nv
     worst = _Worst()
     for case in cr.cases():
         r, d = _cref(case), _dev(case)
         n_all = case.N + _SPARE
         bg = case.bg if bg_stride == 0 else case.bg_rays
+        bg_dev = d.bg if bg_stride == 0 else d.bg_rays
         ws0, dep0, img0 = _train_fwd(nv, case, d)
         ws, dep, img, img_out, dep_out = _nan(n_all), _nan(n_all), _nan(n_all, 3), _nan(n_all, 3), _nan(n_all)
         nv.call("rm_composite_train_finish_fwd", nv.ptr(d.sigmas), nv.ptr(d.rgbs), nv.ptr(d.deltas), nv.ptr(d.rays), case.M, case.N, float(case.T_thresh),
-                nv.ptr(d.nears), nv.ptr(d.fars), nv.ptr(d.bg if bg_stride == 0 else d.bg_rays), bg_stride, nv.ptr(ws), nv.ptr(dep), nv.ptr(img),
+                nv.ptr(d.nears), nv.ptr(d.fars), nv.ptr(bg_dev), bg_stride, nv.ptr(ws), nv.ptr(dep), nv.ptr(img),
                 nv.ptr(img_out), nv.ptr(dep_out), nv.stream())
         assert _bits_equal(ws, ws0) and _bits_equal(dep, dep0) and _bits_equal(img, img0), case.name
+        img_sep, dep_sep = _nan(n_all, 3), _nan(n_all)          # the separate launch: rows 0 .. N-1, which are the table's ids
+        nv.call("rm_finish_fwd", nv.ptr(img0), nv.ptr(dep0), nv.ptr(ws0), nv.ptr(d.nears), nv.ptr(d.fars), nv.ptr(bg_dev), bg_stride, case.N,
+                nv.ptr(img_sep), nv.ptr(dep_sep), nv.stream())
+        rows = _cuda(_owned(case))
+        assert _bits_equal(img_out[rows], img_sep[rows]) and _bits_equal(dep_out[rows], dep_sep[rows]), f"{case.name}: fused tail != rm_finish_fwd"
         want_img, want_dep = cr.finish(r.fwd.weights_sum, r.fwd.image, r.fwd.depth, case.nears, case.fars, bg)
         tol = cr.composite_tolerance(*r.a, r.fwd, bg=bg, nears=case.nears, fars=case.fars)
         own = np.flatnonzero(_owned(case))
@@ -461,7 +468,8 @@ def test_composite_train_finish_fwd_against_float64(bg_stride):
 @pytest.mark.parametrize("in_order", [0, 1])
 def test_composite_train_finish_bwd_against_float64(in_order, with_gws, bg_stride):
     """The backward with the tail's adjoint.  rays_in_order = 1 (no memsets: the kernel zero-fills what it does not own) must leave every one of the M rows
-    finite, and the rows after termination, of dropped rays and of the padding exactly zero."""
+    finite, and the rows after termination, of dropped rays and of the padding exactly zero.  All M rows of both gradients are bit-equal to
+    rm_composite_train_bwd fed grad_weights_sum (zeros where none is given) + rm_finish_bwd's output, one fp32 addition."""
     from nerf_signature_amd import _native as nv
     worst = _Worst()
     for case in cr.cases():
@@ -469,6 +477,7 @@ def test_composite_train_finish_bwd_against_float64(in_order, with_gws, bg_strid
             continue
         r, d = _cref(case), _dev(case)
         bg = case.bg if bg_stride == 0 else case.bg_rays
+        bg_dev = d.bg if bg_stride == 0 else d.bg_rays
         ws, dep, img = _train_fwd(nv, case, d)
         gws_in = case.grad_weights_sum if with_gws else None
         gws, gi = cr.finish_backward(case.grad_image, bg, gws_in)
@@ -476,10 +485,18 @@ def test_composite_train_finish_bwd_against_float64(in_order, with_gws, bg_strid
         tol = cr.composite_tolerance(*r.a, r.fwd, gws_in, case.grad_image, bg=bg)
         gs, gc = _nan(case.M), _nan(case.M, 3)
         nv.call("rm_composite_train_finish_bwd", nv.ptr(d.grad_weights_sum if with_gws else None), nv.ptr(d.grad_image), nv.ptr(d.sigmas), nv.ptr(d.rgbs),
-                nv.ptr(d.deltas), nv.ptr(d.rays), nv.ptr(ws), nv.ptr(img), nv.ptr(d.bg if bg_stride == 0 else d.bg_rays), bg_stride, case.M, case.N,
+                nv.ptr(d.deltas), nv.ptr(d.rays), nv.ptr(ws), nv.ptr(img), nv.ptr(bg_dev), bg_stride, case.M, case.N,
                 float(case.T_thresh), in_order, nv.ptr(gs), nv.ptr(gc), nv.stream())
         _check_grads(worst, case, r.fwd.live, want_gs, want_gc, tol, gs, gc)
         assert bool(torch.isfinite(gs).all()) and bool(torch.isfinite(gc).all()), case.name
+        g_fin = _nan(case.N)                                    # the separate launches: the tail's adjoint, added by torch, then the plain backward
+        nv.call("rm_finish_bwd", nv.ptr(d.grad_image), nv.ptr(None), nv.ptr(dep), nv.ptr(d.nears), nv.ptr(d.fars), nv.ptr(bg_dev), bg_stride, case.N,
+                nv.ptr(g_fin), nv.ptr(None), nv.stream())
+        gws_sep = (d.grad_weights_sum if with_gws else torch.zeros(case.N, device="cuda")) + g_fin
+        gs_sep, gc_sep = _nan(case.M), _nan(case.M, 3)
+        nv.call("rm_composite_train_bwd", nv.ptr(gws_sep), nv.ptr(d.grad_image), nv.ptr(d.sigmas), nv.ptr(d.rgbs), nv.ptr(d.deltas), nv.ptr(d.rays),
+                nv.ptr(ws), nv.ptr(img), case.M, case.N, float(case.T_thresh), nv.ptr(gs_sep), nv.ptr(gc_sep), nv.stream())
+        assert _bits_equal(gs, gs_sep) and _bits_equal(gc, gc_sep), f"{case.name}: fused adjoint != rm_finish_bwd + rm_composite_train_bwd"
     worst.show(f"rm_composite_train_finish_bwd rays_in_order={in_order} grad_weights_sum={'given' if with_gws else 'null'} bg_stride={bg_stride}")
 
 
@@ -503,9 +520,33 @@ def _mse_reference(case, fwd, a, bg):
     return cr.Bag(image_out=img_out, depth_out=dep_out, grad_image=seed, grad_sigmas=gs, grad_rgbs=gc), tol
 
 
+def _mse_three_launches(nv, case, d, bg_stride):
+    """rm_composite_train_finish_fwd -> the MSE seed -> rm_composite_train_finish_bwd(rays_in_order = 1, no grad_weights_sum): what the one launch replaces"""
+    n_all = case.N + _SPARE
+    bg_dev = d.bg if bg_stride == 0 else d.bg_rays
+    o = cr.Bag(weights_sum=_nan(n_all), depth=_nan(n_all), image=_nan(n_all, 3), image_out=_nan(n_all, 3), depth_out=_nan(n_all), grad_image=_nan(n_all, 3),
+               grad_sigmas=_nan(case.M), grad_rgbs=_nan(case.M, 3))
+    nv.call("rm_composite_train_finish_fwd", nv.ptr(d.sigmas), nv.ptr(d.rgbs), nv.ptr(d.deltas), nv.ptr(d.rays), case.M, case.N, float(case.T_thresh),
+            nv.ptr(d.nears), nv.ptr(d.fars), nv.ptr(bg_dev), bg_stride, nv.ptr(o.weights_sum), nv.ptr(o.depth), nv.ptr(o.image), nv.ptr(o.image_out),
+            nv.ptr(o.depth_out), nv.stream())
+    if case.n_values == 3 * case.N and np.array_equal(np.sort(case.rays[:, 0]), np.arange(case.N)):     # n_values covers exactly the table's rows: clean_loss's seed
+        loss = _nan(1)
+        nv.call("clean_loss", nv.ptr(o.image_out), nv.ptr(d.gt), case.n_values, float(case.grad_scale), nv.ptr(loss), nv.ptr(o.grad_image), nv.ptr(None), nv.ptr(None),
+                nv.ptr(None), nv.ptr(None), 0, nv.ptr(None), 0, 0, nv.stream())
+    else:                                                  # the same product and quotient, then k * (image_out - gt), all in fp32
+        k = np.float32(case.grad_scale) * np.float32(2.0) / np.float32(case.n_values)
+        ids = _cuda(np.flatnonzero(_owned(case)))
+        o.grad_image[ids] = float(k) * (o.image_out[ids] - d.gt[ids])
+    nv.call("rm_composite_train_finish_bwd", nv.ptr(None), nv.ptr(o.grad_image), nv.ptr(d.sigmas), nv.ptr(d.rgbs), nv.ptr(d.deltas), nv.ptr(d.rays),
+            nv.ptr(o.weights_sum), nv.ptr(o.image), nv.ptr(bg_dev), bg_stride, case.M, case.N, float(case.T_thresh), 1, nv.ptr(o.grad_sigmas), nv.ptr(o.grad_rgbs),
+            nv.stream())
+    return o
+
+
 @pytest.mark.parametrize("bg_stride", [0, 3])
 def test_composite_train_mse_against_float64(bg_stride):
-    """The one-launch kernel of the captured stage-1 loop: every output against the reference chain, and the zero-fill of all rows it does not own."""
+    """The one-launch kernel of the captured stage-1 loop: every output against the reference chain, and the zero-fill of all rows it does not own.
+    Every output is also bit-equal to the three launches it replaces (_mse_three_launches)."""
     from nerf_signature_amd import _native as nv
     worst = _Worst()
     for case in cr.cases():
@@ -522,6 +563,9 @@ def test_composite_train_mse_against_float64(bg_stride):
             assert bool(torch.isnan(o[k][_cuda(~_owned(case))]).all())
         _check_grads(worst, case, r.fwd.live, want.grad_sigmas, want.grad_rgbs, tol, o.grad_sigmas, o.grad_rgbs)
         assert bool(torch.isfinite(o.grad_sigmas).all()) and bool(torch.isfinite(o.grad_rgbs).all()), case.name
+        sep = _mse_three_launches(nv, case, d, bg_stride)
+        for k in o:
+            assert _bits_equal(o[k], sep[k]), f"{case.name}: {k} of the one launch != the three launches"
     worst.show(f"rm_composite_train_mse bg_stride={bg_stride}")
 
 
