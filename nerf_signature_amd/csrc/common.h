@@ -7,6 +7,7 @@
 
 #include <atomic>
 #include <mutex>
+#include <type_traits>
 
 #include "../../include/nerfsig.h"
 
@@ -62,6 +63,13 @@ int take_pointers(T *const (&dst)[K], T const *const (&src)[K], uint32_t n, cons
         for (size_t k = 0; k < K; ++k) dst[k][i] = src[k][i];
     }
     return NSIG_OK;
+}
+
+// launch(std::true_type{}) or launch(std::false_type{}): a launch that differs in one bool template argument is written once, as a generic lambda (`decltype(flag)::value`).
+template <typename Launch>
+void with_flag(bool flag, Launch launch) {
+    if (flag) launch(std::true_type{});
+    else launch(std::false_type{});
 }
 
 __host__ __device__ inline uint32_t ceil_div(uint32_t a, uint32_t b) { return (a + b - 1) / b; }

@@ -1,5 +1,6 @@
 // Fused field network for gfx950: hash encode (16 base levels + summed codebook table) -> sigma MLP ->
 // trunc_exp | SH(deg 4) + geo features -> color MLP -> sigmoid, forward and input-gradient backward.
+// (The encoder of large batches is encode.hip; its plane set, which the kernels here read, is laid out in planes.h.)
 //
 // Behavioural reference: /root/reference/nerf/network_wtmk_tcnn.py:97-176 (NeRFNetwork.forward / density /
 // color), with the MLP semantics of tiny-cuda-nn's FullyFusedMLP restated in oracle/field_ref.py (the
@@ -31,7 +32,7 @@
 #include <type_traits>
 #include <unordered_set>
 #include "fieldmlp.h"
-#include "packed.h"
+#include "planes.h"
 #include "wave.h"
 
 #include <stdlib.h>
@@ -93,283 +94,6 @@ __global__ void __launch_bounds__(256) k_pack_weights(const float *__restrict__ 
 }
 
 // ----------------------------------------------------------------------------- forward
-
-// XCD-partitioned, level-major encoder.  The expensive part of the encoder is the 5-6 finest levels: consecutive
-// points of a ray fall into different cells there, so every point costs ~4 distinct cache lines per level, served from
-// beyond L2 when all 17 tables (68 MiB) compete for each XCD's 4 MiB L2.  Workgroups are dealt round-robin over the 8
-// XCDs (blockIdx % 8 labels the XCD group; a speed assumption only), so workgroup (tile, slot = blockIdx % 8) encodes
-// for its tile of 256 points only the levels assigned to that slot: each XCD then gathers from ONE fine table (4 MiB,
-// L2-sized) plus a few coarse ones.  Features are written level-major, planes[level][point] (float2), so the stores of
-// a wave are 512 contiguous bytes; streaming loads/stores are non-temporal to leave L2 to the tables.
-struct SlotTable {
-    uint8_t n[8];
-    uint8_t level[8][8];      // 0..15 base levels, 16 = pre-summed codebook; every level belongs to exactly one slot
-};
-
-// Lane pairs cooperate on the gathers.  A gather costs ~2.4 clk per distinct 128-byte line per instruction plus ~1 clk per lane
-// (tools/micro/gather_rate.hip), and the two x-neighbours of a (dy, dz) pair share a line in 15 of 16 cells.  With one lane per
-// point they sit in two different instructions (64 lines each: one misses L1, the next hits it); here lanes 2i and 2i+1 first
-// fetch the x = 0 / x = 1 sides of point 2i, then of point 2i+1, so every instruction touches 32 lines instead of 64 and none
-// relies on L1 to keep a line until its partner instruction arrives.  Same number of gather instructions, same values; the
-// cell hashes travel from the owner to its neighbour by DPP, the fetched corners back the same way.
-__device__ inline uint32_t dpp_u(uint32_t v, int ctrl) {
-    switch (ctrl) {   // quad_perm selectors must be immediates
-        case 0: return (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0xA0, 0xF, 0xF, true);    // [0,0,2,2]: the even lane's value
-        case 1: return (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0xF5, 0xF, 0xF, true);    // [1,1,3,3]: the odd lane's value
-        default: return (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0xB1, 0xF, 0xF, true);   // [1,0,3,2]: swap with the neighbour
-    }
-}
-
-// One level of one 256-point tile: lane pairs fetch the two x sides (see above), trilinear interpolation, one streaming store.
-// Two layouts of a plane set (17 feature planes of `stride` points):
-//   fp32   planes[level][point] float2 -- every consumer reads it;
-//   mixed  levels 0..14 as fp16 pairs (4 bytes per point), then level 15 and the codebook level as float2 -- written by hg_encode_planes_mixed for the fp16
-//          MLP, whose first-layer operand is exactly those fp16 pairs (rounded to nearest even here instead of at the MLP's load: the same bits).  Level 15
-//          stays fp32 because the codebook is added to it BEFORE the rounding (network_wtmk_tcnn.py:106).  15 x 4 + 2 x 8 = 76 instead of 136 bytes per point
-//          each way between the encoder and the MLP.
-constexpr int kHalfLevels = NSIG_BASE_LEVELS - 1;
-__device__ __host__ inline float2 *mixed_f32_plane(void *planes, uint32_t stride, int level) {      // level 15 or 16 of a mixed set
-    return reinterpret_cast<float2 *>(reinterpret_cast<uint32_t *>(planes) + (size_t)kHalfLevels * stride) + (size_t)(level - kHalfLevels) * stride;
-}
-__device__ inline float2 load_plane(const float2 *__restrict__ planes, uint32_t stride, int level, uint32_t s, bool mixed) {
-    if (!mixed) return planes[(size_t)level * stride + s];
-    if (level >= kHalfLevels) return mixed_f32_plane(const_cast<float2 *>(planes), stride, level)[s];
-    const f32x2 w = __builtin_convertvector(__builtin_bit_cast(f16x2, reinterpret_cast<const uint32_t *>(planes)[(size_t)level * stride + s]), f32x2);
-    return make_float2(w[0], w[1]);
-}
-
-__device__ inline void encode_tile_level(const float2 *__restrict__ table, float cell, uint32_t xs, float x, float y, float z,
-                                         float2 *__restrict__ out, bool half_out = false, bool streaming = true) {
-    uint32_t ix, iy, iz;
-    float wx, wy, wz;
-    axis_cell(x, cell, ix, wx);
-    axis_cell(y, cell, iy, wy);
-    axis_cell(z, cell, iz, wz);
-    const uint32_t hy0 = iy * kPrimeY, hy1 = (iy + 1u) * kPrimeY, hz0 = iz * kPrimeZ, hz1 = (iz + 1u) * kPrimeZ;   // corner_rows()
-    float2 v[2][4];   // v[P][q]: this lane's x side of point P of the pair, corner (dy, dz) = (q >> 1, q & 1)
-#pragma unroll
-    for (int P = 0; P < 2; ++P) {
-        const uint32_t hx = dpp_u(ix, P) + xs;
-        const uint32_t a0 = dpp_u(hy0, P), a1 = dpp_u(hy1, P), b0 = dpp_u(hz0, P), b1 = dpp_u(hz1, P);
-        v[P][0] = table[(hx ^ a0 ^ b0) & kRowMask];
-        v[P][1] = table[(hx ^ a0 ^ b1) & kRowMask];
-        v[P][2] = table[(hx ^ a1 ^ b0) & kRowMask];
-        v[P][3] = table[(hx ^ a1 ^ b1) & kRowMask];
-    }
-    float2 e[8];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        const float2 mine = xs ? v[1][q] : v[0][q];      // my own point, my x side
-        const float2 give = xs ? v[0][q] : v[1][q];      // the neighbour's point, my x side
-        float2 got;                                       // my own point, the other x side (fetched by the neighbour)
-        got.x = __uint_as_float(dpp_u(__float_as_uint(give.x), 2));
-        got.y = __uint_as_float(dpp_u(__float_as_uint(give.y), 2));
-        e[q] = xs ? got : mine;          // corner k = 4*dx + q
-        e[4 + q] = xs ? mine : got;
-    }
-    const float2 val = trilerp(e, wx, wy, wz);
-    if (half_out) {      // (a level of a mixed plane set: `out` addresses 4-byte elements)
-        __builtin_nontemporal_store(cvt_pk_f16(val.x, val.y), reinterpret_cast<uint32_t *>(out));
-        return;
-    }
-    typedef float f32x2_t __attribute__((ext_vector_type(2)));
-    const f32x2_t vv = {val.x, val.y};
-    // the all-fp32 plane set (stage 1, the split-bf16 MLP) goes through the caches: its consumer runs right behind this launch and found the planes in memory when
-    // they were streamed out (stage-1 forward 166 -> 133 us, this launch +2.5, same box, two rounds); the mixed set of the headline step keeps its streaming
-    // stores (LABNOTES section 12: fewer store transactions on the fabric the line fills compete for)
-    if (streaming) __builtin_nontemporal_store(vv, reinterpret_cast<f32x2_t *>(out));
-    else *reinterpret_cast<f32x2_t *>(out) = vv;
-}
-
-// Reads a slot's finest table (its first) through that slot's XCD (blockIdx % 8): its L2 then holds that table when the encoder starts.  Only that one: it is the
-// L2's size, and the slot's coarser tables behind it made the pass as long as the fullest slot's 12 MiB (include/nerfsig.h, hg_warm_tables).
-__global__ void __launch_bounds__(256) k_warm_tables(TablePtrs base, const float *__restrict__ S, SlotTable tab, float *__restrict__ sink) {
-    const uint32_t slot = blockIdx.x & 7u, wg = blockIdx.x >> 3, n_wg = gridDim.x >> 3;
-    float acc = 0.0f;
-    if (tab.n[slot] > 0) {
-        const int l = tab.level[slot][0];
-        const float4 *t = reinterpret_cast<const float4 *>(l == NSIG_BASE_LEVELS ? S : base.p[l]);
-        // eight requests per lane before the first is waited for (the default grid: all of a lane's eight): one at a time, the pass was eight memory latencies long
-        for (uint32_t e = wg * 256 + threadIdx.x; t != nullptr && e < NSIG_TABLE_ROWS / 2; e += 8 * n_wg * 256) {
-            float4 v[8];
-#pragma unroll
-            for (uint32_t k = 0; k < 8; ++k) v[k] = t[min(e + k * n_wg * 256, NSIG_TABLE_ROWS / 2 - 1)];
-#pragma unroll
-            for (uint32_t k = 0; k < 8; ++k) acc += v[k].x + v[k].y + v[k].z + v[k].w;
-        }
-    }
-    if (acc == 1.2345e-33f) *sink = acc;      // (never: keeps the loads)
-}
-
-// Workgroup (tile, slot) encodes, for its 256 points, the levels (or the part of a level's tile range) assigned to its XCD slot.
-template <bool mixed>      // (the plane layout as a compile-time constant: the destination of a level's features is then one address computation, not a chain of branches per level)
-__global__ void __launch_bounds__(256) k_encode_planes(const float *__restrict__ xyzs, uint32_t M, float bound, TablePtrs base, LevelGeom geom,
-                                                       const float *__restrict__ S, float2 *__restrict__ planes, uint32_t stride, SlotTable tab,
-                                                       const uint32_t *__restrict__ rows_dev = nullptr) {
-    // rows_dev (the eval loop's bursts, hg_encode_planes_rows): the number of rows that exist is known on the device only; the launch is sized for `M`
-    // (the buffers' capacity, which also fixes the plane stride) and rows beyond the count are skipped
-    uint32_t lim = stride;
-    if (rows_dev != nullptr) {
-        const uint32_t r = *rows_dev;
-        if (r == 0) return;
-        M = min(M, r);
-        lim = min(stride, ceil_div(M, 32u) * 32u);
-    }
-    const uint32_t slot = blockIdx.x & 7u;
-    const uint32_t n_tiles = ceil_div(stride, 256u);
-    const int n_levels = tab.n[slot];
-    const float two_b = 2.0f * bound;
-    const uint32_t xs = threadIdx.x & 1u;   // which x side of the cell this lane fetches
-    for (uint32_t tile = blockIdx.x >> 3; tile < n_tiles; tile += gridDim.x >> 3) {
-        const uint32_t m = tile * 256 + threadIdx.x;
-        if (m >= lim) continue;             // a multiple of 32: lane pairs (and DPP quads) are in or out together
-        const uint32_t ml = min(m, M - 1);  // rows in [M, stride) replicate the last point (never consumed)
-        // one 12-byte load and one 8-byte streaming store per level: the kernel is bound by the address path, every instruction counts
-        const float3 pt = *reinterpret_cast<const float3 *>(xyzs + 3 * (size_t)ml);
-        const float x = (pt.x + bound) / two_b, y = (pt.y + bound) / two_b, z = (pt.z + bound) / two_b;
-        for (int i = 0; i < n_levels; ++i) {
-            const int l = tab.level[slot][i];
-            const bool half_out = mixed && l < kHalfLevels;
-            float2 *out = !mixed ? planes + (size_t)l * stride + m
-                                 : (half_out ? reinterpret_cast<float2 *>(reinterpret_cast<uint32_t *>(planes) + (size_t)l * stride + m) : mixed_f32_plane(planes, stride, l) + m);
-            encode_tile_level(reinterpret_cast<const float2 *>(l == NSIG_BASE_LEVELS ? S : base.p[l]), geom.cell[l], xs, x, y, z, out, half_out, /*streaming=*/mixed);
-        }
-    }
-}
-
-// ---- the encoder over PACKED tables (hg_encode_planes_packed; formats and decode: include/nerfsig.h "packed released model", csrc/packed.h).  The fp32 functions
-// above are left exactly as they are; these stand beside them.  Same slot table, same lane-pair gather, same axis_cell / trilerp: the one difference is the row load,
-// which fetches a 4-, 2- or 1-byte row word.  The lane pair exchanges the RAW row words by DPP (one exchange per corner instead of two) and every lane decodes the
-// eight corners of its own point once; decode(word) is a pure function of the word, so the floats are those the fp32 encoder gathers from the decoded table.
-template <int FMT>
-__device__ inline void encode_tile_level_packed(const void *__restrict__ table, float lo, float step, float cell, uint32_t xs, float x, float y, float z,
-                                                float2 *__restrict__ out, bool half_out, bool streaming) {
-    uint32_t ix, iy, iz;
-    float wx, wy, wz;
-    axis_cell(x, cell, ix, wx);
-    axis_cell(y, cell, iy, wy);
-    axis_cell(z, cell, iz, wz);
-    const uint32_t hy0 = iy * kPrimeY, hy1 = (iy + 1u) * kPrimeY, hz0 = iz * kPrimeZ, hz1 = (iz + 1u) * kPrimeZ;   // corner_rows()
-    uint32_t v[2][4];   // v[P][q]: the row word of this lane's x side of point P of the pair, corner (dy, dz) = (q >> 1, q & 1)
-#pragma unroll
-    for (int P = 0; P < 2; ++P) {
-        const uint32_t hx = dpp_u(ix, P) + xs;
-        const uint32_t a0 = dpp_u(hy0, P), a1 = dpp_u(hy1, P), b0 = dpp_u(hz0, P), b1 = dpp_u(hz1, P);
-        v[P][0] = pk_load_row<FMT>(table, (hx ^ a0 ^ b0) & kRowMask);      // (a row index is < NSIG_TABLE_ROWS: inside the table's pk_table_bytes)
-        v[P][1] = pk_load_row<FMT>(table, (hx ^ a0 ^ b1) & kRowMask);
-        v[P][2] = pk_load_row<FMT>(table, (hx ^ a1 ^ b0) & kRowMask);
-        v[P][3] = pk_load_row<FMT>(table, (hx ^ a1 ^ b1) & kRowMask);
-    }
-    float2 e[8];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        const uint32_t mine = xs ? v[1][q] : v[0][q];      // my own point, my x side
-        const uint32_t give = xs ? v[0][q] : v[1][q];      // the neighbour's point, my x side
-        const uint32_t got = dpp_u(give, 2);               // my own point, the other x side (fetched by the neighbour)
-        e[q] = pk_decode_row<FMT>(xs ? got : mine, lo, step);          // corner k = 4*dx + q
-        e[4 + q] = pk_decode_row<FMT>(xs ? mine : got, lo, step);
-    }
-    const float2 val = trilerp(e, wx, wy, wz);
-    if (half_out) {
-        __builtin_nontemporal_store(cvt_pk_f16(val.x, val.y), reinterpret_cast<uint32_t *>(out));
-        return;
-    }
-    typedef float f32x2_t __attribute__((ext_vector_type(2)));
-    const f32x2_t vv = {val.x, val.y};
-    if (streaming) __builtin_nontemporal_store(vv, reinterpret_cast<f32x2_t *>(out));
-    else *reinterpret_cast<f32x2_t *>(out) = vv;
-}
-
-struct PackedTablePtrs {
-    const void *p[NSIG_BASE_LEVELS + 1];      // [16]: the signature table (level 16), NULL without one
-};
-
-// k_encode_planes over packed tables: the same walk (tiles, slots, rows_dev, the replicated last row), the same destinations; params[l] = {lo, step} of table l.
-template <int FMT, bool mixed>
-__global__ void __launch_bounds__(256) k_encode_planes_packed(const float *__restrict__ xyzs, uint32_t M, float bound, PackedTablePtrs tabs, LevelGeom geom,
-                                                              const float2 *__restrict__ params, float2 *__restrict__ planes, uint32_t stride, SlotTable tab,
-                                                              const uint32_t *__restrict__ rows_dev) {
-    uint32_t lim = stride;
-    if (rows_dev != nullptr) {
-        const uint32_t r = *rows_dev;
-        if (r == 0) return;
-        M = min(M, r);
-        lim = min(stride, ceil_div(M, 32u) * 32u);
-    }
-    const uint32_t slot = blockIdx.x & 7u;
-    const uint32_t n_tiles = ceil_div(stride, 256u);
-    const int n_levels = tab.n[slot];
-    const float two_b = 2.0f * bound;
-    const uint32_t xs = threadIdx.x & 1u;
-    for (uint32_t tile = blockIdx.x >> 3; tile < n_tiles; tile += gridDim.x >> 3) {
-        const uint32_t m = tile * 256 + threadIdx.x;
-        if (m >= lim) continue;             // a multiple of 32: lane pairs (and DPP quads) are in or out together
-        const uint32_t ml = min(m, M - 1);  // rows in [M, stride) replicate the last point (never consumed)
-        const float3 pt = *reinterpret_cast<const float3 *>(xyzs + 3 * (size_t)ml);
-        const float x = (pt.x + bound) / two_b, y = (pt.y + bound) / two_b, z = (pt.z + bound) / two_b;
-        for (int i = 0; i < n_levels; ++i) {
-            const int l = tab.level[slot][i];
-            const bool half_out = mixed && l < kHalfLevels;
-            float2 *out = !mixed ? planes + (size_t)l * stride + m
-                                 : (half_out ? reinterpret_cast<float2 *>(reinterpret_cast<uint32_t *>(planes) + (size_t)l * stride + m) : mixed_f32_plane(planes, stride, l) + m);
-            float2 ps = make_float2(0.0f, 0.0f);
-            if (FMT != NSIG_PACK_F16) ps = params[l];      // (uniform: one scalar load per level)
-            encode_tile_level_packed<FMT>(tabs.p[l], ps.x, ps.y, geom.cell[l], xs, x, y, z, out, half_out, /*streaming=*/mixed);
-        }
-    }
-}
-
-// The codebook level alone, into plane 16 of a plane set whose base planes are already there (hg_encode_codebook_plane: rays that
-// do not change between steps).  One tile per workgroup, all XCDs: S (4 MiB) is the only table, every L2 holds its own copy.
-// reset: the header of a scatter plan kept across steps -- its largest-gradient word starts every step at zero (k_plan_dest does
-// that for a plan computed per step).
-__global__ void __launch_bounds__(256) k_encode_codebook_plane(const float *__restrict__ xyzs, uint32_t M, float bound, float cell, const float *__restrict__ S,
-                                                               float2 *__restrict__ plane, uint32_t stride, BinHeader *__restrict__ reset) {
-    if (reset != nullptr && blockIdx.x == 0 && threadIdx.x == 0) reset->gmax_bits = 0;
-    const uint32_t m = blockIdx.x * 256 + threadIdx.x;
-    if (m >= stride) return;                // stride is a multiple of 32: lane pairs (and DPP quads) are in or out together
-    const uint32_t ml = min(m, M - 1);
-    const float two_b = 2.0f * bound;
-    const float3 pt = *reinterpret_cast<const float3 *>(xyzs + 3 * (size_t)ml);
-    const float x = (pt.x + bound) / two_b, y = (pt.y + bound) / two_b, z = (pt.z + bound) / two_b;
-    encode_tile_level(reinterpret_cast<const float2 *>(S), cell, threadIdx.x & 1u, x, y, z, plane + m);
-}
-
-// The codebook level of M points under K messages at once (hg_encode_codebook_planes_multi): S is K pre-sums row-interleaved, S[row][k] (float2), so one corner
-// of one point is ONE contiguous read of 8 K bytes for all messages.  A group of G consecutive lanes shares a point: lane j of the group reads, of each of the
-// point's eight rows, messages 2 j and 2 j + 1 as one 16-byte load (kPair: K even, G = K / 2) or message j as one 8-byte load (K odd, G = K) -- a group's loads
-// of a row are adjacent, a wave's instruction touches 64 / G rows instead of 64.  Every lane derives its point's rows and weights itself (corner_rows; no lane
-// exchange, so groups may straddle waves), interpolates with trilerp as encode_tile_level does -- plane k has the bits of hg_encode_codebook_plane from S_k -- and
-// writes cplanes[k][point].  Rows in [M, stride) replicate the last point, as there.
-template <bool kPair>
-__global__ void __launch_bounds__(256) k_encode_codebook_planes_multi(const float *__restrict__ xyzs, uint32_t M, float bound, float cell, const float2 *__restrict__ S,
-                                                                      uint32_t K, uint32_t G, float2 *__restrict__ cplanes, uint32_t stride) {
-    const uint64_t gid = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-    const uint32_t m = (uint32_t)(gid / G), j = (uint32_t)(gid - (uint64_t)m * G);
-    if (m >= stride) return;
-    const uint32_t ml = min(m, M - 1);
-    const float two_b = 2.0f * bound;
-    const float3 pt = *reinterpret_cast<const float3 *>(xyzs + 3 * (size_t)ml);
-    const float x = (pt.x + bound) / two_b, y = (pt.y + bound) / two_b, z = (pt.z + bound) / two_b;
-    Corner8 c;
-    corner_rows(x, y, z, cell, c);
-    float2 e[8];
-    if constexpr (kPair) {
-        float4 v[8];
-#pragma unroll
-        for (int q = 0; q < 8; ++q) v[q] = *reinterpret_cast<const float4 *>(S + (size_t)c.row[q] * K + 2 * j);
-#pragma unroll
-        for (int q = 0; q < 8; ++q) e[q] = make_float2(v[q].x, v[q].y);
-        cplanes[(size_t)(2 * j) * stride + m] = trilerp(e, c.wx, c.wy, c.wz);
-#pragma unroll
-        for (int q = 0; q < 8; ++q) e[q] = make_float2(v[q].z, v[q].w);
-        cplanes[(size_t)(2 * j + 1) * stride + m] = trilerp(e, c.wx, c.wy, c.wz);
-    } else {
-#pragma unroll
-        for (int q = 0; q < 8; ++q) e[q] = S[(size_t)c.row[q] * K + j];
-        cplanes[(size_t)j * stride + m] = trilerp(e, c.wx, c.wy, c.wz);
-    }
-}
 
 // (k_field_fwd's kPlanes = 0: gather the features in-kernel (fused); 1: read all 17 from the level-major planes.)
 // The training render's forward launch (all 17 feature planes in memory, sigma + rgb + ReLU masks out), software-pipelined over a wave's tiles.
@@ -1122,12 +846,6 @@ static void with_mlp(Launch launch) {
     if (mlp_precision() == 1) launch(F16{});
     else launch(Bf16x3{});
 }
-// launch(std::true_type{}) or launch(std::false_type{}): the same for a launch that differs in one bool template argument (`decltype(flag)::value`).
-template <typename Launch>
-static void with_flag(bool flag, Launch launch) {
-    if (flag) launch(std::true_type{});
-    else launch(std::false_type{});
-}
 NSIG_EXPORT int mlp_set_precision(int mode) {
     NSIG_REQUIRE(mode == 0 || mode == 1, "mlp_set_precision: 0 (bf16x3) or 1 (f16)");
     g_mlp_precision = mode;
@@ -1166,127 +884,23 @@ static uint32_t field_grid(uint32_t M, bool forward = false, uint32_t per_cu = 0
     return blocks < cap ? blocks : cap;
 }
 
-// Level -> XCD-slot assignment of k_encode_planes: the six finest levels each get a slot of their own or share it only with coarse
-// (cache-resident) levels; whole levels per slot.  The assignment that won round 1's same-box sweeps (profiles/r01_k_encoder_slots_sweep.txt); a
-// cost-balanced split with levels cut across slots was measured slower (287-292 against 283 us, profiles/r02_encoder_experiments.txt: with all eight
-// XCDs busy the launch is bound chip-wide by L2->L1 line fills, not by its fullest slot) and is gone.
-static SlotTable default_slots(bool with_codebook) {
-    static const uint8_t kWith[8][4] = {{16, 255, 255, 255}, {15, 255, 255, 255}, {14, 0, 255, 255}, {13, 1, 255, 255}, {12, 2, 3, 255}, {11, 4, 5, 255}, {10, 9, 255, 255}, {8, 7, 6, 255}};
-    static const uint8_t kWithout[8][4] = {{15, 255, 255, 255}, {14, 255, 255, 255}, {13, 255, 255, 255}, {12, 255, 255, 255}, {11, 0, 1, 255}, {10, 2, 3, 255}, {9, 8, 4, 255}, {7, 6, 5, 255}};
-    SlotTable t{};
-    for (int slot = 0; slot < 8; ++slot)
-        for (int k = 0; k < 4; ++k) {
-            const uint8_t l = (with_codebook ? kWith : kWithout)[slot][k];
-            if (l != 255) t.level[slot][t.n[slot]++] = l;
-        }
-    return t;
-}
-
-NSIG_EXPORT int hg_warm_tables(const float *const *base_tables_host, const float *S, float *sink, nsig_stream_t stream) {
-    NSIG_REQUIRE(sink != nullptr, "hg_warm_tables: sink is one writable float (never written)");
-    TablePtrs base{};
-    if (int e = fill_base_tables(base_tables_host, base, "hg_warm_tables")) return e;
-    k_warm_tables<<<8 * 128, 256, 0, as_stream(stream)>>>(base, S, default_slots(S != nullptr), sink);
-    return check_launch("hg_warm_tables");
-}
-
-NSIG_EXPORT size_t hg_planes_bytes(uint32_t M) { return (size_t)(NSIG_BASE_LEVELS + 1) * ceil_div(M, 32u) * 32u * sizeof(float2); }
-
-// A plane set is in one of two layouts, NSIG_PLANES_F32 ([17][stride] float2) or NSIG_PLANES_MIXED (hg_encode_planes_mixed); the OWNER of the buffer says which when
-// it hands the set to an entry point that reads or completes it (field_fwd / field_fwd_rows / hg_encode_codebook_plane: `planes_layout`).
-static int check_layout(int layout, const char *who) {
-    NSIG_REQUIRE(layout == NSIG_PLANES_F32 || layout == NSIG_PLANES_MIXED, "%s: planes_layout must be NSIG_PLANES_F32 (0) or NSIG_PLANES_MIXED (1)", who);
-    return NSIG_OK;
-}
-
-static int encode_planes_impl(const float *xyzs, uint32_t M, float bound, const float *const *base_tables_host, const float *S, void *planes,
-                              const uint32_t *rows_dev, nsig_stream_t stream, bool mixed = false) {
-    if (M == 0) return NSIG_OK;
-    NSIG_REQUIRE(xyzs && planes, "hg_encode_planes: null pointer");
-    NSIG_REQUIRE(bound > 0.0f, "hg_encode_planes: bound must be positive");
-    NSIG_REQUIRE(aligned8(planes), "hg_encode_planes: planes must be 8-byte aligned");
-    TablePtrs base{};
-    if (int e = fill_base_tables(base_tables_host, base, "hg_encode_planes")) return e;
-    const uint32_t stride = ceil_div(M, 32u) * 32u;
-    const SlotTable tab = default_slots(S != nullptr);
-    int covered[NSIG_BASE_LEVELS + 1] = {};     // slots that encode the level: exactly one
-    for (int s = 0; s < 8; ++s)
-        for (int i = 0; i < tab.n[s]; ++i) covered[tab.level[s][i]] += 1;
-    for (int l = 0; l < NSIG_BASE_LEVELS + (S != nullptr ? 1 : 0); ++l)
-        NSIG_REQUIRE(covered[l] == 1, "hg_encode_planes: level %d is assigned to %d slots", l, covered[l]);
-    NSIG_REQUIRE(S != nullptr || covered[NSIG_BASE_LEVELS] == 0, "hg_encode_planes: slot table names the codebook level but S is NULL");
-    const uint32_t tiles = ceil_div(stride, 256u);
-    // tiles per XCD slot handled by distinct workgroups before they start looping: with one tile per workgroup (cap >= tiles) the block
-    // render's launch takes 244-247 us against 258-261 us with 1024 looping workgroups per slot (same-box sweep, profiles/r01_k_encoder_grid_sweep.txt)
-    const uint32_t per_slot = tiles < 8192u ? tiles : 8192u;
-    with_flag(mixed, [&](auto kMixed) {
-        k_encode_planes<decltype(kMixed)::value><<<per_slot * 8, 256, 0, as_stream(stream)>>>(xyzs, M, bound, base, make_level_geom(), S, reinterpret_cast<float2 *>(planes), stride, tab, rows_dev);
-    });
-    return check_launch("hg_encode_planes");
-}
-
-NSIG_EXPORT int hg_encode_planes_mixed(const float *xyzs, uint32_t M_capacity, const uint32_t *rows_dev, float bound, const float *const *base_tables_host,
-                                       const float *S, void *planes, nsig_stream_t stream) {
-    NSIG_REQUIRE(mlp_precision() == 1, "hg_encode_planes_mixed: the mixed layout carries the fp16 MLP's operands (mlp_set_precision(1))");
-    return encode_planes_impl(xyzs, M_capacity, bound, base_tables_host, S, planes, rows_dev, stream, true);
-}
-
-NSIG_EXPORT int hg_encode_planes(const float *xyzs, uint32_t M, float bound, const float *const *base_tables_host, const float *S, void *planes,
-                                 nsig_stream_t stream) {
-    return encode_planes_impl(xyzs, M, bound, base_tables_host, S, planes, nullptr, stream);
-}
-
-NSIG_EXPORT int hg_encode_planes_rows(const float *xyzs, uint32_t M_capacity, const uint32_t *rows_dev, float bound, const float *const *base_tables_host,
-                                      const float *S, void *planes, nsig_stream_t stream) {
-    NSIG_REQUIRE(rows_dev != nullptr, "hg_encode_planes_rows: null row count");
-    return encode_planes_impl(xyzs, M_capacity, bound, base_tables_host, S, planes, rows_dev, stream);
-}
-
-// hg_encode_planes[_rows|_mixed] over packed tables: encode_planes_impl's launch shape (one tile per workgroup and slot up to 8192 tiles), default_slots(signature present).
-NSIG_EXPORT int hg_encode_planes_packed(const float *xyzs, uint32_t M_capacity, const uint32_t *rows_dev, float bound, const void *const *tables_host, int format,
-                                        const float *params, void *planes, int planes_layout, nsig_stream_t stream) {
-    NSIG_REQUIRE(pk_row_bytes(format) != 0, "hg_encode_planes_packed: unknown format %d (0 f16, 1 q8, 2 q4)", format);
-    if (int e = check_layout(planes_layout, "hg_encode_planes_packed")) return e;
-    const bool mixed = planes_layout == NSIG_PLANES_MIXED;
-    NSIG_REQUIRE(!mixed || mlp_precision() == 1, "hg_encode_planes_packed: the mixed layout carries the fp16 MLP's operands (mlp_set_precision(1))");
-    NSIG_REQUIRE(xyzs && planes && tables_host, "hg_encode_planes_packed: null pointer");
-    NSIG_REQUIRE(format == NSIG_PACK_F16 || params != nullptr, "hg_encode_planes_packed: the q8 and q4 formats need the per-table parameters (params, pk_pack_tables')");
-    NSIG_REQUIRE(bound > 0.0f, "hg_encode_planes_packed: bound must be positive");
-    NSIG_REQUIRE(aligned8(planes) && aligned8(params), "hg_encode_planes_packed: planes and params must be 8-byte aligned");
-    PackedTablePtrs tabs{};
-    for (uint32_t i = 0; i <= NSIG_BASE_LEVELS; ++i) {
-        NSIG_REQUIRE((tables_host[i] != nullptr || i == NSIG_BASE_LEVELS) && aligned16(tables_host[i]), "hg_encode_planes_packed: table %u is null or not 16-byte aligned", i);
-        tabs.p[i] = tables_host[i];
+// The MLP over a finished plane set (field_fwd_impl's planes route, field_fwd_planes): the pipelined launch -- the training render's (masks) and staged no-grad
+// renders -- or the plain loop.  Neither reads anything but the set (k_field_fwd<P, 1> takes S only as the flag "plane 16 is there"), so they are handed no tables,
+// no points and -- as the flag -- the plane set's own address.
+static void launch_fwd_planes(const float *dirs, uint32_t M, const uint32_t *rows_dev, const char *pk, const float2 *pl, bool mixed, bool with_codebook, float *sigmas,
+                              float *rgbs, float *geo_feat, uint32_t *masks, hipStream_t st) {
+    const uint32_t stride = plane_stride(M);
+    if (mlp_precision() == 1 && fwd_pipelined() && dirs != nullptr && rgbs != nullptr && geo_feat == nullptr) {
+        with_flag(mixed, [&](auto kMixed) {
+            k_field_fwd_train<F16, decltype(kMixed)::value><<<field_grid(M, true, 2), 256, F16::kFwdLds, st>>>(dirs, M, with_codebook, pl, stride, pk, sigmas, rgbs, masks, rows_dev);
+        });
+        return;
     }
-    if (M_capacity == 0) return NSIG_OK;
-    const uint32_t stride = ceil_div(M_capacity, 32u) * 32u;
-    const SlotTable tab = default_slots(tabs.p[NSIG_BASE_LEVELS] != nullptr);
-    const uint32_t tiles = ceil_div(stride, 256u), per_slot = tiles < 8192u ? tiles : 8192u;
-    const float2 *ps = reinterpret_cast<const float2 *>(params);
-    float2 *pl = reinterpret_cast<float2 *>(planes);
-    hipStream_t st = as_stream(stream);
-    with_flag(mixed, [&](auto kMixed) {
-        constexpr bool kM = decltype(kMixed)::value;
-        if (format == NSIG_PACK_F16) k_encode_planes_packed<NSIG_PACK_F16, kM><<<per_slot * 8, 256, 0, st>>>(xyzs, M_capacity, bound, tabs, make_level_geom(), ps, pl, stride, tab, rows_dev);
-        else if (format == NSIG_PACK_Q8) k_encode_planes_packed<NSIG_PACK_Q8, kM><<<per_slot * 8, 256, 0, st>>>(xyzs, M_capacity, bound, tabs, make_level_geom(), ps, pl, stride, tab, rows_dev);
-        else k_encode_planes_packed<NSIG_PACK_Q4, kM><<<per_slot * 8, 256, 0, st>>>(xyzs, M_capacity, bound, tabs, make_level_geom(), ps, pl, stride, tab, rows_dev);
+    const float *flag = with_codebook ? reinterpret_cast<const float *>(pl) : nullptr;      // (never dereferenced by the planes route)
+    with_mlp([&](auto tag) {
+        using P = decltype(tag);
+        k_field_fwd<P, 1><<<field_grid(M, true), 256, P::kFwdLds, st>>>(nullptr, dirs, M, 1.0f, TablePtrs{}, make_level_geom(), flag, pl, stride, pk, sigmas, rgbs, geo_feat, masks, ActTrace{}, rows_dev, mixed);
     });
-    return check_launch("hg_encode_planes_packed");
-}
-
-NSIG_EXPORT int hg_encode_codebook_plane(const float *xyzs, uint32_t M, float bound, const float *S, void *planes, int planes_layout, void *plan_to_reset,
-                                         nsig_stream_t stream) {
-    if (M == 0) return NSIG_OK;
-    if (int e = check_layout(planes_layout, "hg_encode_codebook_plane")) return e;
-    NSIG_REQUIRE(xyzs && S && planes, "hg_encode_codebook_plane: null pointer");
-    NSIG_REQUIRE(bound > 0.0f, "hg_encode_codebook_plane: bound must be positive");
-    NSIG_REQUIRE(aligned8(planes), "hg_encode_codebook_plane: planes must be 8-byte aligned");
-    NSIG_REQUIRE(plan_to_reset == nullptr || aligned16(plan_to_reset), "hg_encode_codebook_plane: plan must be 16-byte aligned");
-    const uint32_t stride = ceil_div(M, 32u) * 32u;
-    float2 *plane = planes_layout == NSIG_PLANES_MIXED ? mixed_f32_plane(planes, stride, NSIG_BASE_LEVELS) : reinterpret_cast<float2 *>(planes) + (size_t)NSIG_BASE_LEVELS * stride;
-    k_encode_codebook_plane<<<ceil_div(stride, 256u), 256, 0, as_stream(stream)>>>(xyzs, M, bound, make_level_geom().cell[NSIG_BASE_LEVELS], S, plane, stride,
-                                                                                  reinterpret_cast<BinHeader *>(plan_to_reset));
-    return check_launch("hg_encode_codebook_plane");
 }
 
 static int field_fwd_impl(const float *xyzs, const float *dirs, uint32_t M, float bound, const float *const *base_tables_host,
@@ -1311,12 +925,12 @@ static int field_fwd_impl(const float *xyzs, const float *dirs, uint32_t M, floa
         return check_launch("field_fwd");
     }
     NSIG_REQUIRE(aligned8(planes), "field_fwd: planes must be 8-byte aligned");
-    const uint32_t stride = ceil_div(M, 32u) * 32u;
+    const uint32_t stride = plane_stride(M);
     const float2 *pl = reinterpret_cast<const float2 *>(planes);
     if (int e = check_layout(planes_layout, "field_fwd")) return e;
     const bool mixed = planes_layout == NSIG_PLANES_MIXED;
     NSIG_REQUIRE(!mixed || f16, "field_fwd: this plane set was written in the mixed (fp16) layout; the split-bf16 MLP needs hg_encode_planes");
-    if (sigmas_clean != nullptr) {      // field_fwd_twin (it checked its own arguments): the same choice of loop as below
+    if (sigmas_clean != nullptr) {      // field_fwd_twin (it checked its own arguments): the same choice of loop as launch_fwd_planes'
         if (f16 && fwd_pipelined() && geo_feat == nullptr) {
             with_flag(mixed, [&](auto kMixed) {
                 k_field_fwd_train_twin<F16, decltype(kMixed)::value><<<field_grid(M, true, 2), 256, F16::kFwdLds, st>>>(dirs, M, pl, stride, pk, sigmas, rgbs, masks, sigmas_clean, rgbs_clean);
@@ -1329,16 +943,7 @@ static int field_fwd_impl(const float *xyzs, const float *dirs, uint32_t M, floa
         }
         return check_launch("field_fwd_twin");
     }
-    if (f16 && fwd_pipelined() && dirs != nullptr && rgbs != nullptr && geo_feat == nullptr) {    // the training render's launch (masks) and staged no-grad renders
-        with_flag(mixed, [&](auto kMixed) {
-            k_field_fwd_train<F16, decltype(kMixed)::value><<<field_grid(M, true, 2), 256, F16::kFwdLds, st>>>(dirs, M, S != nullptr, pl, stride, pk, sigmas, rgbs, masks, rows_dev);
-        });
-        return check_launch("field_fwd");
-    }
-    with_mlp([&](auto tag) {
-        using P = decltype(tag);
-        k_field_fwd<P, 1><<<field_grid(M, true), 256, P::kFwdLds, st>>>(xyzs, dirs, M, bound, base, make_level_geom(), S, pl, stride, pk, sigmas, rgbs, geo_feat, masks, ActTrace{}, rows_dev, mixed);
-    });
+    launch_fwd_planes(dirs, M, rows_dev, pk, pl, mixed, S != nullptr, sigmas, rgbs, geo_feat, masks, st);
     return check_launch("field_fwd");
 }
 
@@ -1357,34 +962,6 @@ NSIG_EXPORT int field_fwd_twin(const float *xyzs, const float *dirs, uint32_t M,
     return field_fwd_impl(xyzs, dirs, M, bound, base_tables_host, S, packed, sigmas, rgbs, geo_feat, masks, planes, planes_layout, nullptr, stream, sigmas_clean, rgbs_clean);
 }
 
-// ---- K messages over one set of points (hg_codebook_presum_multi in hashgrid.hip makes S_multi)
-static int check_multi_k(uint32_t K, const char *who) {
-    NSIG_REQUIRE(K >= 1 && K <= NSIG_MULTI_MAX_MESSAGES, "%s: K=%u out of range [1,%d]", who, K, NSIG_MULTI_MAX_MESSAGES);
-    return NSIG_OK;
-}
-
-NSIG_EXPORT size_t hg_multi_planes_bytes(uint32_t M, uint32_t K) { return (size_t)K * ceil_div(M, 32u) * 32u * sizeof(float2); }
-
-NSIG_EXPORT int hg_encode_codebook_planes_multi(const float *xyzs, uint32_t M, float bound, const void *S_multi, uint32_t K, void *cplanes, nsig_stream_t stream) {
-    NSIG_REQUIRE(xyzs && S_multi && cplanes, "hg_encode_codebook_planes_multi: null pointer");
-    if (int e = check_multi_k(K, "hg_encode_codebook_planes_multi")) return e;
-    NSIG_REQUIRE(bound > 0.0f, "hg_encode_codebook_planes_multi: bound must be positive");
-    NSIG_REQUIRE(aligned16(S_multi), "hg_encode_codebook_planes_multi: S_multi must be 16-byte aligned");
-    NSIG_REQUIRE(aligned8(cplanes), "hg_encode_codebook_planes_multi: cplanes must be 8-byte aligned");
-    NSIG_REQUIRE(M <= (1u << 27), "hg_encode_codebook_planes_multi: M=%u too large", M);
-    if (M == 0) return NSIG_OK;
-    const uint32_t stride = ceil_div(M, 32u) * 32u;
-    const bool pair = (K & 1u) == 0u;
-    const uint32_t G = pair ? K / 2 : K;
-    const uint32_t grid = (uint32_t)(((uint64_t)stride * G + 255) / 256);
-    const float cell = make_level_geom().cell[NSIG_BASE_LEVELS];
-    const float2 *S = reinterpret_cast<const float2 *>(S_multi);
-    with_flag(pair, [&](auto kPair) {
-        k_encode_codebook_planes_multi<decltype(kPair)::value><<<grid, 256, 0, as_stream(stream)>>>(xyzs, M, bound, cell, S, K, G, reinterpret_cast<float2 *>(cplanes), stride);
-    });
-    return check_launch("hg_encode_codebook_planes_multi");
-}
-
 NSIG_EXPORT int field_fwd_multi(const float *dirs, uint32_t M, const void *packed, const void *planes, int planes_layout, const void *cplanes, uint32_t K,
                                 float *sigmas, float *rgbs, nsig_stream_t stream) {
     NSIG_REQUIRE(dirs && packed && planes && cplanes && sigmas && rgbs, "field_fwd_multi: null pointer");
@@ -1396,7 +973,7 @@ NSIG_EXPORT int field_fwd_multi(const float *dirs, uint32_t M, const void *packe
     NSIG_REQUIRE(!mixed || f16, "field_fwd_multi: this plane set was written in the mixed (fp16) layout; the split-bf16 MLP needs hg_encode_planes");
     NSIG_REQUIRE(M <= (1u << 27), "field_fwd_multi: M=%u too large", M);      // (the same range as the gather that fills cplanes: row indices and the stride stay far from 2^32)
     if (M == 0) return NSIG_OK;
-    const uint32_t stride = ceil_div(M, 32u) * 32u;
+    const uint32_t stride = plane_stride(M);
     const float2 *pl = reinterpret_cast<const float2 *>(planes), *cp = reinterpret_cast<const float2 *>(cplanes);
     const char *pk = reinterpret_cast<const char *>(packed);
     hipStream_t st = as_stream(stream);
@@ -1414,8 +991,7 @@ NSIG_EXPORT int field_fwd_rows(const float *xyzs, const float *dirs, uint32_t M_
     return field_fwd_impl(xyzs, dirs, M_capacity, bound, base_tables_host, S, packed, sigmas, rgbs, nullptr, nullptr, planes, planes_layout, rows_dev, stream);
 }
 
-// The MLP over a finished plane set, without a table list: the kernels of field_fwd_impl's planes route read nothing but the set (k_field_fwd<P, 1> takes S only as
-// the flag "plane 16 is there"), so this launcher hands them no tables, no points and -- as the flag -- the plane set's own address.  Same choice of loop as there.
+// The MLP over a finished plane set, without a table list.
 NSIG_EXPORT int field_fwd_planes(const float *dirs, uint32_t M_capacity, const uint32_t *rows_dev, const void *packed, const void *planes, int planes_layout,
                                  int with_codebook, float *sigmas, float *rgbs, float *geo_feat, nsig_stream_t stream) {
     NSIG_REQUIRE(packed && planes && sigmas, "field_fwd_planes: null pointer");
@@ -1426,21 +1002,8 @@ NSIG_EXPORT int field_fwd_planes(const float *dirs, uint32_t M_capacity, const u
     const bool f16 = mlp_precision() == 1, mixed = planes_layout == NSIG_PLANES_MIXED;
     NSIG_REQUIRE(!mixed || f16, "field_fwd_planes: this plane set was written in the mixed (fp16) layout; the split-bf16 MLP needs an fp32 set (NSIG_PLANES_F32)");
     if (M_capacity == 0) return NSIG_OK;
-    const uint32_t M = M_capacity, stride = ceil_div(M, 32u) * 32u;
-    const float2 *pl = reinterpret_cast<const float2 *>(planes);
-    const char *pk = reinterpret_cast<const char *>(packed);
-    const float *flag = with_codebook ? reinterpret_cast<const float *>(planes) : nullptr;      // (never dereferenced by the planes route)
-    hipStream_t st = as_stream(stream);
-    if (f16 && fwd_pipelined() && dirs != nullptr && rgbs != nullptr && geo_feat == nullptr) {
-        with_flag(mixed, [&](auto kMixed) {
-            k_field_fwd_train<F16, decltype(kMixed)::value><<<field_grid(M, true, 2), 256, F16::kFwdLds, st>>>(dirs, M, flag != nullptr, pl, stride, pk, sigmas, rgbs, nullptr, rows_dev);
-        });
-        return check_launch("field_fwd_planes");
-    }
-    with_mlp([&](auto tag) {
-        using P = decltype(tag);
-        k_field_fwd<P, 1><<<field_grid(M, true), 256, P::kFwdLds, st>>>(nullptr, dirs, M, 1.0f, TablePtrs{}, make_level_geom(), flag, pl, stride, pk, sigmas, rgbs, geo_feat, nullptr, ActTrace{}, rows_dev, mixed);
-    });
+    launch_fwd_planes(dirs, M_capacity, rows_dev, reinterpret_cast<const char *>(packed), reinterpret_cast<const float2 *>(planes), mixed, with_codebook != 0, sigmas, rgbs,
+                      geo_feat, nullptr, as_stream(stream));
     return check_launch("field_fwd_planes");
 }
 
@@ -1500,7 +1063,7 @@ static int fwd_trace_impl(const float *xyzs, const float *dirs, uint32_t M, cons
     NSIG_REQUIRE(M <= (1u << 26), "field_fwd_trace: M=%u out of range (<= 2^26: the lane part of a trace address is a 32-bit byte offset of up to 32 x stride)", M);
     TablePtrs base{};
     if (int e = fill_base_tables(base_tables_host, base, "field_fwd_trace")) return e;
-    const uint32_t stride = ceil_div(M, 32u) * 32u;
+    const uint32_t stride = plane_stride(M);
     ActTrace tr{act_hs, act_cin, act_h1, act_h2};
     if (trace_f16)      // (the ActTrace pointers address _Float16 rows)
         k_field_fwd_trace<_Float16><<<field_grid(M), 256, Bf16x3::kFwdLds, as_stream(stream)>>>(dirs, M, reinterpret_cast<const float2 *>(planes), stride,
@@ -1543,7 +1106,7 @@ static int bwd_trace_impl(uint32_t M, const uint32_t *rows_dev, const float *gra
     NSIG_REQUIRE(grad_sigmas && grad_rgbs && sigmas && rgbs && masks && packed && d_hs && d_so && d_h1 && d_h2 && d_out && d_planes,
                  "field_bwd_trace: null pointer");
     NSIG_REQUIRE(M <= (1u << 26), "field_bwd_trace: M=%u out of range (<= 2^26: the lane part of a trace address is a 32-bit byte offset of up to 32 x stride)", M);
-    const uint32_t stride = ceil_div(M, 32u) * 32u;
+    const uint32_t stride = plane_stride(M);
     GradTrace gt{d_hs, d_h1, d_h2, d_so, d_out, reinterpret_cast<float2 *>(d_planes)};
     k_field_bwd<Bf16x3, true><<<field_grid(M), 256, Bf16x3::kBwdLds, as_stream(stream)>>>(nullptr, M, 1.0f, 1.0f / kCodebookResolution, grad_sigmas, grad_rgbs, sigmas,
                                                                                rgbs, masks, reinterpret_cast<const char *>(packed), nullptr, nullptr,

@@ -1,4 +1,4 @@
-// Device-side hash-grid lookup shared by hashgrid.hip and field.hip.
+// Device-side hash-grid lookup shared by hashgrid.hip, encode.hip and field.hip.
 //
 // Behavioural reference: /root/reference/hash_encoding.py:11-46,73-94 (get_voxel_vertices, hash,
 // trilinear_interp) with bounding box (0,1), T = 2^19 rows of 2 features, every level hashed.

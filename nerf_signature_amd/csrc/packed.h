@@ -1,4 +1,4 @@
-// Row words of a PACKED table (include/nerfsig.h "packed released model"): what csrc/packed.hip writes and what the packed encoder in csrc/field.hip gathers.
+// Row words of a PACKED table (include/nerfsig.h "packed released model"): what csrc/packed.hip writes and what the packed row source of csrc/encode.hip gathers.
 // A table is NSIG_TABLE_ROWS rows of 2 features; a row is ONE word of 4 (f16), 2 (q8) or 1 (q4) bytes, feature 0 in its low half.
 //   decode:  f16  (float)(_Float16)h
 //            q8 / q4  lo + (float)q * step -- the product and the sum each rounded on its own (written with the explicit round-to-nearest intrinsics, and the

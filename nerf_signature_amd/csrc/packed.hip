@@ -1,7 +1,7 @@
 // Packed tables of a released model (include/nerfsig.h "packed released model"): the 17 fp32 tables of release.ReleasedModel stored as fp16
 // pairs, 8-bit or 4-bit codes, with the quantiser of the tamper kernels (csrc/tamper.hip: NSIG_TAMPER_HALF, NSIG_TAMPER_QUANTIZE at 8 / 4 bits) -- so that
-// decode(pack(x)) is, bit for bit, what tm_apply leaves in the fp32 table.  The encoder that gathers from such tables is in csrc/field.hip
-// (k_encode_planes_packed); the row words and their decode in csrc/packed.h.
+// decode(pack(x)) is, bit for bit, what tm_apply leaves in the fp32 table.  The encoder that gathers from such tables is in csrc/encode.hip
+// (k_encode_planes<PackedTables<FMT>, mixed>); the row words and their decode in csrc/packed.h.
 //
 //   pack    one launch over the whole list: workgroup (table, chunk) turns 1024 rows (8 KiB of fp32) into 4 KiB / 2 KiB / 1 KiB of row words; a thread reads its four
 //           rows as two 16-byte loads and writes them as ONE 16-, 8- or 4-byte store.  lo and step are computed by every workgroup from the table's statistics

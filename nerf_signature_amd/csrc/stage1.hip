@@ -11,6 +11,7 @@
 // The level scatter of the base-table gradients lives beside its siblings in hashgrid.hip (hg_levels_plan / hg_levels_scatter).
 #include "hashgrid.h"
 #include "mfma.h"
+#include "planes.h"
 #include "wave.h"
 
 namespace nsig {
@@ -280,7 +281,7 @@ NSIG_EXPORT int field_wgrad(uint32_t M, const uint32_t *rows_dev, const void *pl
     NSIG_REQUIRE(M >= 1 && M < (1u << 28), "field_wgrad: M=%u out of range", M);
     const void *all[] = {planes, act_hs, act_cin, act_h1, act_h2, d_hs, d_so, d_h1, d_h2, d_out, scratch};
     for (const void *p : all) NSIG_REQUIRE(aligned16(p), "field_wgrad: every buffer must be 16-byte aligned");
-    const uint32_t stride = ceil_div(M, 32u) * 32u, n_wg = wgrad_workgroups(M);
+    const uint32_t stride = plane_stride(M), n_wg = wgrad_workgroups(M);
     WgradArgs a{reinterpret_cast<const float2 *>(planes), act_hs, act_cin, act_h1, act_h2, d_hs, d_so, d_h1, d_h2, d_out};
     hipStream_t st = as_stream(stream);
     k_field_wgrad<<<dim3(n_wg, kWgradRoles), 256, 0, st>>>(a, stride, M, rows_dev, reinterpret_cast<float *>(scratch));

@@ -20,6 +20,7 @@
 // One workgroup per compute unit (48 KiB of split-bf16 backward weights + 4 x 18 KiB of scratch); nothing but d_planes (128 B per point, the table
 // scatter's input) is written per point.
 #include "fieldmlp.h"
+#include "planes.h"
 
 namespace nsig {
 
@@ -344,7 +345,7 @@ static int bwd_wgrad_impl(const char *who, bool trace_f16, uint32_t M, const uin
     NSIG_REQUIRE(M >= 1 && M <= (1u << 26), "%s: M=%u out of range (1 .. 2^26, as field_fwd_trace: the lane part of an address is a 32-bit byte offset of up to 32 x stride)", who, M);
     const void *all[] = {packed, planes, act_hs, act_cin, act_h1, act_h2, d_planes, scratch};
     for (const void *q : all) NSIG_REQUIRE(aligned16(q), "%s: packed, planes, the layer inputs, d_planes and scratch must be 16-byte aligned", who);
-    const uint32_t stride = ceil_div(M, 32u) * 32u, n_wg = fused_workgroups(M);
+    const uint32_t stride = plane_stride(M), n_wg = fused_workgroups(M);
     FusedArgs a{grad_sigmas, grad_rgbs, sigmas, rgbs, masks, reinterpret_cast<const char *>(packed), reinterpret_cast<const float2 *>(planes),
                 reinterpret_cast<const float *>(act_hs), reinterpret_cast<const float *>(act_cin), reinterpret_cast<const float *>(act_h1), reinterpret_cast<const float *>(act_h2),
                 reinterpret_cast<float2 *>(d_planes), reinterpret_cast<float *>(scratch)};

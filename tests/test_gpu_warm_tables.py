@@ -1,4 +1,4 @@
-"""The warm-up pass (hg_warm_tables, csrc/field.hip) reads one table per XCD -- the finest its workgroups gather from -- and writes nothing.
+"""The warm-up pass (hg_warm_tables, csrc/encode.hip) reads one table per XCD -- the finest its workgroups gather from -- and writes nothing.
 
 The 16 base tables, the pre-summed codebook S and the sink word are bit-identical after the pass with S and without it (a clean model: another slot assignment),
 and a field pass behind it gives what it gives without warming; a null sink, a null table list and a null table are refused."""

@@ -12,7 +12,7 @@ import sys
 
 KERNELS = {"k_field_bwd_wgrad": "k_field_bwd_wgrad", "k_field_wgrad": "k_field_wgrad", "k_level_entries": "k_level_entries", "k_scatter_binned": "k_scatter_binned",
            "k_levels_count": "k_levels_count", "k_field_fwd<Bf16x3, 1, true>": "k_field_fwd_trace", "k_field_fwd_trace": "k_field_fwd_trace", "k_field_fwd_trace<float>": "k_field_fwd_trace", "k_field_bwd_wgrad<float>": "k_field_bwd_wgrad", "k_field_bwd<Bf16x3, true>": "k_field_bwd_trace",
-           "k_encode_planes": "k_encode_planes", "k_encode_planes<false>": "k_encode_planes", "k_wgrad_reduce": "k_wgrad_reduce"}
+           "k_encode_planes": "k_encode_planes", "k_encode_planes<false>": "k_encode_planes", "k_encode_planes<F32Tables, false>": "k_encode_planes", "k_wgrad_reduce": "k_wgrad_reduce"}
 
 
 def main():
