@@ -66,7 +66,9 @@ int rm_packbits(const float *grid, uint32_t n_bytes, float density_thresh, uint8
  *                      the order the density query wants -- and ids[2N], the draw each came from.  scratch: rg_refresh_draw_scratch_bytes(N, H) bytes
  *   rg_refresh_points  probe point and morton cell index of every key (keys / ids NULL: the full form, key = id = i, n = H^3): cell centre (:474,480-482) + jitter (:484)
  *   (the density query is hg_encode_planes + field_fwd)
- *   rg_refresh_scatter fresh[cell] = max(fresh[cell], sigma * density_scale), fresh pre-filled with -1 (:489,:514; repeated cells: the largest candidate, deterministically)
+ *   rg_refresh_scatter fresh[cell] = max(fresh[cell], sigma * density_scale), fresh pre-filled with -1 (:489,:514; repeated cells: the largest candidate, deterministically).
+ *                      Only candidates >= 0 land (-0.0 as +0: the cell decays, :521); a negative one is skipped (a cell with no other stays -1 and keeps its grid value);
+ *                      a NaN lands, wins over every number and stays NaN in fresh (rg_refresh_finish leaves such a cell's grid value alone)
  * and once per refresh
  *   rg_refresh_finish  grid = max(grid * decay, fresh) where both >= 0 (:521-522), *mean_density = mean(clamp(grid, 0)) (:523), bitfield packed at
  *                      min(*mean_density, density_thresh) (:528-529), *iter_dev += 1, and for window > 0 *mean_count = int(sum of the ring's last `window` sample totals /

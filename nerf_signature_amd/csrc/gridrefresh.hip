@@ -15,6 +15,7 @@
 //         -> rg_refresh_finish: k_grid_ema (per-workgroup partial sums in double, fixed order) -> k_grid_stats (one workgroup: the mean, the refresh
 //            count, the mean sample count of the window from the loop's ring) -> k_packbits_dev (threshold read from device memory).
 // Everything is a pure function of (grid, parameters, seed, refresh count): two runs leave the same bits (tests/test_gpu_stage1.py, test_gpu_grid.py).
+// Every entry point alone against tests/grid_refresh_ref.py, exactly: tests/test_gpu_grid.py (`test_rg_*`); that restatement and every refusal: tests/test_grid_refresh_cpu.py.
 #include "wave.h"
 
 namespace nsig {
@@ -225,14 +226,16 @@ __global__ void __launch_bounds__(256) k_refresh_points(const int32_t *__restric
     cells[i] = (int32_t)morton3(x, y, z);
 }
 
-// fresh[cell] = max(fresh[cell], sigma * density_scale): fresh starts at -1 (negative as an integer too), the candidates are >= 0, and for non-negative floats the
-// integer order of the bit patterns is the float order.  A NaN density (diverged parameters) has the largest pattern of all and stays visible.
+// fresh[cell] = max(fresh[cell], sigma * density_scale) over the candidates the reference's `tmp >= 0` (:521) lets through: fresh starts at -1 (negative as an integer
+// too), and for non-negative floats the integer order of the bit patterns is the float order.  A negative candidate is not written -- a cell with no other stays -1 and
+// the EMA leaves it alone, as the reference does; -0.0 passes `>= 0` there and here, and lands as +0 (its own pattern is INT_MIN and would lose to the fill).  A NaN
+// density (diverged parameters) lands with its sign cleared: the largest pattern of all, it stays visible in `fresh`, and the EMA leaves such a cell alone too.
 __global__ void __launch_bounds__(256) k_refresh_scatter(const float *__restrict__ sigmas, const int32_t *__restrict__ cells, uint32_t n, float density_scale,
                                                         float *__restrict__ fresh) {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     if (i >= n) return;
     const float v = sigmas[i] * density_scale;
-    atomicMax(reinterpret_cast<int *>(fresh) + cells[i], __float_as_int(v >= 0.0f || v != v ? v : 0.0f));
+    if (v >= 0.0f || v != v) atomicMax(reinterpret_cast<int *>(fresh) + cells[i], __float_as_int(fabsf(v)));
 }
 
 constexpr uint32_t kEmaThreads = 256, kEmaPerThread = 16;      // 4096 cells per workgroup: 512 partial sums for one 128^3 cascade
