@@ -862,6 +862,61 @@ int mc_vertex_normals(const float *u, uint32_t nx, uint32_t ny, uint32_t nz, flo
 size_t mesh_components_scratch_bytes(uint32_t V, uint32_t T);
 int mesh_components(const int32_t *triangles, uint32_t T, uint32_t V, int32_t *labels, void *scratch, nsig_stream_t stream);
 
+/* ------------------------------------------------------------------ mesh rasteriser */
+
+/*
+ * Renders a triangle mesh (mc_emit's, or any other) from a pinhole camera, so that an exported mesh can be looked at, compared with the field it came from and
+ * put through release.verify (nerf_signature_amd/raster.py; this project's own evaluation -- the reference has no counterpart).  The answer is unique: integer
+ * coverage and a 64-bit (depth bits, triangle index) minimum per pixel, so two runs, and any order of arrival, give the same bits.  Nothing is allocated, no
+ * device value is read on the host, no thread waits for another and every loop ends on its own.  Camera conventions are get_rays' (rg_get_rays): pose is a
+ * row-major camera-to-world [4,4] in DEVICE memory (R = its upper-left 3 x 3, t = its last column), camera +z looks forward, x right, y down; pixel (i, j) --
+ * column i, row j -- has its centre at (i + 0.5, j + 0.5); intrinsics fx, fy, cx, cy.  1 <= H, W <= 4096; V, T < 2^31.
+ *
+ * scratch: rs_scratch_bytes(V, T, H, W) bytes (0 = out of range), 16-byte aligned, need not be initialised, the same for the three calls of one view and
+ * reusable for the next.  With a(n) = n rounded up to a multiple of 256 its layout is
+ *   [0, 256)              status, 32-bit words: 0 = 0xffffffff or the smallest index of a triangle with an id outside [0, V); 1 = triangles skipped for a vertex
+ *                         behind the near plane; 2 = triangles skipped for a vertex outside the guard band; 3 = triangles that took the large route
+ *   then a(16 V) bytes    screen records, four words per vertex: int32 x, int32 y, float iz, uint32 flag
+ *   then a(8 H W) bytes   z-buffer, uint64 per pixel, row-major [H, W]: all ones, or (bits of the float depth) << 32 | triangle index
+ *   then a(4 T) bytes     the large route's list of triangle indices (its order is the one thing here that depends on arrival; nothing reads it but rs_raster)
+ * The caller reads the status words after the stream has finished.
+ *
+ * rs_project: vertices [V, 3] fp32 world positions -> the screen records; resets the z-buffer and the status words.  One launch.  All arithmetic is fp32 and every
+ * operation is rounded on its own (the library is built with -ffp-contract=off), in this order: d = p - t; Xc = (R00 d0 + R10 d1) + R20 d2, Yc and Zc the same with
+ * columns 1 and 2 of R; u = fx (Xc / Zc) + cx, v = fy (Yc / Zc) + cy; iz = 1.0f / Zc.  flag, the first that applies: 1 when !(Zc >= near) (NaN lands here);
+ * 2 when |u| or |v| exceeds NSIG_RASTER_GUARD_PIXELS or is not finite; else 0.  x = (int32)rintf(u * 256), y = (int32)rintf(v * 256): 8 sub-pixel bits, round half
+ * to even.  A flagged vertex's record is (0, 0, 0.0f, flag).  near: finite and > 0.
+ *
+ * rs_raster: triangles [T, 3] int32 -> the z-buffer.  V = 0 or T = 0 launches nothing, otherwise two launches.  Per triangle (a, b, c), in this order:
+ *   bad ids    an id outside [0, V): skipped, never dereferenced, status word 0 = min(status word 0, its index) (mesh_components' convention).
+ *   culled     a vertex with flag 1: skipped, counted in status word 1; else a vertex with flag 2: skipped, counted in word 2.  There is NO near-plane clipping: a
+ *              triangle that crosses the near plane leaves a hole, and the counts tell the caller that holes are coming.
+ *   area       A2 = (xb - xa)(yc - ya) - (yb - ya)(xc - xa) in int64 on the fixed-point coordinates.  A2 == 0: skipped.  A2 < 0: b and c change places (and A2 its
+ *              sign), here and in everything below -- both windings are drawn, nothing is culled by orientation.
+ *   coverage   at the pixel centre P = (256 i + 128, 256 j + 128), with E(p -> q) = (xq - xp)(yP - yp) - (yq - yp)(xP - xp) in int64: E_a = E(b -> c), E_b = E(c -> a),
+ *              E_c = E(a -> b) (E_a + E_b + E_c = A2).  The pixel is covered when every E_k is > 0, or is == 0 on an edge the TOP-LEFT RULE gives to this triangle:
+ *              the directed edge p -> q with dy = yq - yp < 0 (a left edge: with A2 > 0 and y down the vertices run clockwise on the screen), or with dy == 0 and
+ *              dx = xq - xp > 0 (a top edge).  The neighbour across a shared edge walks it in the opposite direction, so a centre on the edge belongs to exactly
+ *              one of two triangles that do not overlap, and a centre on the hub of a closed fan to exactly one triangle of the fan.
+ *   depth      in float64, every operation rounded on its own: b_k = (double)E_k / (double)A2; q = (b_a iz_a + b_b iz_b) + b_c iz_c; depth = (float)(1.0 / q).
+ *   winner     atomic minimum of the pixel's z-buffer word with (bits of depth) << 32 | triangle index: the nearest wins, equal depths go to the lower index.
+ * Routes: a triangle whose box of pixel centres, clamped to the image, holds at most NSIG_RASTER_SMALL_BOX centres is drawn by the lane that classified it (first
+ * launch, one lane per triangle); a larger one is appended to the list -- one ballot and one atomic add per wave -- and drawn by the second launch, a fixed grid of
+ * waves that reads the list's length on the device, one wave per listed triangle, its lanes striding the box.  Both routes call one coverage-and-depth body.
+ *
+ * rs_shade: z-buffer, records and the SAME triangles, colours [V, 3] fp32 and bg[3] -> image [H, W, 3] fp32, depth [H, W] fp32, triangle [H, W] int32.  One launch, one
+ * lane per pixel.  An untouched pixel: bg, +infinity, -1.  Otherwise the winner's b_k and q are recomputed exactly as above and, in float64, every operation
+ * rounded on its own: w_k = b_k (double)iz_k; per channel n = (w_a c_a + w_b c_b) + w_c c_c; rgb = (float)(n / q) -- perspective-correct.  Nothing is clamped.
+ */
+#define NSIG_RASTER_SMALL_BOX 64u
+#define NSIG_RASTER_GUARD_PIXELS 16384.0f
+size_t rs_scratch_bytes(uint32_t V, uint32_t T, uint32_t H, uint32_t W);
+int rs_project(const float *vertices, uint32_t V, const float *pose, float fx, float fy, float cx, float cy, float near, uint32_t H, uint32_t W, void *scratch,
+               nsig_stream_t stream);
+int rs_raster(const int32_t *triangles, uint32_t T, uint32_t V, uint32_t H, uint32_t W, void *scratch, nsig_stream_t stream);
+int rs_shade(const int32_t *triangles, uint32_t T, uint32_t V, const float *colors, const float *bg, uint32_t H, uint32_t W, const void *scratch, float *image,
+             float *depth, int32_t *triangle, nsig_stream_t stream);
+
 /* ------------------------------------------------------------------ image metrics */
 
 /*

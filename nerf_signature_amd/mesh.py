@@ -12,7 +12,9 @@ on the CPU and exports a PLY through trimesh.  Here the lattice stays on the dev
 Opt-in mesh attributes and cleaning, all on the device ("Mesh attributes"):
 
     vertex_normals(u, threshold, scratch=None, scale=(1, 1, 1))   the normals of marching_cubes' vertices (mc_vertex_normals)
-    vertex_colors(model, vertices_world, normals, message=None)   the colour head seen against the normal, rgb [V,3] fp32
+    vertex_colors(model, vertices_world, normals, message=None, directions=None)   the colour head seen against the normal (or along given directions), rgb [V,3] fp32
+    occupied(model, bound_min, bound_max, resolution)             which lattice nodes lie in cells the model's occupancy bitfield marks, bool [R,R,R]
+    read_ply(path)                                                what write_ply wrote, back (raster.render_mesh draws it: tools/mesh_view.py)
     components(triangles, n_vertices)                             labels [V] int32: the smallest vertex id of each component (mesh_components)
     clean(vertices, triangles, min_triangles=0, keep_largest=None, attributes=())   drop small components, stable compaction
 
@@ -157,6 +159,31 @@ def lattice(model, bound_min, bound_max, resolution, message=None):
 
 
 @torch.no_grad()
+def occupied(model, bound_min, bound_max, resolution):
+    """bool [R,R,R] on the model's device: which nodes of lattice()'s lattice lie in a cell the model's occupancy bitfield marks -- the only places a render of the
+    model ever evaluates the field.  The cascade of a node is the smallest whose cube holds it (the marcher's rule for a position), the cell floor((p / extent + 1) / 2 *
+    grid_size) clamped, the bit at its morton index (x -> bit 0).  `torch.where(occupied(...), lattice(...), -1)` is the density a render can see."""
+    R, G, C = int(resolution), int(model.grid_size), int(model.cascade)
+    dev = model.density_bitfield.device
+    ax = torch.stack(_axes(bound_min, bound_max, R)).to(dev)
+    p = torch.stack(torch.meshgrid(ax[0], ax[1], ax[2], indexing="ij"), dim=-1).reshape(-1, 3)
+    linf = p.abs().amax(dim=-1).clamp_min(1e-6)
+    cas = torch.ceil(torch.log2(linf)).clamp(0, C - 1).long()
+    extent = torch.minimum(torch.pow(2.0, cas.float()), torch.tensor(float(model.bound), device=dev))
+    cell = torch.floor((p / extent[:, None] + 1.0) * (0.5 * G)).long().clamp(0, G - 1)
+
+    def spread(v):
+        v = (v * 0x00010001) & 0xFF0000FF
+        v = (v * 0x00000101) & 0x0F00F00F
+        v = (v * 0x00000011) & 0xC30C30C3
+        return (v * 0x00000005) & 0x49249249
+
+    bit = cas * G ** 3 + (spread(cell[:, 0]) | (spread(cell[:, 1]) << 1) | (spread(cell[:, 2]) << 2))
+    byte = model.density_bitfield[bit >> 3].long()
+    return ((byte >> (bit & 7)) & 1).bool().view(R, R, R)
+
+
+@torch.no_grad()
 def query_lattice(bound_min, bound_max, resolution, query_func, device=None):
     """extract_fields with the lattice kept on the device: the same axes, 128^3 chunks and point order, any callable, no per-chunk host copy."""
     R = int(resolution)
@@ -205,18 +232,25 @@ def world_vertices(vertices, bound_min, bound_max, resolution):
 
 
 @torch.no_grad()
-def vertex_colors(model, vertices_world, normals, message=None):
+def vertex_colors(model, vertices_world, normals, message=None, directions=None):
     """rgb float32 [V,3] on the device: the model's colour head at every vertex, seen against the normal -- position float32(vertices_world), view
     direction -normal, (0, 0, 1) where the normal is zero.  Queried through field_forward as lattice() queries the density (NeRFNetwork with or without a
-    message, CleanNeRFNetwork), in chunks of about 2 M vertices: up to one chunk the result is bit-equal to one model(x, d, message) call on these rows."""
+    message, CleanNeRFNetwork), in chunks of about 2 M vertices: up to one chunk the result is bit-equal to one model(x, d, message) call on these rows.
+    directions: view directions [V,3] to use as they are instead of -normal (raster.view_directions: the mesh coloured as one camera sees the field);
+    the normals are then not looked at and may be None."""
     bound, tables, S, packed = _field_of(model, message)
     dev = packed.device
     x = torch.as_tensor(vertices_world).to(dev, torch.float32).reshape(-1, 3).contiguous()
-    n = torch.as_tensor(normals).to(dev, torch.float32).reshape(-1, 3)
-    if n.shape != x.shape:
-        raise ValueError(f"vertex_colors: {x.shape[0]} vertices with {n.shape[0]} normals")
-    zero = (n == 0).all(dim=-1, keepdim=True)
-    d = torch.where(zero, torch.tensor([0.0, 0.0, 1.0], device=dev), -n).contiguous()
+    if directions is not None:
+        d = torch.as_tensor(directions).to(dev, torch.float32).reshape(-1, 3).contiguous()
+        if d.shape != x.shape:
+            raise ValueError(f"vertex_colors: {x.shape[0]} vertices with {d.shape[0]} directions")
+    else:
+        n = torch.as_tensor(normals).to(dev, torch.float32).reshape(-1, 3)
+        if n.shape != x.shape:
+            raise ValueError(f"vertex_colors: {x.shape[0]} vertices with {n.shape[0]} normals")
+        zero = (n == 0).all(dim=-1, keepdim=True)
+        d = torch.where(zero, torch.tensor([0.0, 0.0, 1.0], device=dev), -n).contiguous()
     V = x.shape[0]
     rgb = torch.empty(V, 3, dtype=torch.float32, device=dev)
     n_chunks = max(1, math.ceil(V / LATTICE_CHUNK))
@@ -355,6 +389,66 @@ def write_ply(path, vertices, triangles, normals=None, colors=None):
         f.write(header.encode("ascii"))
         f.write(record.tobytes())
         f.write(faces.tobytes())
+
+
+_PLY_VERTEX = ["property double x", "property double y", "property double z"]
+_PLY_NORMAL = ["property float nx", "property float ny", "property float nz"]
+_PLY_COLOR = ["property uchar red", "property uchar green", "property uchar blue"]
+
+
+def read_ply(path):
+    """The binary PLY write_ply writes, back: {"vertices" float64 [V,3], "triangles" int32 [T,3], "normals" float32 [V,3] or None, "colors" uint8 [V,3] or None}
+    as numpy arrays.  Exactly that layout is read -- little-endian binary, double positions, then optional float normals, then optional uchar colours, faces as
+    `list uchar int vertex_indices` of three -- and any other is refused with the line or the size that differs."""
+    with open(path, "rb") as f:
+        data = f.read()
+    end = data.find(b"end_header\n")
+    if not data.startswith(b"ply\n") or end < 0:
+        raise ValueError(f"read_ply: {path} is not a PLY file (no 'ply' magic or no end_header)")
+    lines = data[:end].decode("ascii", "replace").split("\n")[1:-1]
+    lines = [" ".join(l.split()) for l in lines if l and not l.startswith(("comment", "obj_info"))]
+    body = data[end + len(b"end_header\n"):]
+
+    def expect(got, want):
+        if got != want:
+            raise ValueError(f"read_ply: unsupported layout: '{got}' where write_ply has '{want}'")
+
+    def count(line, element):
+        words = line.split()
+        if len(words) != 3 or words[:2] != ["element", element] or not words[2].isdigit():
+            raise ValueError(f"read_ply: unsupported layout: '{line}' where write_ply has 'element {element} <count>'")
+        return int(words[2])
+
+    if len(lines) < 7:
+        raise ValueError(f"read_ply: unsupported layout: a header of {len(lines)} lines")
+    expect(lines[0], "format binary_little_endian 1.0")
+    V = count(lines[1], "vertex")
+    T = count(lines[-2], "face")
+    expect(lines[-1], "property list uchar int vertex_indices")
+    props = lines[2:-2]
+    expect(" / ".join(props[:3]), " / ".join(_PLY_VERTEX))
+    rest = props[3:]
+    fields = [("p", "<f8", (3,))]
+    has_n = rest[:3] == _PLY_NORMAL
+    if has_n:
+        fields.append(("n", "<f4", (3,)))
+        rest = rest[3:]
+    has_c = rest[:3] == _PLY_COLOR
+    if has_c:
+        fields.append(("c", "u1", (3,)))
+        rest = rest[3:]
+    if rest:
+        raise ValueError(f"read_ply: unsupported layout: '{rest[0]}' is no vertex property write_ply writes (double x y z, float nx ny nz, uchar red green blue, in that order)")
+    vtype, ftype = np.dtype(fields), np.dtype([("n", "u1"), ("v", "<i4", (3,))])
+    want = V * vtype.itemsize + T * ftype.itemsize
+    if len(body) != want:
+        raise ValueError(f"read_ply: {len(body)} bytes after the header, {want} expected for {V} vertices and {T} triangles")
+    rec = np.frombuffer(body, dtype=vtype, count=V)
+    faces = np.frombuffer(body, dtype=ftype, count=T, offset=V * vtype.itemsize)
+    if T and (faces["n"] != 3).any():
+        raise ValueError(f"read_ply: face {int(np.flatnonzero(faces['n'] != 3)[0])} is not a triangle")
+    return {"vertices": np.array(rec["p"], dtype=np.float64).reshape(V, 3), "triangles": np.array(faces["v"], dtype=np.int32).reshape(T, 3),
+            "normals": np.array(rec["n"], dtype=np.float32).reshape(V, 3) if has_n else None, "colors": np.array(rec["c"], dtype=np.uint8).reshape(V, 3) if has_c else None}
 
 
 def save_mesh(model, path, resolution=256, threshold=10, message=None, normals=False, colors=False, min_triangles=0, keep_largest=None):

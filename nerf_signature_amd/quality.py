@@ -29,8 +29,9 @@ README = dict(iters=1000, lambda_w=0.005, lambda_i=1.0, lr=1e-2)       # README.
 ORBIT_THETA = (0.6, 1.5)      # the polar range the stage's stored poses are drawn from (bench.py's): online targets draw their cameras from the same
 
 
-def watermark_stage(scene="hotdog", device="cuda", n_poses=8, n_test_poses=10, codebook_scale=1e-4, n_rays=4096, seed=0, online_targets=False):
-    """online_targets: no clean-render pre-pass and no image store -- `poses` / `clean` are None, train() draws a new orbit camera every step
+def watermark_stage(scene="hotdog", device="cuda", n_poses=8, n_test_poses=10, codebook_scale=1e-4, n_rays=4096, seed=0, online_targets=False, opaque=False):
+    """opaque: the density head scaled so that the ball is a solid (synthetic.init_model(opaque=True)): a scene with a surface, which a mesh can stand for
+    (mesh_survival); the default is the translucent ball every other measurement uses.  online_targets: no clean-render pre-pass and no image store -- `poses` / `clean` are None, train() draws a new orbit camera every step
     (rays.OrbitRaySampler) and the step renders its own target (the content render's clean twin); the held-out views' clean images are rendered when
     test_views asks for them."""
     from .network import NeRFNetwork
@@ -40,7 +41,7 @@ def watermark_stage(scene="hotdog", device="cuda", n_poses=8, n_test_poses=10, c
     intr = (cfg["focal"], cfg["focal"], W / 2, H / 2)
     torch.manual_seed(seed)
     model = NeRFNetwork(bound=cfg["bound"], cuda_ray=True, density_scale=1, min_near=0.2, density_thresh=10, bg_radius=-1, message_dim=D, n_views=1)
-    synthetic.init_model(model, scene, codebook_scale=codebook_scale)
+    synthetic.init_model(model, scene, codebook_scale=codebook_scale, opaque=opaque)
     model.to(dev).train()
     kw = dict(dt_gamma=cfg["dt_gamma"], max_steps=1024)
     bo, bd = synthetic.block_rays(scene, dev)
@@ -295,6 +296,70 @@ def packed_report(stage, message, formats=("f16", "q8", "q4"), view=0, repeats=5
             out[name] = {"bytes": os.path.getsize(path), "verify": rel.verify(m, key), "psnr": float(metrics.psnr(full(m), truth)),
                          "render_ms": float(np.median(times)), "render_ms_all": [round(t, 3) for t in times]}
             os.remove(path)
+    return out
+
+
+def stage_key(stage, message):
+    """The pose-and-blocks SignatureKey of a synthetic stage: synthetic.block_rays' pose (orbit_pose(1.1, 0.7, radius)) and the rectangles of its blocks in the scene's
+    rows x cols grid, with the stage's decoder.  Its rays are rebuilt on the device (rg_get_rays); they must equal the stage's block rays bit for bit -- the model was
+    trained on those -- and a key whose rays differ is refused here."""
+    from . import release as rel
+    scene = stage["scene"]
+    key = rel.SignatureKey(message, stage["model"].msg_decoder.state_dict(), stage["intr"], stage["H"], stage["W"], synthetic.block_pose(scene)[None],
+                           synthetic.block_coordinates(scene), stage["render_kwargs"])
+    o, d = key.block_rays(stage["device"])
+    if not (torch.equal(o, stage["block_o"]) and torch.equal(d, stage["block_d"])):
+        raise RuntimeError("stage_key: the key's block rays differ from the stage's (max |difference| of the directions: "
+                           f"{float((d - stage['block_d']).abs().max()):.3g})")
+    return key
+
+
+@torch.no_grad()
+def mesh_survival(stage, message, resolutions=(128, 256, 384), colors=("normal", "view"), min_triangles=8, threshold=10, near=0.05, quantize=True, occupancy=True):
+    """Does the signature survive the export to a coloured mesh?  stage['model'] under `message` is turned into a mesh exactly as mesh.save_mesh does it -- mesh.lattice
+    over aabb_infer at each of `resolutions`, marching cubes at `threshold` (a density, or "median": the median density of the lattice's occupied nodes) with normals, vertex colours, mesh.clean(min_triangles) -- and the mesh alone is
+    verified against the stage's key (raster.verify_mesh: the key view rasterised, release.verify on its blocks).  colors: "normal" = the colour head seen against
+    the normal (save_mesh's), "view" = seen from the key camera (raster.view_directions: the best case for the signature).  quantize: colours go through the PLY's
+    bytes (mesh.quantize_colors) first; positions through float32.  occupancy: the lattice is cut to the cells the model's occupancy grid marks (mesh.occupied; density
+    -1 elsewhere) -- a render never evaluates the field outside them, and the synthetic stage's geometry IS that grid: its random density head fills the whole box, and
+    without the cut the mesh is a cube of noise around the ball the renders show.  The stage wants a surface: watermark_stage(opaque=True).  The mesh's key view is also compared with the field's own render of that view (the released
+    model's, staged, white background; metrics.ImageMetrics).
+    -> {"field": release.verify's record of the released FIELD (the yardstick), "cells": [one dict per (resolution, colouring): "resolution", "colors", "threshold", "V", "T",
+        "matches", "bit_accuracy", "p_value", "psnr_db", "ssim", "culled": (near, guard)]}.  What survives is REPORTED here and asserted nowhere."""
+    from . import mesh, raster, release as rel
+    model, dev, H, W = stage["model"], stage["device"], stage["H"], stage["W"]
+    key = stage_key(stage, message)
+    pose = torch.from_numpy(key.poses[0]).to(dev)
+    released = rel.release(model, message, copy=True)
+    r = rays.get_rays(pose[None], stage["intr"], H, W, -1)
+    truth = released.render(r["rays_o"], r["rays_d"], staged=True, bg_color=1, perturb=False, force_all_rays=True, **stage["render_kwargs"])["image"] \
+        .reshape(1, H, W, 3).clamp(0, 1)
+    out = {"field": rel.verify(released, key), "cells": []}
+    bmin, bmax = model.aabb_infer[:3], model.aabb_infer[3:]
+    for R in resolutions:
+        u = mesh.lattice(model, bmin, bmax, R, message)
+        occ = mesh.occupied(model, bmin, bmax, R) if occupancy else None
+        thr = float(threshold) if threshold != "median" else float((u[occ] if occupancy else u.reshape(-1)).median())
+        if occupancy:
+            u = torch.where(occ, u, torch.full_like(u, -1.0))
+        v, t, n = mesh.marching_cubes(u, thr, normals=True, scale=mesh.lattice_scale(bmin, bmax, R))
+        del u
+        world = mesh.world_vertices(v, bmin, bmax, R)
+        for how in colors:
+            if how not in ("normal", "view"):
+                raise ValueError(f"mesh_survival: colouring '{how}' is neither 'normal' nor 'view'")
+            rgb = mesh.vertex_colors(model, world, n, message, directions=raster.view_directions(world, pose) if how == "view" else None)
+            if quantize:
+                rgb = mesh.quantize_colors(rgb).float() / 255.0
+            cv, ct, crgb = mesh.clean(v, t, min_triangles, attributes=(rgb,))
+            cw = mesh.world_vertices(cv, bmin, bmax, R).float().contiguous()
+            record, view = raster.verify_mesh(cw, ct, crgb.contiguous(), key, near=near, details=True)
+            meter = ImageMetrics(dev)
+            meter.update(view["image"].reshape(1, H, W, 3).clamp(0, 1), truth)
+            m = meter.measure()
+            out["cells"].append({"resolution": int(R), "colors": how, "threshold": thr, "V": int(cv.shape[0]), "T": int(ct.shape[0]), "matches": record["matches"],
+                                 "bit_accuracy": record["bit_accuracy"], "p_value": record["p_value"], "psnr_db": m["psnr_db"], "ssim": m["ssim"],
+                                 "culled": view["culled"]})
     return out
 
 

@@ -97,10 +97,33 @@ def block_rays(scene, device="cpu"):
     The reference keeps the D blocks whose rendering JPEG-compresses worst, i.e. the most textured ones
     (provider_wtmk.py:146-218); the deterministic stand-in keeps the D blocks with the largest fraction of
     rays hitting the occupied ball, nearest the silhouette centre first."""
+    o, d, order = _block_order(scene)
+    cfg = SCENES[scene]
+    bh, bw = cfg["H"] // cfg["rows"], cfg["W"] // cfg["cols"]
+    bo = torch.stack([o[(k // cfg["cols"]) * bh:(k // cfg["cols"] + 1) * bh, (k % cfg["cols"]) * bw:(k % cfg["cols"] + 1) * bw] for k in order])
+    bd = torch.stack([d[(k // cfg["cols"]) * bh:(k // cfg["cols"] + 1) * bh, (k % cfg["cols"]) * bw:(k % cfg["cols"] + 1) * bw] for k in order])
+    return bo.contiguous().to(device), bd.contiguous().to(device)
+
+
+def block_pose(scene):
+    """The watermark pose of block_rays, [4,4] float32."""
+    return orbit_pose(1.1, 0.7, SCENES[scene]["radius"])
+
+
+def block_coordinates(scene):
+    """The rectangles of block_rays' D blocks in the watermark view, in its order: int64 [D,4] (row0, col0, row1, col1), the form of a key's block file."""
+    cfg = SCENES[scene]
+    bh, bw = cfg["H"] // cfg["rows"], cfg["W"] // cfg["cols"]
+    order = _block_order(scene)[2]
+    return np.array([[(k // cfg["cols"]) * bh, (k % cfg["cols"]) * bw, (k // cfg["cols"] + 1) * bh, (k % cfg["cols"] + 1) * bw] for k in order], np.int64)
+
+
+def _block_order(scene):
+    """(rays_o, rays_d [H,W,3] of the watermark view, the indices of the D chosen blocks in the scene's rows x cols grid)."""
     cfg = SCENES[scene]
     H, W, D = cfg["H"], cfg["W"], cfg["message_dim"]
     bh, bw = H // cfg["rows"], W // cfg["cols"]
-    pose = orbit_pose(1.1, 0.7, cfg["radius"])
+    pose = block_pose(scene)
     intr = (cfg["focal"], cfg["focal"], W / 2, H / 2)
     o, d = get_rays(torch.from_numpy(pose)[None], intr, H, W)
     o, d = o.view(H, W, 3), d.view(H, W, 3)
@@ -111,9 +134,7 @@ def block_rays(scene, device="cpu"):
     rr, cc = torch.meshgrid(torch.arange(cfg["rows"]), torch.arange(cfg["cols"]), indexing="ij")
     dist = ((rr + 0.5) * bh - H / 2) ** 2 + ((cc + 0.5) * bw - W / 2) ** 2
     order = sorted(range(cfg["rows"] * cfg["cols"]), key=lambda k: (-float(hit.view(-1)[k]), float(dist.view(-1)[k]), k))[:D]
-    bo = torch.stack([o[(k // cfg["cols"]) * bh:(k // cfg["cols"] + 1) * bh, (k % cfg["cols"]) * bw:(k % cfg["cols"] + 1) * bw] for k in order])
-    bd = torch.stack([d[(k // cfg["cols"]) * bh:(k // cfg["cols"] + 1) * bh, (k % cfg["cols"]) * bw:(k % cfg["cols"] + 1) * bw] for k in order])
-    return bo.contiguous().to(device), bd.contiguous().to(device)
+    return o, d, order
 
 
 def table_values(index, scale, T=1 << 19):
