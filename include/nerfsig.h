@@ -917,6 +917,52 @@ int rs_raster(const int32_t *triangles, uint32_t T, uint32_t V, uint32_t H, uint
 int rs_shade(const int32_t *triangles, uint32_t T, uint32_t V, const float *colors, const float *bg, uint32_t H, uint32_t W, const void *scratch, float *image,
              float *depth, int32_t *triangle, nsig_stream_t stream);
 
+/* ------------------------------------------------------------------ procedural scenes */
+
+/*
+ * Ray-casts a small analytic scene -- spheres and axis-aligned boxes, Lambert shading, an optional checker texture -- from P pinhole cameras straight into the
+ * uint8 [P, H, W, C] image store the device samplers draw from (rg_sample_rays_u8; nerf_signature_amd/procedural.py; this project's own ground truth -- the
+ * reference has no counterpart).  The picture is a single-valued function of the arguments: one lane per pixel, nothing shared, every operation rounded on its
+ * own (the library is built with -ffp-contract=off) in the order written below, so two runs give the same bytes and tests/procedural_ref.py restates it from
+ * this text.  One launch; nothing is allocated and no device value is read on the host.
+ *
+ * Arguments.  poses [P, 4, 4] fp32 in DEVICE memory, rg_get_rays' convention (row-major camera-to-world, +z forward, x right, y down); they must be finite with
+ * a rotation in the upper-left 3 x 3 -- anything else still finishes and writes only its own pixels, but the bytes are not specified.  fx, fy, cx, cy finite,
+ * fx and fy non-zero; 1 <= H, W <= 4096; P >= 1 and P H W < 2^32.  prims_host [K, 16] fp32 in HOST memory (they travel in the launch's arguments, so they are
+ * checked before anything is launched), 0 <= K <= NSIG_PROCEDURAL_MAX_PRIMS; the 16 words of a primitive:
+ *   0 kind (0 sphere, 1 box)   1 texture (0 flat, 1 checker)   2 checker frequency f   3 unused   4-6 a = the sphere's centre c or the box's corner lo
+ *   7-9 b = the radius r in word 7 (8, 9 unused) or the box's corner hi   10-12 colour A   13-15 colour B
+ * Every word, used or not, must be finite; r > 0; lo_k <= hi_k.  light (a direction TOWARDS the light, finite, not zero), ambient in [0, 1], samples S in
+ * {1, 2, 4}, channels C in {3, 4}, bg (finite; used when C = 3).  image: uint8 [P, H, W, C] in device memory.
+ *
+ * Rays.  Sub-sample (a, b), 0 <= a, b < S, of pixel (i, j) -- column i, row j -- lies at u = (float)i + (float)(2a + 1) / (float)(2S), v = (float)j +
+ * (float)(2b + 1) / (float)(2S) (exact in fp32).  Its ray is rg_get_rays' arithmetic at that position, in fp32: x = (u - cx) / fx, y = (v - cy) / fy,
+ * nrm = sqrtf((x x + y y) + 1), (dx, dy, dz) = (x, y, 1) / nrm, d_r = (dx R_r0 + dy R_r1) + dz R_r2, o_r = pose[r][3].  At S = 1 this is rg_get_rays' ray of the
+ * pixel bit for bit.  o and d are then widened to float64 and EVERYTHING below is float64; fp32 arguments are widened where they enter; sums of three go
+ * (x + y) + z.
+ *
+ * Sphere.  oc = o - c; A = d.d; B = oc.d; Cq = oc.oc - r r; disc = B B - A Cq.  disc >= 0 or a miss.  s = sqrt(disc); t = (-B - s) / A; if not t > t_min then
+ * t = (-B + s) / A; t > t_min or a miss.  n_k = ((o_k + t d_k) - c_k) / r.
+ * Box.  tn = -inf, tf = +inf; for k = 0, 1, 2: when d_k == 0 the axis divides nothing -- a miss if o_k < lo_k or o_k > hi_k, no constraint otherwise; else
+ * t0 = (lo_k - o_k) / d_k, t1 = (hi_k - o_k) / d_k, (near, far) = (t0, t1) if d_k > 0 else (t1, t0); near > tn: tn = near and the entry axis is k; far < tf: tf = far and
+ * the exit axis is k (strict comparisons: on a tie the lower axis keeps it).  tn <= tf and tf > t_min or a miss.  tn > t_min: t = tn on the entry axis; else (the
+ * camera is inside) t = tf on the exit axis.  n = -sign(d_k) e_k of that axis k: the face as the camera sees it.
+ * t_min = NSIG_PROCEDURAL_T_MIN.  The primitive with the smallest t wins the sub-sample; equal t goes to the lower index; none: a miss.
+ *
+ * Shading.  p_k = o_k + t d_k.  albedo = colour A; with the checker texture colour B where (int64)floor(f p_0) + (int64)floor(f p_1) + (int64)floor(f p_2) is odd.
+ * len = sqrt(light.light), L = light / len; shade = ambient + (1 - ambient) max(0, n.L); colour_c = albedo_c shade.
+ * Pixel.  Over the sub-samples with b the outer and a the inner loop: sum_c = sum_c + colour_c (from 0), hits counted.  alpha = hits / (S S); rgb_c = sum_c / hits, or 0
+ * without a hit (STRAIGHT alpha: the colour of what was hit, as the Blender PNGs store it).  clamp(x) = min(1, max(0, x)); rint rounds half to even.
+ *   C = 4: bytes rint(255 clamp(rgb_c)), c = 0, 1, 2, then rint(255 alpha).      C = 3: bytes rint(255 clamp(rgb_c alpha + bg_c (1 - alpha))).
+ * No shadows, no specular term, no rotated boxes.
+ */
+#define NSIG_PROCEDURAL_MAX_PRIMS 16u
+#define NSIG_PROCEDURAL_PRIM_WORDS 16u
+#define NSIG_PROCEDURAL_T_MIN 1e-4
+int ps_render_u8(const float *poses, uint32_t P, float fx, float fy, float cx, float cy, uint32_t H, uint32_t W, const float *prims_host, uint32_t K,
+                 float light_x, float light_y, float light_z, float ambient, uint32_t samples, uint32_t channels, float bg_r, float bg_g, float bg_b,
+                 uint8_t *image, nsig_stream_t stream);
+
 /* ------------------------------------------------------------------ image metrics */
 
 /*

@@ -301,12 +301,15 @@ def packed_report(stage, message, formats=("f16", "q8", "q4"), view=0, repeats=5
 
 def stage_key(stage, message):
     """The pose-and-blocks SignatureKey of a synthetic stage: synthetic.block_rays' pose (orbit_pose(1.1, 0.7, radius)) and the rectangles of its blocks in the scene's
-    rows x cols grid, with the stage's decoder.  Its rays are rebuilt on the device (rg_get_rays); they must equal the stage's block rays bit for bit -- the model was
+    rows x cols grid, with the stage's decoder; a scene's stage (scene_stage) names its own pose and rectangles in "key_pose" / "block_coordinates".  Its rays are rebuilt on the device (rg_get_rays); they must equal the stage's block rays bit for bit -- the model was
     trained on those -- and a key whose rays differ is refused here."""
     from . import release as rel
-    scene = stage["scene"]
-    key = rel.SignatureKey(message, stage["model"].msg_decoder.state_dict(), stage["intr"], stage["H"], stage["W"], synthetic.block_pose(scene)[None],
-                           synthetic.block_coordinates(scene), stage["render_kwargs"])
+    if stage.get("key_pose") is not None and stage.get("block_coordinates") is not None:      # a scene's stage (scene_stage) carries its own key view and blocks
+        pose, coordinates = stage["key_pose"], stage["block_coordinates"]
+    else:
+        pose, coordinates = synthetic.block_pose(stage["scene"]), synthetic.block_coordinates(stage["scene"])
+    key = rel.SignatureKey(message, stage["model"].msg_decoder.state_dict(), stage["intr"], stage["H"], stage["W"], np.asarray(pose, np.float32)[None], coordinates,
+                           stage["render_kwargs"])
     o, d = key.block_rays(stage["device"])
     if not (torch.equal(o, stage["block_o"]) and torch.equal(d, stage["block_d"])):
         raise RuntimeError("stage_key: the key's block rays differ from the stage's (max |difference| of the directions: "
@@ -401,6 +404,127 @@ def test_image_metrics(stage, seed=9876, max_ray_batch=4096, views=None, psnr_me
 
 
 test_views.__test__ = test_image.__test__ = test_image_metrics.__test__ = False
+
+
+@torch.no_grad()
+def scene_stage(model, scene, D=32, rows=16, cols=16, key_view=0, n_test=2, n_rays=4096, render_kwargs=None, test_poses=None):
+    """watermark_stage for a model that was TRAINED on `scene` (a dataset.Scene: loaded from a directory, or procedural.dataset's): the same dict, built the way the
+    reference's loader builds it.  Clean store: blocks.clean_render of the scene's poses (provider_wtmk.py:408-421).  Key: pose `key_view` and the D blocks of the
+    rows x cols grid that blocks.process_image keeps of its clean render (the ones JPEG compresses worst); block_o / block_d: blocks.block_rays over rays.get_rays of
+    that pose.  test_poses: the held-out cameras (default: the scene's first n_test).  Beside watermark_stage's fields: key_pose [4,4] float32 (numpy),
+    block_coordinates int64 [D,4] (numpy) -- what stage_key builds the key from -- and scene=None."""
+    dev = scene.poses.device
+    H, W, intr = scene.H, scene.W, tuple(float(v) for v in scene.intrinsics)
+    kw = dict(dt_gamma=0.0, max_steps=1024) if render_kwargs is None else dict(render_kwargs)
+    poses = scene.poses.float().contiguous()
+    test_poses = poses[:n_test].clone() if test_poses is None else test_poses.to(dev).float().contiguous()
+    model.train()
+    clean = blocks.clean_render(model, poses, intr, H, W, kw, max_ray_batch=H * W).reshape(poses.shape[0], H * W, 3).clamp_(0, 1).contiguous()
+    clean_test = blocks.clean_render(model, test_poses, intr, H, W, kw, max_ray_batch=H * W).reshape(test_poses.shape[0], H, W, 3).clamp_(0, 1).contiguous()
+    coordinates, bh, bw = blocks.process_image(clean[key_view].reshape(1, H, W, 3), rows, cols, D)
+    if coordinates.shape[0] != D:
+        raise ValueError(f"scene_stage: a {rows} x {cols} grid has {rows * cols} blocks, fewer than the {D} bits of the message")
+    r = rays.get_rays(poses[key_view:key_view + 1], intr, H, W, -1)
+    bo, bd = blocks.block_rays(r["rays_o"].reshape(1, H, W, 3), r["rays_d"].reshape(1, H, W, 3), coordinates)
+    return dict(model=model, scene=None, device=dev, D=D, H=H, W=W, intr=intr, render_kwargs=kw, block_o=bo, block_d=bd, poses=poses, clean=clean,
+                test_poses=test_poses, clean_test=clean_test, n_rays=n_rays, key_pose=poses[key_view].cpu().numpy(),
+                block_coordinates=coordinates.cpu().numpy().astype(np.int64))
+
+
+def _constant_image_psnr(truth):
+    """PSNR [dB] of the best constant-colour picture of these views: the per-channel mean of `truth` [B,H,W,3] (values in [0, 1]) against it."""
+    mean = truth.mean(dim=(0, 1, 2), keepdim=True)
+    return float(-10.0 * torch.log10(((truth - mean) ** 2).mean()))
+
+
+def sign_scene(scene, message, bound=1.0, stage1_steps=1024, stage2_steps=README["iters"], ema_decay=0.95, seed=0, workdir=None, held_out=None, rows=16, cols=16,
+               key_view=0, n_rays=4096, lr=README["lr"], n_messages=50):
+    """From a dataset.Scene to a released, signed, verified model -- both stages in one run:
+      stage 1   a fresh stage1.CleanNeRFNetwork, mark_untrained_grid over the scene's cameras, stage1.GraphedCleanLoop over scene.sampler(n_rays) (RGBA when the
+                store is: a random background per ray), the grid refreshed on the device every 16 steps, the moving average of the weights on;
+      handover  under ema_weights(): checkpoint.save_checkpoint to <workdir>/stage1.pth (workdir=None: a temporary directory, removed), and the held-out views
+                (held_out: a dataset.Scene with the same intrinsics; None: the scene's first two training views, record["held_out"] False) scored;
+      stage 2   a fresh watermark NeRFNetwork of D = len(message) bits, checkpoint.load_checkpoint(model_only=True), mark_untrained_grid, scene_stage,
+                train(stage, stage2_steps), release.release under `message`, stage_key (poses and blocks), release.verify.
+    -> {"released", "key", "stage", "record", "clean"}; clean: {"model": the stage-1 model (its trained weights), "ema": copies of what was checkpointed, in the order
+    of model.trainable(), "missing" / "unexpected": load_checkpoint's}.  record: stage1 {psnr_db, ssim, constant_psnr_db, steps, ms_per_step, samples_per_ray (the
+    march's mean over the last 16 steps: the grid stage 2 marches), overflowed, recaptures}, stage2 {steps, ms_per_step, bit_acc_before_training, test_bitacc,
+    psnr_db / ssim of the watermarked against the clean held-out views, overflowed}, verify, phases_s (wall seconds of each phase), overflowed (either loop)."""
+    import os
+    import tempfile
+    from . import checkpoint, release as rel, stage1
+    from .network import NeRFNetwork
+    dev = scene.poses.device
+    message = torch.as_tensor(message).detach().float().reshape(-1)
+    D = int(message.numel())
+    kw = dict(dt_gamma=0.0, max_steps=1024)
+    phases, t0 = {}, time.perf_counter()
+
+    def lap(name):
+        nonlocal t0
+        torch.cuda.synchronize()
+        now = time.perf_counter()
+        phases[name], t0 = now - t0, now
+
+    # ---- stage 1
+    torch.manual_seed(seed)
+    clean = stage1.CleanNeRFNetwork(bound=bound, cuda_ray=True, density_scale=1, min_near=0.2, density_thresh=10, bg_radius=-1).to(dev).train()
+    clean.mark_untrained_grid(scene.poses, scene.intrinsics)
+    optimizer = torch.optim.Adam(clean.get_params(lr), betas=(0.9, 0.99), eps=1e-15)
+    loop = stage1.GraphedCleanLoop(clean, optimizer, kw, n_rays=n_rays, sampler=scene.sampler(n_rays, seed=seed), update_extra_interval=16, lr_lambda=lr_lambda(stage1_steps),
+                                   headroom=1.0, seed=seed, device_refresh=True, ema_decay=ema_decay)
+    loop.step()
+    lap("stage1_capture_s")
+    overflow1 = False
+    for k in range(1, stage1_steps):
+        loop.step()
+        if k % 256 == 255:
+            overflow1 = overflow1 or loop.overflowed()
+    overflow1 = overflow1 or loop.overflowed()
+    lap("stage1_train_s")
+    samples_per_ray = float(loop.count_ring[:min(16, stage1_steps), 0].float().mean()) / n_rays
+    views = scene if held_out is None else held_out
+    n_views = min(2, views.poses.shape[0]) if held_out is None else views.poses.shape[0]
+    with tempfile.TemporaryDirectory() as tmp, loop.ema_weights():
+        path = checkpoint.save_checkpoint(os.path.join(tmp if workdir is None else workdir, "stage1.pth"), clean)
+        ema = [p.detach().clone() for p in clean.trainable()]
+        meter, truths = ImageMetrics(dev), []
+        clean.eval()      # as the reference's evaluate (nerf/utils.py:874): a model left in training mode marches a view with the training march, bounded by the mean
+        for i in range(n_views):      # sample count of the last steps, and drops the rays that do not fit -- whole bands of a full view come out as background
+            pred, _, gt, _ = stage1.eval_step(clean, views.view(i), kw)
+            meter.update(pred.clamp(0, 1), gt)
+            truths.append(gt)
+        clean.train()
+        m1 = meter.measure()
+        lap("handover_s")
+        # ---- stage 2
+        torch.manual_seed(seed)
+        model = NeRFNetwork(bound=bound, cuda_ray=True, density_scale=1, min_near=0.2, density_thresh=10, bg_radius=-1, message_dim=D, n_views=1)
+        missing, unexpected, _ = checkpoint.load_checkpoint(path, model, model_only=True, map_location="cpu")
+    loop.close()
+    model.to(dev).train()
+    model.mark_untrained_grid(scene.poses, scene.intrinsics)
+    stage = scene_stage(model, scene, D=D, rows=rows, cols=cols, key_view=key_view, n_rays=n_rays, render_kwargs=kw, test_poses=views.poses[:n_views])
+    lap("stage2_prepass_s")
+    before = test_bitacc(stage, n_messages)[0]
+    rec = train(stage, stage2_steps)
+    lap("stage2_train_s")
+    after = test_bitacc(stage, n_messages)
+    marked = test_image_metrics(stage)
+    released = rel.release(model, message.to(dev), copy=True)
+    key = stage_key(stage, message)
+    verdict = rel.verify(released, key)
+    lap("evaluate_release_verify_s")
+    record = {"stage1": {"steps": stage1_steps, "psnr_db": m1["psnr_db"], "ssim": m1["ssim"], "constant_psnr_db": _constant_image_psnr(torch.cat(truths, dim=0)),
+                         "views": n_views, "held_out": held_out is not None, "ms_per_step": phases["stage1_train_s"] / max(stage1_steps - 1, 1) * 1e3,
+                         "samples_per_ray": samples_per_ray, "overflowed": bool(overflow1), "recaptures": loop.recaptures},
+              "stage2": {"steps": rec["steps"], "ms_per_step": rec["ms_per_step"], "capture_s": rec["prepare_s"], "bit_acc_before_training": before, "test_bitacc": after[0],
+                         "wrong_bits_mean": after[1], "wrong_bits_worst_message": after[2], "psnr_db": marked["psnr_db"], "ssim": marked["ssim"],
+                         "overflowed": bool(rec["overflowed"]), "recaptures": rec["recaptures"], "loss_image": rec["loss_image"], "loss_watermark": rec["loss_watermark"]},
+              "verify": verdict, "phases_s": phases, "overflowed": bool(overflow1 or rec["overflowed"]), "D": D, "image": [scene.H, scene.W],
+              "train_views": int(scene.poses.shape[0]), "blocks": [rows, cols]}
+    return {"released": released, "key": key, "stage": stage, "record": record,
+            "clean": {"model": clean, "ema": ema, "missing": missing, "unexpected": unexpected}}
 
 
 LAST_STAGE = None      # (tools/converge.py's two-rank run compares the ranks' final models)
