@@ -316,6 +316,19 @@ int hg_scatter_binned(const float *rec, uint32_t M, float *G, void *scratch, nsi
 size_t hg_scatter_plan_bytes(uint32_t M);
 int hg_scatter_plan(const float *xyzs, uint32_t M, float bound, void *plan, nsig_stream_t stream);
 int hg_scatter_planned(const void *plan, uint32_t M, float *G, nsig_stream_t stream);
+/* The same three calls for buffers with more rows than points (a captured step sizes them with headroom; the march zero-fills the tail): M_capacity sizes the
+ * launches and addresses `plan` (hg_scatter_plan_bytes(M_capacity)); the kernels stop at min(M_capacity, *rows_dev), a device word (hg_scatter_plan_rows,
+ * field_bwd_planned_rows; the owners take their counts from the plan).  G is, bit for bit, what the three calls above give at M = *rows_dev on the first
+ * *rows_dev rows -- the tail rows get no queue entries, so neither the owners' time nor a slice's fixed-point scale depends on the capacity.  *rows_dev == 0: G
+ * is left as it is.
+ * owners: a launch of at most NSIG_SINGLE_OWNER_MAX_POINTS points (hg_scatter_planned: M, here: M_capacity) runs ONE owner per slice, which converts its
+ * fixed-point sums and adds them to G itself -- one float add per non-zero element, the bits of the four replicas and their merge launch, without the slabs and
+ * without that launch; larger ones keep the replicas.  NSIG_OWNERS_BY_SIZE says so; the other two values name a form (parity tests, the sweep behind the limit). */
+#define NSIG_OWNERS_BY_SIZE 0
+#define NSIG_OWNERS_SINGLE 1
+#define NSIG_OWNERS_REPLICAS 2
+int hg_scatter_plan_rows(const float *xyzs, uint32_t M_capacity, const uint32_t *rows_dev, float bound, void *plan, nsig_stream_t stream);
+int hg_scatter_planned_rows(const void *plan, uint32_t M_capacity, const uint32_t *rows_dev, float *G, int owners, nsig_stream_t stream);
 
 /* grads[i][t] (+)= G[t] for the D selected tables; grads_host: host array of D device pointers. */
 int hg_fanout_grad(const float *G, float *const *grads_host, uint32_t D, int accumulate, nsig_stream_t stream);
@@ -502,6 +515,11 @@ int field_bwd(const float *xyzs, uint32_t M, float bound, const float *grad_sigm
 int field_bwd_planned(const float *xyzs, uint32_t M, float bound, const float *grad_sigmas, const float *grad_rgbs,
                       const float *sigmas, const float *rgbs, const uint32_t *masks, const void *packed, void *plan,
                       nsig_stream_t stream);
+/* field_bwd_planned over the first min(M_capacity, *rows_dev) rows (see hg_scatter_plan_rows, which prepared `plan` with the same two values): tiles beyond
+ * them are never loaded, the last partial tile's tail lanes are dead. */
+int field_bwd_planned_rows(const float *xyzs, uint32_t M_capacity, const uint32_t *rows_dev, float bound, const float *grad_sigmas, const float *grad_rgbs,
+                           const float *sigmas, const float *rgbs, const uint32_t *masks, const void *packed, void *plan,
+                           nsig_stream_t stream);
 
 /*
  * torch.optim.Adam (betas, eps; no weight decay / amsgrad) in its capturable form over n dense fp32 tensors in one pass:

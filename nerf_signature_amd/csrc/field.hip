@@ -817,8 +817,14 @@ __device__ inline void field_bwd_pipelined(const char *lds, int lane, const floa
 template <typename P>
 __global__ void __launch_bounds__(256) k_field_bwd_train(const float *__restrict__ xyzs, uint32_t M, float bound, const float *__restrict__ g_sigma,
                                                          const float *__restrict__ g_rgb, const float *__restrict__ sigmas, const float *__restrict__ rgbs,
-                                                         const uint32_t *__restrict__ masks, const char *__restrict__ packed, ScatterPlan plan) {
+                                                         const uint32_t *__restrict__ masks, const char *__restrict__ packed, ScatterPlan plan,
+                                                         const uint32_t *__restrict__ rows_dev = nullptr) {
     extern __shared__ __attribute__((aligned(16))) char lds[];
+    if (rows_dev != nullptr) {      // (field_bwd_planned_rows: as k_field_fwd_train -- M is the capacity the launch and the plan were sized for)
+        const uint32_t r = *rows_dev;
+        if (r == 0) return;
+        M = min(M, r);
+    }
     stage_weights(lds, packed + P::kBwdOffset, (int)P::kBwdLds);
     field_bwd_pipelined<P>(lds, threadIdx.x & 63, xyzs, M, bound, g_sigma, g_rgb, sigmas, rgbs, masks, plan);
 }
@@ -1034,22 +1040,34 @@ NSIG_EXPORT int field_bwd(const float *xyzs, uint32_t M, float bound, const floa
 
 // field_bwd with the codebook scatter's queue as its output: `plan` was prepared by hg_scatter_plan from the same xyzs; follow with
 // hg_scatter_planned.  (reference: the autograd backward of network_wtmk_tcnn.py:97-124 down to the index_add of hash_encoding.py)
-NSIG_EXPORT int field_bwd_planned(const float *xyzs, uint32_t M, float bound, const float *grad_sigmas, const float *grad_rgbs, const float *sigmas,
-                                  const float *rgbs, const uint32_t *masks, const void *packed, void *plan, nsig_stream_t stream) {
+// rows_dev (field_bwd_planned_rows): M sizes the launch and addresses the plan, the kernels stop at min(M, *rows_dev)
+static int bwd_planned_launch(const char *who, const float *xyzs, uint32_t M, const uint32_t *rows_dev, float bound, const float *grad_sigmas, const float *grad_rgbs,
+                              const float *sigmas, const float *rgbs, const uint32_t *masks, const void *packed, void *plan, nsig_stream_t stream) {
     if (M == 0) return NSIG_OK;
-    NSIG_REQUIRE(xyzs && grad_sigmas && grad_rgbs && sigmas && rgbs && masks && packed && plan, "field_bwd_planned: null pointer");
-    NSIG_REQUIRE(bound > 0.0f && aligned16(plan) && M < (1u << 28), "field_bwd_planned: bound must be positive, plan 16-byte aligned, M < 2^28");
+    NSIG_REQUIRE(xyzs && grad_sigmas && grad_rgbs && sigmas && rgbs && masks && packed && plan, "%s: null pointer", who);
+    NSIG_REQUIRE(bound > 0.0f && aligned16(plan) && M < (1u << 28), "%s: bound must be positive, plan 16-byte aligned, M < 2^28", who);
     if (mlp_precision() == 1 && bwd_pipelined())
         k_field_bwd_train<F16><<<field_grid(M), 256, F16::kBwdLds, as_stream(stream)>>>(xyzs, M, bound, grad_sigmas, grad_rgbs, sigmas, rgbs, masks,
-                                                                                reinterpret_cast<const char *>(packed), scatter_plan_view(plan, M));
+                                                                                reinterpret_cast<const char *>(packed), scatter_plan_view(plan, M), rows_dev);
     else
         with_mlp([&](auto tag) {
             using P = decltype(tag);
             k_field_bwd<P, false><<<field_grid(M), 256, P::kBwdLds, as_stream(stream)>>>(xyzs, M, bound, 1.0f / kCodebookResolution, grad_sigmas, grad_rgbs, sigmas, rgbs, masks,
                                                                                  reinterpret_cast<const char *>(packed), nullptr, nullptr, nullptr, GradTrace{}, 0,
-                                                                                 scatter_plan_view(plan, M));
+                                                                                 scatter_plan_view(plan, M), rows_dev);
         });
-    return check_launch("field_bwd_planned");
+    return check_launch(who);
+}
+
+NSIG_EXPORT int field_bwd_planned(const float *xyzs, uint32_t M, float bound, const float *grad_sigmas, const float *grad_rgbs, const float *sigmas,
+                                  const float *rgbs, const uint32_t *masks, const void *packed, void *plan, nsig_stream_t stream) {
+    return bwd_planned_launch("field_bwd_planned", xyzs, M, nullptr, bound, grad_sigmas, grad_rgbs, sigmas, rgbs, masks, packed, plan, stream);
+}
+
+NSIG_EXPORT int field_bwd_planned_rows(const float *xyzs, uint32_t M_capacity, const uint32_t *rows_dev, float bound, const float *grad_sigmas, const float *grad_rgbs,
+                                       const float *sigmas, const float *rgbs, const uint32_t *masks, const void *packed, void *plan, nsig_stream_t stream) {
+    NSIG_REQUIRE(rows_dev != nullptr, "field_bwd_planned_rows: null row count");
+    return bwd_planned_launch("field_bwd_planned_rows", xyzs, M_capacity, rows_dev, bound, grad_sigmas, grad_rgbs, sigmas, rgbs, masks, packed, plan, stream);
 }
 
 // ----------------------------------------------------------------------------- stage-1 (clean model) training entry points

@@ -116,6 +116,9 @@ __device__ inline float corner_weight(const Corner8 &c, int k, float g) {
 #ifndef NSIG_BIN_REPLICAS      // (diagnostic builds sweep it: tools/build_variant.sh rep2 -DNSIG_BIN_REPLICAS=2)
 #define NSIG_BIN_REPLICAS 4
 #endif
+#ifndef NSIG_SINGLE_OWNER_MAX_POINTS      // hg_scatter_planned: up to this many points one owner per slice, no merge launch (include/nerfsig.h NSIG_OWNERS_*)
+#define NSIG_SINGLE_OWNER_MAX_POINTS 400000
+#endif
 constexpr uint32_t kBinThreads = 1024, kBinSlices = 64, kBinRows = NSIG_TABLE_ROWS / kBinSlices, kBinReplicas = NSIG_BIN_REPLICAS;
 constexpr uint32_t kBinGrid = 256;   // workgroups of the binning passes (each walks chunks w, w + kBinGrid, ...)
 

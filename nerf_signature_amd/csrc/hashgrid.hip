@@ -372,8 +372,12 @@ __device__ inline void point_slices(const float *__restrict__ xyzs, uint32_t m, 
     for (uint32_t q = 0; q < 4; ++q) sl[q] = pair_slice(pair_hash(iy, iz, q));
 }
 
-__global__ void __launch_bounds__(kBinThreads) k_plan_count(const float *__restrict__ xyzs, uint32_t M, float bound, BinHeader *__restrict__ hd) {
+// rows_dev (hg_scatter_plan_rows; both kernels): the point count lives on the device, M is the capacity the launch and the plan were sized for -- rows beyond
+// *rows_dev get no entries, workgroups beyond them count nothing (with *rows_dev == 0 the plan is the reset header: no entries, gmax_bits 0).
+__global__ void __launch_bounds__(kBinThreads) k_plan_count(const float *__restrict__ xyzs, uint32_t M, float bound, BinHeader *__restrict__ hd,
+                                                            const uint32_t *__restrict__ rows_dev = nullptr) {
     __shared__ uint32_t h[kBinSlices];
+    if (rows_dev != nullptr) M = min(M, *rows_dev);
     if (threadIdx.x < kBinSlices) h[threadIdx.x] = 0;
     if (blockIdx.x == 0 && threadIdx.x == 0) hd->gmax_bits = 0;   // k_field_bwd raises it (stream-ordered after the plan)
     __syncthreads();
@@ -392,8 +396,9 @@ __global__ void __launch_bounds__(kBinThreads) k_plan_count(const float *__restr
 // used to sit between the two passes (k_bin_scan: 2-16 us in a chain of small launches) is gone.  Workgroup 0 stores the slice totals
 // the owners read.  Same queue order as count -> scan -> dest.
 __global__ void __launch_bounds__(kBinThreads) k_plan_dest(const float *__restrict__ xyzs, uint32_t M, float bound, BinHeader *__restrict__ hd,
-                                                           uint4 *__restrict__ dest) {
+                                                           uint4 *__restrict__ dest, const uint32_t *__restrict__ rows_dev = nullptr) {
     __shared__ uint32_t h[kBinSlices], running[kBinSlices], seg_tot[16][kBinSlices], seg_before[16][kBinSlices];
+    if (rows_dev != nullptr) M = min(M, *rows_dev);      // (one value for the launch: the trip count below stays uniform per workgroup)
     {
         static_assert(kBinThreads == 16 * kBinSlices && kBinGrid == 256, "16 segments of 16 workgroups, one thread per (segment, slice)");
         const uint32_t s = threadIdx.x & (kBinSlices - 1), g = threadIdx.x >> 6, n_wg = gridDim.x;
@@ -796,11 +801,12 @@ struct OwnerAdam {
 // launch gap.)
 // The fixed-point scale leaves room for as many maximal contributions as the slice has entries (fixed_scale): at level 0 of stage 1 a million samples
 // share 4913 rows, and a codebook launch may put all of its points on one vertex.
+// add_to_g (replicas == 1; hg_scatter_planned on a small launch): the single owner ADDS its rows to G as the merge would have -- see the end of the kernel.
 // set_max (optional): [sets][n_set_max] partial maxima of |contribution| (float bit patterns) whose maximum replaces the header's gmax_bits.
 __global__ void __launch_bounds__(1024) k_scatter_binned(const BinHeader *__restrict__ hd_all, const uint4 *__restrict__ queue_all, uint32_t M,
                                                          ScatterTargets tg, uint32_t replicas,
                                                          const uint32_t *__restrict__ set_max = nullptr, uint32_t n_set_max = 0, OwnerAdam adam = OwnerAdam{},
-                                                         unsigned long long *__restrict__ slabs = nullptr) {
+                                                         unsigned long long *__restrict__ slabs = nullptr, bool add_to_g = false) {
     extern __shared__ unsigned long long acc64[];  // [kBinRows][2] fixed point
     const BinHeader *__restrict__ hd = hd_all + blockIdx.y;
     const uint4 *__restrict__ queue = queue_all + (size_t)blockIdx.y * 4 * M;
@@ -850,7 +856,7 @@ __global__ void __launch_bounds__(1024) k_scatter_binned(const BinHeader *__rest
     const int k = poisoned ? 0 : fixed_scale(gb, n);
     float *out = G + 2 * (size_t)slice * kBinRows;
     if (beg >= end && !adam.on) {      // (uniform) nothing for this owner (two of level 0's 64 slices hold no cell pair at all; a replica beyond a short slice's end -- it leaves no slab, and the merge knows): its rows are zeros, no accumulators needed
-        if (poisoned || replicas == 1) {
+        if (poisoned || (replicas == 1 && !add_to_g)) {
             const float f = poisoned ? __uint_as_float(0x7fc00000u) : 0.0f;
             for (uint32_t i4 = threadIdx.x; i4 < kBinRows / 2u; i4 += blockDim.x) *reinterpret_cast<float4 *>(out + 4u * i4) = make_float4(f, f, f, f);
         }
@@ -915,7 +921,14 @@ __global__ void __launch_bounds__(1024) k_scatter_binned(const BinHeader *__rest
         }
         return;
     }
-    if (poisoned || replicas == 1) {
+    if (add_to_g && !poisoned) {
+        // what k_scatter_merge does with the sum of a slice's slabs, done here with the one owner's accumulators: the same integer, the same conversion, one float
+        // atomic per non-zero element (consecutive lanes on consecutive words, as in the merge) -- the same bits in G, no slabs and no second launch
+        for (uint32_t i = threadIdx.x; i < 2u * kBinRows; i += blockDim.x) {
+            const long long v = (long long)acc64[i];
+            if (v != 0) atomicAdd(out + i, (float)ldexp((double)v, -k));
+        }
+    } else if (poisoned || replicas == 1) {
         for (uint32_t i4 = threadIdx.x; i4 < kBinRows / 2u; i4 += blockDim.x) {      // two rows = four sums per thread and trip: 16-byte stores (the slice is 64 KiB-aligned in G)
             float r[4];
 #pragma unroll
@@ -1276,34 +1289,66 @@ NSIG_EXPORT int hg_scatter_binned(const float *rec, uint32_t M, float *G, void *
 
 NSIG_EXPORT size_t hg_scatter_plan_bytes(uint32_t M) { return scatter_plan_bytes(M); }
 
-NSIG_EXPORT int hg_scatter_plan(const float *xyzs, uint32_t M, float bound, void *plan, nsig_stream_t stream) {
+// M sizes the launch and addresses the plan; rows_dev (hg_scatter_plan_rows): the kernels stop at min(M, *rows_dev)
+static int scatter_plan_launch(const char *who, const float *xyzs, uint32_t M, const uint32_t *rows_dev, float bound, void *plan, nsig_stream_t stream) {
     if (M == 0) return NSIG_OK;
-    NSIG_REQUIRE(xyzs && plan, "hg_scatter_plan: null pointer");
-    NSIG_REQUIRE(aligned16(plan) && M < (1u << 28) && bound > 0.0f, "hg_scatter_plan: plan must be 16-byte aligned, M < 2^28, bound > 0");
+    NSIG_REQUIRE(xyzs && plan, "%s: null pointer", who);
+    NSIG_REQUIRE(aligned16(plan) && M < (1u << 28) && bound > 0.0f, "%s: plan must be 16-byte aligned, M < 2^28, bound > 0", who);
     const ScatterPlan pl = scatter_plan_view(plan, M);
     hipStream_t st = as_stream(stream);
     const uint32_t blocks = ceil_div(M, kBinThreads) < kBinGrid ? ceil_div(M, kBinThreads) : kBinGrid;
-    k_plan_count<<<blocks, kBinThreads, 0, st>>>(xyzs, M, bound, pl.hd);
-    k_plan_dest<<<blocks, kBinThreads, 0, st>>>(xyzs, M, bound, pl.hd, pl.dest);
-    return check_launch("hg_scatter_plan");
+    k_plan_count<<<blocks, kBinThreads, 0, st>>>(xyzs, M, bound, pl.hd, rows_dev);
+    k_plan_dest<<<blocks, kBinThreads, 0, st>>>(xyzs, M, bound, pl.hd, pl.dest, rows_dev);
+    return check_launch(who);
 }
 
-NSIG_EXPORT int hg_scatter_planned(const void *plan, uint32_t M, float *G, nsig_stream_t stream) {
+NSIG_EXPORT int hg_scatter_plan(const float *xyzs, uint32_t M, float bound, void *plan, nsig_stream_t stream) {
+    return scatter_plan_launch("hg_scatter_plan", xyzs, M, nullptr, bound, plan, stream);
+}
+
+NSIG_EXPORT int hg_scatter_plan_rows(const float *xyzs, uint32_t M_capacity, const uint32_t *rows_dev, float bound, void *plan, nsig_stream_t stream) {
+    NSIG_REQUIRE(rows_dev != nullptr, "hg_scatter_plan_rows: null row count");
+    return scatter_plan_launch("hg_scatter_plan_rows", xyzs, M_capacity, rows_dev, bound, plan, stream);
+}
+
+// Launches of at most this many points (capacity: 4 entries each) get ONE owner per slice, which adds its rows to G itself (k_scatter_binned's add_to_g): no
+// slabs, no merge launch.  Same bits as the replicas + merge.  Same-box sweep of the two forms over the launch size (tools/scatter_owner_sweep.py, us per call,
+// single | replicas + merge): 66 k points 10.9 | 20.4, 115 k 12.4 | 20.7, 144 k 13.3 | 20.9, 200 k 15.0 | 21.9, 288 k 17.6 | 23.1, 400 k 21.0 | 24.2,
+// 576 k 26.0 | 26.3, 800 k 32.7 | 28.5, 1.29 M 46.8 | 34.4 (profiles/scatter_rows_owner_sweep.txt): the last size at which one owner is clearly ahead.
+constexpr uint32_t kSingleOwnerMaxPoints = NSIG_SINGLE_OWNER_MAX_POINTS;
+
+// owners: NSIG_OWNERS_BY_SIZE, or one of the two forms by name (the parity tests and the sweep run both on one queue)
+static int scatter_planned_launch(const char *who, const void *plan, uint32_t M, float *G, int owners, nsig_stream_t stream) {
     if (M == 0) return NSIG_OK;
-    NSIG_REQUIRE(plan && G, "hg_scatter_planned: null pointer");
-    NSIG_REQUIRE(aligned16(plan) && M < (1u << 28), "hg_scatter_planned: plan must be 16-byte aligned and M < 2^28");
-    if (int e = reserve_owner_lds("hg_scatter_planned")) return e;
+    NSIG_REQUIRE(plan && G, "%s: null pointer", who);
+    NSIG_REQUIRE(aligned16(plan) && M < (1u << 28), "%s: plan must be 16-byte aligned and M < 2^28", who);
+    NSIG_REQUIRE(owners == NSIG_OWNERS_BY_SIZE || owners == NSIG_OWNERS_SINGLE || owners == NSIG_OWNERS_REPLICAS, "%s: owners=%d is none of NSIG_OWNERS_*", who, owners);
+    if (int e = reserve_owner_lds(who)) return e;
     const ScatterPlan pl = scatter_plan_view(const_cast<void *>(plan), M);
     ScatterTargets tg{};
     tg.g[0] = G;
-    if (int e = owner_targets_aligned(tg, 1, "hg_scatter_planned")) return e;
+    if (int e = owner_targets_aligned(tg, 1, who)) return e;
+    hipStream_t st = as_stream(stream);
+    const size_t lds = (size_t)kBinRows * 2 * sizeof(unsigned long long);
+    if (owners == NSIG_OWNERS_SINGLE || (owners == NSIG_OWNERS_BY_SIZE && M <= kSingleOwnerMaxPoints)) {
+        k_scatter_binned<<<dim3(kBinSlices, 1), 1024, lds, st>>>(pl.hd, pl.queue, M, tg, 1u, nullptr, 0u, OwnerAdam{}, nullptr, true);
+        return check_launch(who);
+    }
     // replicas: 1 -> 63 us, 2 -> 40, 4 -> 32, 8 -> 43 on 5.2 M entries (more owners stream less each, but merge with more float atomics)
     // (with the owners' pipelined queue walk, round 5: 2 -> 31.0, 3 -> 28.5, 4 -> 28.9, 6 -> 37.4, 8 -> 43.2 us; the step the same for 2..4)
-    k_scatter_binned<<<dim3(kBinSlices * kBinReplicas, 1), 1024, (size_t)kBinRows * 2 * sizeof(unsigned long long), as_stream(stream)>>>(pl.hd, pl.queue, M, tg,
-                                                                                                                                           kBinReplicas, nullptr, 0u,
-                                                                                                                                           OwnerAdam{}, pl.slabs);
-    k_scatter_merge<<<dim3(kBinSlices * kMergeParts, 1), kMergeThreads, 0, as_stream(stream)>>>(pl.hd, tg, kBinReplicas, pl.slabs);
-    return check_launch("hg_scatter_planned");
+    k_scatter_binned<<<dim3(kBinSlices * kBinReplicas, 1), 1024, lds, st>>>(pl.hd, pl.queue, M, tg, kBinReplicas, nullptr, 0u, OwnerAdam{}, pl.slabs);
+    k_scatter_merge<<<dim3(kBinSlices * kMergeParts, 1), kMergeThreads, 0, st>>>(pl.hd, tg, kBinReplicas, pl.slabs);
+    return check_launch(who);
+}
+
+NSIG_EXPORT int hg_scatter_planned(const void *plan, uint32_t M, float *G, nsig_stream_t stream) {
+    return scatter_planned_launch("hg_scatter_planned", plan, M, G, NSIG_OWNERS_BY_SIZE, stream);
+}
+
+// (the owners take their entry counts from the header hg_scatter_plan_rows left: nothing in them reads the row count)
+NSIG_EXPORT int hg_scatter_planned_rows(const void *plan, uint32_t M_capacity, const uint32_t *rows_dev, float *G, int owners, nsig_stream_t stream) {
+    NSIG_REQUIRE(rows_dev != nullptr, "hg_scatter_planned_rows: null row count");
+    return scatter_planned_launch("hg_scatter_planned_rows", plan, M_capacity, G, owners, stream);
 }
 
 NSIG_EXPORT size_t hg_scatter_levels_scratch_bytes(uint32_t M) {

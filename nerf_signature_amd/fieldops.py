@@ -499,10 +499,12 @@ def forget_plan_events():
 
 
 class ScatterPlan:
-    """Counts, offsets and per-point queue destinations of the slice-binned codebook scatter -> hg_scatter_plan."""
+    """Counts, offsets and per-point queue destinations of the slice-binned codebook scatter -> hg_scatter_plan.
+    rows_dev: a device count (int32) of the rows that hold points, for buffers a captured loop sized with headroom -> hg_scatter_plan_rows; the backward that
+    consumes the plan (field_backward_planned) then stops at that count as well."""
 
-    def __init__(self, xyzs, bound):
-        self.M, self.xyzs, self.bound = xyzs.shape[0], xyzs, float(bound)
+    def __init__(self, xyzs, bound, rows_dev=None):
+        self.M, self.xyzs, self.bound, self.rows_dev = xyzs.shape[0], xyzs, float(bound), rows_dev
         self.buf = torch.empty(int(nv.fn("hg_scatter_plan_bytes")(self.M)), dtype=torch.uint8, device=xyzs.device)
         self.stream, self.ready, self.launched = _PLAN_STREAM, None, False
         self.src_ready = None
@@ -523,16 +525,22 @@ class ScatterPlan:
                 self.src_ready.record()
             _PENDING_PLANS.append(self)
 
+    def _enqueue(self, stream):
+        if self.rows_dev is None:
+            nv.call("hg_scatter_plan", nv.ptr(self.xyzs), self.M, self.bound, nv.ptr(self.buf), stream)
+        else:
+            nv.call("hg_scatter_plan_rows", nv.ptr(self.xyzs), self.M, nv.ptr(self.rows_dev), self.bound, nv.ptr(self.buf), stream)
+
     def launch(self):
         if self.launched:
             return
         self.launched = True
         if self.stream is None:
-            nv.call("hg_scatter_plan", nv.ptr(self.xyzs), self.M, self.bound, nv.ptr(self.buf), nv.stream())
+            self._enqueue(nv.stream())
         else:
             if self.src_ready is not None:
                 self.stream.wait_event(self.src_ready)
-            nv.call("hg_scatter_plan", nv.ptr(self.xyzs), self.M, self.bound, nv.ptr(self.buf), self.stream.cuda_stream)
+            self._enqueue(self.stream.cuda_stream)
             self.xyzs.record_stream(self.stream)
             self.buf.record_stream(self.stream)
             self.ready = torch.cuda.Event()     # the consumer waits for the plan, not for whatever else that stream runs later
@@ -609,12 +617,26 @@ class FixedPoints:
             self.refresh(xyzs, base_tables)
 
 
-def field_backward_planned(xyzs, bound, g_sigma, g_rgb, sigmas, rgbs, masks, packed, plan, G):
-    """MLP input gradients written straight into the planned queue, then the slice owners -> field_bwd_planned, hg_scatter_planned."""
+OWNERS = {None: 0, "single": 1, "replicas": 2}      # include/nerfsig.h NSIG_OWNERS_*
+
+
+def field_backward_planned(xyzs, bound, g_sigma, g_rgb, sigmas, rgbs, masks, packed, plan, G, owners=None):
+    """MLP input gradients written straight into the planned queue, then the slice owners -> field_bwd_planned, hg_scatter_planned; for a plan made with a
+    device row count (ScatterPlan(rows_dev=...)) -> field_bwd_planned_rows, hg_scatter_planned_rows: nothing is computed for the rows behind it.
+    owners ("single" | "replicas", plans with a row count only): the owners' form by name instead of by launch size -- the same bits either way."""
     plan.join()
-    nv.call("field_bwd_planned", nv.ptr(xyzs), plan.M, float(bound), nv.ptr(g_sigma.contiguous().float()), nv.ptr(g_rgb.contiguous().float()),
-            nv.ptr(sigmas), nv.ptr(rgbs), nv.ptr(masks), nv.ptr(packed), nv.ptr(plan.buf), nv.stream())
-    nv.call("hg_scatter_planned", nv.ptr(plan.buf), plan.M, nv.ptr(G), nv.stream())
+    rows_dev = getattr(plan, "rows_dev", None)
+    gs, gc = g_sigma.contiguous().float(), g_rgb.contiguous().float()
+    if rows_dev is None:
+        if owners is not None:
+            raise ValueError("field_backward_planned(owners=...) needs a plan with a device row count")
+        nv.call("field_bwd_planned", nv.ptr(xyzs), plan.M, float(bound), nv.ptr(gs), nv.ptr(gc), nv.ptr(sigmas), nv.ptr(rgbs), nv.ptr(masks), nv.ptr(packed), nv.ptr(plan.buf),
+                nv.stream())
+        nv.call("hg_scatter_planned", nv.ptr(plan.buf), plan.M, nv.ptr(G), nv.stream())
+    else:
+        nv.call("field_bwd_planned_rows", nv.ptr(xyzs), plan.M, nv.ptr(rows_dev), float(bound), nv.ptr(gs), nv.ptr(gc), nv.ptr(sigmas), nv.ptr(rgbs), nv.ptr(masks),
+                nv.ptr(packed), nv.ptr(plan.buf), nv.stream())
+        nv.call("hg_scatter_planned_rows", nv.ptr(plan.buf), plan.M, nv.ptr(rows_dev), nv.ptr(G), OWNERS[owners], nv.stream())
     return G
 
 
@@ -732,11 +754,13 @@ class _FieldFunction(Function):
     table -- backward returns the fan-out of the shared gradient for each (unselected tables are not inputs, so their grad stays None exactly as in the
     reference); with a sink the gradient accumulates there, autograd sees None, and ONE selected table is passed only so that the node is recorded.
     twin: returns (sigma, rgb, sigma_clean, rgb_clean) -- the clean field at the same points from the same launch (field_forward(twin=True)), marked
-    non-differentiable: it depends on nothing that trains."""
+    non-differentiable: it depends on nothing that trains.
+    rows_dev: a device count of the rows of `xyzs` that hold points (buffers sized with headroom; the rest is the march's zero fill), or None: the planned
+    backward and its scatter then stop there (ScatterPlan(rows_dev=...)); the forward pass runs over every row as before."""
 
     @staticmethod
     @_fwd32
-    def forward(ctx, xyzs, dirs, bound, packed, S, sink, tabs, fixed, twin, *diff):
+    def forward(ctx, xyzs, dirs, bound, packed, S, sink, tabs, fixed, twin, rows_dev, *diff):
         base, sel = tabs.base, tabs.sel
         n_sel = len(sel)
         need_grad = n_sel > 0 and len(diff) > 0
@@ -745,7 +769,7 @@ class _FieldFunction(Function):
             ctx.plan = fixed.plan if need_grad else None
         else:
             # before the encoder is enqueued: a plan on its own stream forks right behind the march, not behind this forward pass
-            ctx.plan = ScatterPlan(xyzs, bound) if need_grad and xyzs.shape[0] >= binned_min_points() else None
+            ctx.plan = ScatterPlan(xyzs, bound, rows_dev) if need_grad and xyzs.shape[0] >= binned_min_points() else None
         sigmas, rgbs, _, masks, *clean = field_forward(xyzs, dirs, bound, base, S, packed, want_masks=need_grad, fixed=fixed, twin=twin)
         ctx.bound, ctx.n_diff, ctx.need_grad, ctx.sink = bound, len(diff), need_grad, sink
         if need_grad:
@@ -764,7 +788,7 @@ class _FieldFunction(Function):
     @staticmethod
     @_bwd
     def backward(ctx, g_sigma, g_rgb, *g_clean):
-        head = (None,) * 9
+        head = (None,) * 10
         if not ctx.need_grad:
             return head + (None,) * ctx.n_diff
         xyzs, sigmas, rgbs, masks, packed = ctx.saved_tensors
@@ -901,10 +925,10 @@ def color_apply(dirs, geo_feat, packed, color_params):
     return _ColorFunction.apply(dirs, geo_feat, packed, color_params)
 
 
-def field_apply(xyzs, dirs, bound, packed, base_tables, selected, S=None, sink=None, fixed=None, twin=False):
+def field_apply(xyzs, dirs, bound, packed, base_tables, selected, S=None, sink=None, fixed=None, twin=False, rows_dev=None):
     """(sigma, rgb) with autograd to the selected codebook tables.  S: their pre-sum (computed here if omitted).
     fixed: the FixedPoints of exactly these points (rays that do not change between steps), or None.
-    twin: (sigma, rgb, sigma_clean, rgb_clean) -- see _FieldFunction."""
+    twin: (sigma, rgb, sigma_clean, rgb_clean) -- see _FieldFunction.  rows_dev: a device count of the rows that hold points -- see _FieldFunction."""
     if twin and not len(selected):
         raise ValueError("field_apply(twin=True) without a message: the field is already the clean one")
     if len(selected) and S is None:
@@ -916,4 +940,4 @@ def field_apply(xyzs, dirs, bound, packed, base_tables, selected, S=None, sink=N
         diff = tuple(selected) if any(t.requires_grad for t in selected) else ()
     else:           # the gradient goes to the sink: one differentiable input is enough to have the node recorded
         diff = next(((t,) for t in selected if t.requires_grad), ())
-    return _FieldFunction.apply(xyzs, dirs, bound, packed, S, sink, _Tables(base_tables, selected), fixed, bool(twin), *diff)
+    return _FieldFunction.apply(xyzs, dirs, bound, packed, S, sink, _Tables(base_tables, selected), fixed, bool(twin), rows_dev, *diff)

@@ -171,17 +171,18 @@ class NeRFNetwork(NeRFRenderer):
         else:
             self._select(message)
 
-    def forward(self, x, d, message, fixed=None, twin=False):
+    def forward(self, x, d, message, fixed=None, twin=False, rows_dev=None):
         """x: [N,3] in [-bound,bound], d: [N,3] unit, message: [message_dim] of 0./1. or None -> (sigma [N], color [N,3]).
         fixed: the fieldops.FixedPoints of exactly these points (fix_rays), or None.
-        twin: -> (sigma, color, sigma_clean, color_clean): the field without the message at the same points, from the same launch (needs a message)."""
+        twin: -> (sigma, color, sigma_clean, color_clean): the field without the message at the same points, from the same launch (needs a message).
+        rows_dev: a device count of the rows of x that hold points (a captured loop's padded buffers), or None: the backward pass stops there."""
         if twin and message is None:
             raise ValueError("forward(twin=True) needs a message: without one the field is the clean one")
         if self.device_select and message is not None and message.is_cuda:
             if self.grad_sink is None and torch.is_grad_enabled():
                 raise RuntimeError("device_select needs a grad_sink: which tables were selected is not known on the host")
             tables, S = self._select_on_device(message)
-            return fo.field_apply(x, d, self.bound, self._packed(), self.encoder.tables(), tables, S, self.grad_sink, fixed, twin)
+            return fo.field_apply(x, d, self.bound, self._packed(), self.encoder.tables(), tables, S, self.grad_sink, fixed, twin, rows_dev)
         selected, _, S = self._select(message)
         sink = self.grad_sink
         if sink is None and self.shared_gradient_step and len(selected) and torch.is_grad_enabled() and x.is_cuda and not _data_parallel():
@@ -190,7 +191,7 @@ class NeRFNetwork(NeRFRenderer):
                 self._shared_sink = fo.SharedGradient(x.device)
                 install_shared_gradient_hook(self._shared_sink)
             sink = self._shared_sink
-        return fo.field_apply(x, d, self.bound, self._packed(), self.encoder.tables(), selected, S, sink, fixed, twin)
+        return fo.field_apply(x, d, self.bound, self._packed(), self.encoder.tables(), selected, S, sink, fixed, twin, rows_dev)
 
     # ------------------------------------------------------------------ one set of points under K messages (inference)
 

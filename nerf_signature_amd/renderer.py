@@ -153,6 +153,7 @@ class NeRFRenderer(nn.Module):
         self._grid_epoch = 0      # bumped by everything that rewrites the occupancy grid (see grid_key)
         # the training march's host state (plain attributes: none of it belongs in a state_dict)
         self.point_capacity = None      # {ray count: sample rows} set by a captured loop: the no-host-sync march (capacity_for)
+        self.point_headroom = ()        # the ray counts among them whose rows were sized with headroom: their backward stops at the march's device count (rows_for)
         self._marched = {}              # _rays_key -> raymarching.MarchRecord of samples marched ahead of their render (march_ahead, fix_rays)
         self._premarched = None         # the MarchRecord of premarch(), for the next render only
         self._keep_rays, self._last_rays = False, None      # _render_staged_fused: leave the last march's ray table in _last_rays
@@ -318,6 +319,10 @@ class NeRFRenderer(nn.Module):
         """Sample rows a captured loop has reserved for renders of this many rays (`point_capacity`), or None."""
         return self.point_capacity.get(n_rays) if self.point_capacity else None
 
+    def rows_for(self, n_rays, counter):
+        """The march's device counter as the row count of the field backward, for renders whose reserved rows carry headroom (`point_headroom`); else None."""
+        return counter if self.point_capacity and n_rays in self.point_headroom else None
+
     def march_ahead(self, rays_o, rays_d, dt_gamma=0, max_steps=1024, perturb=False, capacity=None, noises=None):
         """March the training samples of these rays now, for a render issued later with the same (unmodified) ray tensors.
 
@@ -443,12 +448,15 @@ class NeRFRenderer(nn.Module):
                                    marched=None, limits=None, clean_twin=False):
         """All samples of all rays at once, then one differentiable composite (renderer_wtmk.py:280-321)."""
         if marched is not None:      # the samples were marched ahead of this step (march_ahead)
+            rows_dev = self.rows_for(o.shape[0], marched.counter) if marched.fixed is None else None
             return self._field_and_composite(marched.xyzs, marched.dirs, marched.deltas, marched.rays, message, nears, fars, finish, T_thresh, marched.fixed,
-                                             clean_twin)
+                                             clean_twin, rows_dev=rows_dev)
         counter = self.step_counter[self.local_step % 16]  # ring of the last 16 (points, rays) totals
         self.local_step += 1
         capacity = self.capacity_for(o.shape[0])
+        rows_dev = None
         if capacity is not None and force_all_rays:
+            rows_dev = self.rows_for(o.shape[0], counter)
             # no host round trip: buffers sized by a known bound on the padded point count (see march_rays_train_capacity); its scan kernel writes
             # both entries of `counter` itself (no zero-fill: one launch less in the captured step)
             xyzs, dirs, deltas, rays = raymarching.march_rays_train_capacity(o, d, self.bound, self.density_bitfield, self.cascade,
@@ -460,11 +468,13 @@ class NeRFRenderer(nn.Module):
                                                                    nears, fars, counter, self.mean_count, perturb, 128, force_all_rays,
                                                                    dt_gamma, max_steps)
         self._last_rays = rays if self._keep_rays else None      # (render's fused staging reads the per-ray counts)
-        return self._field_and_composite(xyzs, dirs, deltas, rays, message, nears, fars, finish, T_thresh, clean_twin=clean_twin)
+        return self._field_and_composite(xyzs, dirs, deltas, rays, message, nears, fars, finish, T_thresh, clean_twin=clean_twin, rows_dev=rows_dev)
 
-    def _field_and_composite(self, xyzs, dirs, deltas, rays, message, nears, fars, finish, T_thresh, fixed=None, clean_twin=False):
+    def _field_and_composite(self, xyzs, dirs, deltas, rays, message, nears, fars, finish, T_thresh, fixed=None, clean_twin=False, rows_dev=None):
         # fixed: rays declared constant (NeRFNetwork.fix_rays) -- base planes and scatter plan are kept beside the samples
         # clean_twin: a fourth result, the (weights_sum, depth, image) of the clean field at the same samples -- the same compositing launch once more, no gradient
+        # rows_dev: the march's device counter when the sample buffers carry headroom (rows_for): the field's backward pass stops at the rows that hold samples
+        rows = {} if rows_dev is None else {"rows_dev": rows_dev}
         if is_multi_message(message):
             # K messages: the field pass shares everything but the codebook level (forward_multi_chunks: base planes once, at most NSIG_MULTI_MAX_MESSAGES messages
             # per launch); slice k then goes through the compositing launch and render tail of the single render -- stacked (weights_sum [K,N], depth [K,N], image [K,N,3])
@@ -480,9 +490,9 @@ class NeRFRenderer(nn.Module):
         if clean_twin:
             if fixed is not None:
                 raise NotImplementedError("clean_twin for rays declared constant (fix_rays): their kept plane set is not read by the twin launch")
-            sigmas, rgbs, sigmas_clean, rgbs_clean = self(xyzs, dirs, message, twin=True)
+            sigmas, rgbs, sigmas_clean, rgbs_clean = self(xyzs, dirs, message, twin=True, **rows)
         else:
-            sigmas, rgbs = self(xyzs, dirs, message) if fixed is None else self(xyzs, dirs, message, fixed=fixed)
+            sigmas, rgbs = self(xyzs, dirs, message, **rows) if fixed is None else self(xyzs, dirs, message, fixed=fixed)
         sigmas = sigmas if self.density_scale == 1 else self.density_scale * sigmas
         composite = ((lambda s, c: _CompositeFinish.apply(s, c, deltas, rays, nears, fars, finish, T_thresh)) if finish is not None
                      else (lambda s, c: raymarching.composite_rays_train(s, c, deltas, rays, T_thresh)))

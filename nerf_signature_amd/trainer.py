@@ -924,6 +924,8 @@ class GraphedWatermarkLoop:
         cap_block = padded_point_count(int(n_block * (1.0 + self.headroom)))
         cap_content = padded_point_count(int(n_content * (1.0 + self.content_headroom)))
         model.point_capacity = {rays_block: cap_block, rays_content: cap_content}
+        # a render whose rows carry headroom hands its field backward the march's device count (no plan entries, no MLP tiles, no scatter for the zero-filled tail)
+        model.point_headroom = tuple(n for n, h in ((rays_block, self.headroom), (rays_content, self.content_headroom)) if h > 0)
         model.device_select = True
         self._set_inputs(message, None)
 
