@@ -3,6 +3,7 @@
 #include <algorithm>
 
 #include "distortion.h"
+#include "draws.h"
 
 using namespace nsig;
 
@@ -51,27 +52,20 @@ void launch_distort_adjoint(const float *gy, const float *img, const Distortion 
 
 // ---- the step's random draws, counter-based: everything is a function of (seed, *step, element) -- a replayed graph draws fresh values every step without a
 // host-side generator.  Brightness factor U[0.5, 1.5], blur sigma U[0.01, 0.5], scaling factor 0.75 + 0.5 u (the factor the host draws for the same key,
-// distortion.host_uniform; both are one rounding of the same sum), one angle per image, noise[i] ~ N(0, 0.1) (Box-Muller).
-__device__ inline uint64_t mix64(uint64_t z) {      // splitmix64's finaliser
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
-__device__ inline uint64_t draw_key(uint64_t seed, const uint32_t *__restrict__ step) { return mix64(seed ^ (0x9E3779B97F4A7C15ull * ((uint64_t)(step ? step[0] : 0u) + 1ull))); }
-__device__ inline float draw_unit(uint64_t key) { return (float)(mix64(key ^ 0xFFFFFFFFFFFFFFFFull) >> 40) * (1.0f / 16777216.0f); }      // [0, 1)
+// distortion.host_uniform; both are one rounding of the same sum), one angle per image, noise[i] ~ N(0, 0.1) (Box-Muller).  The hash is draws.h's 64-bit family
+// under the key of (seed, step); the words outside the noise's indexed sequence finalise the key XORed with a constant of this file's own.
+constexpr uint64_t kUnitXor = 0xFFFFFFFFFFFFFFFFull;          // the step's one uniform word: brightness, sigma, scaling factor
+constexpr uint64_t kRotationMul = 0xA0761D6478BD642Full;      // image i's angle: key ^ (kRotationMul (i + 1))
+constexpr uint64_t kSelectorXor = 0xC2B2AE3D27D4EB4Full;      // a mixed set's selector
+__device__ inline float draw_unit(uint64_t key) { return unit24((uint32_t)(mix64(key ^ kUnitXor) >> 40)); }
 // one angle in [-30, 30) degrees per image, stored as (cos, sin): param[2 i], param[2 i + 1]
 __device__ inline void draw_rotation(uint64_t key, uint32_t i, float *__restrict__ param) {
-    const float u = (float)(mix64(key ^ (0xA0761D6478BD642Full * ((uint64_t)i + 1ull))) >> 40) * (1.0f / 16777216.0f);
+    const float u = unit24((uint32_t)(mix64(key ^ (kRotationMul * ((uint64_t)i + 1ull))) >> 40));
     const float a = (60.0f * u - 30.0f) * 0.0174532925199432958f;
     param[2 * i] = cosf(a);
     param[2 * i + 1] = sinf(a);
 }
-__device__ inline float draw_noise(uint64_t key, uint32_t i) {
-    const uint64_t h = mix64(key + 0xD1B54A32D192ED03ull * ((uint64_t)i + 1ull));
-    const float u1 = ((float)(uint32_t)(h >> 40) + 1.0f) * (1.0f / 16777216.0f);                   // (0, 1]
-    const float u2 = (float)(uint32_t)((h >> 8) & 0xFFFFFFu) * (1.0f / 16777216.0f);              // [0, 1)
-    return 0.316227766016837933f * sqrtf(-2.0f * logf(u1)) * cosf(6.28318530717958648f * u2);      // sigma = sqrt(0.1)
-}
+__device__ inline float draw_noise(uint64_t key, uint32_t i) { return unit_normal(draw64(key, i), 0.316227766016837933f); }      // sigma = sqrt(0.1)
 // Where the draw of a set (mask bit k = kind k) goes.  A mixed set: the words of its block.  A single kind, the one-member set: its parameter is param_out itself,
 // there is no selector word (selector == nullptr) and no other kind's rotation pairs to keep at the identity (n_images = 0 unless rotation is the kind).
 struct DrawDst {
@@ -85,8 +79,8 @@ struct DrawDst {
 // only when noise is selected.  Every thread derives the selector itself (nothing is read back from the block); thread 0 stores it.
 __global__ void __launch_bounds__(256) k_distort_draw(uint32_t mask, uint64_t seed, const uint32_t *__restrict__ step, DrawDst dst) {
     const uint32_t i = blockIdx.x * 256 + threadIdx.x;
-    const uint64_t key = draw_key(seed, step);
-    uint32_t pick = (uint32_t)(((mix64(key ^ 0xC2B2AE3D27D4EB4Full) >> 40) * (uint64_t)__popc(mask)) >> 24), kind = 0;
+    const uint64_t key = stream_key(seed, step ? step[0] : 0u);
+    uint32_t pick = (uint32_t)(((mix64(key ^ kSelectorXor) >> 40) * (uint64_t)__popc(mask)) >> 24), kind = 0;
     for (uint32_t k = 0; k <= kDistScaling; ++k)
         if ((mask >> k) & 1u) {
             if (pick == 0) {

@@ -16,22 +16,13 @@
 //            count, the mean sample count of the window from the loop's ring) -> k_packbits_dev (threshold read from device memory).
 // Everything is a pure function of (grid, parameters, seed, refresh count): two runs leave the same bits (tests/test_gpu_stage1.py, test_gpu_grid.py).
 // Every entry point alone against tests/grid_refresh_ref.py, exactly: tests/test_gpu_grid.py (`test_rg_*`); that restatement and every refusal: tests/test_grid_refresh_cpu.py.
+#include "draws.h"
 #include "wave.h"
 
 namespace nsig {
 
-__device__ inline uint64_t rg_mix64(uint64_t z) {      // splitmix64's finaliser (as stage1.hip's mix64)
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
-
-// the key of one (refresh, cascade, purpose) stream of draws
-__device__ inline uint64_t rg_stream(uint64_t seed, int32_t iter, uint32_t cas, uint32_t purpose) {
-    return rg_mix64(seed ^ (0x9E3779B97F4A7C15ull * ((uint64_t)(uint32_t)iter * 64ull + (uint64_t)cas * 8ull + (uint64_t)purpose + 1ull)));
-}
-__device__ inline uint64_t rg_draw(uint64_t stream, uint64_t i) { return rg_mix64(stream + 0xD1B54A32D192ED03ull * (i + 1ull)); }
-__device__ inline float rg_u01(uint64_t bits) { return (float)(uint32_t)(bits >> 40) * (1.0f / 16777216.0f); }      // 24 bits, [0, 1): torch.rand's grid
+// the key of one (refresh, cascade, purpose) stream of draws (draws.h's 64-bit family); purpose 0: the uniform cells, 1: the occupied cells, 2: the jitter
+__device__ inline uint64_t refresh_key(uint64_t seed, int32_t iter, uint32_t cas, uint32_t purpose) { return stream_key(seed, (uint64_t)(uint32_t)iter * 64ull + cas * 8ull + purpose); }
 
 // ---- the inclusive prefix sum of the occupancy flags `grid[cas] > 0` (morton order), in three launches of this file's own (no library scan, no memset node: the
 // captured refresh holds nothing but kernel nodes): per-workgroup counts of 4096 cells -> exclusive scan of the counts by one workgroup (k_refresh_bins) -> the
@@ -83,13 +74,13 @@ __device__ inline uint32_t draw_cell_key(uint32_t i, uint32_t N, uint32_t H, con
     const uint32_t cells = H * H * H;
     uint32_t x, y, z;
     if (i < N) {
-        const uint64_t b = rg_draw(rg_stream(seed, iter, cas, 0u), i);
+        const uint64_t b = draw64(refresh_key(seed, iter, cas, 0u), i);
         x = (uint32_t)b & (H - 1u); y = (uint32_t)(b >> 20) & (H - 1u); z = (uint32_t)(b >> 40) & (H - 1u);
     } else {
         const uint32_t total = (uint32_t)occ_prefix[cells - 1u];
         uint32_t m = 0;
         if (total > 0) {
-            const uint64_t b = rg_draw(rg_stream(seed, iter, cas, 1u), i - N);
+            const uint64_t b = draw64(refresh_key(seed, iter, cas, 1u), i - N);
             const uint32_t t = (uint32_t)(((b >> 32) * (uint64_t)total) >> 32);      // uniform in [0, total)
             uint32_t lo = 0, hi = cells - 1u;                                        // first index with occ_prefix > t
             while (lo < hi) {
@@ -214,12 +205,12 @@ __global__ void __launch_bounds__(256) k_refresh_points(const int32_t *__restric
     if (i >= n) return;
     const uint32_t key = keys != nullptr ? (uint32_t)keys[i] : i, id = ids != nullptr ? (uint32_t)ids[i] : i;
     const uint32_t x = key % H, y = (key / H) % H, z = key / (H * H);
-    const uint64_t stream = rg_stream(seed, *iter_dev, cas, 2u);
+    const uint64_t stream = refresh_key(seed, *iter_dev, cas, 2u);
     const float scale = extent - half_cell, hm1 = (float)(H - 1u);
     const uint32_t c[3] = {x, y, z};
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
-        const float u = rg_u01(rg_draw(stream, 3ull * id + (uint64_t)a));
+        const float u = unit24((uint32_t)(draw64(stream, 3ull * id + (uint64_t)a) >> 40));      // [0, 1): torch.rand's grid
         const float centre = ((2.0f * (float)c[a]) / hm1 - 1.0f) * scale;
         xyz[3u * i + a] = centre + (u * 2.0f - 1.0f) * half_cell;
     }

@@ -3,10 +3,9 @@
 // ps_render_u8: one lane per pixel of [P, H, W]; S x S sub-samples per pixel, K primitives per sub-sample, both loops with trip counts every lane shares.  The
 // primitives, the light and the background travel in the launch's arguments: nothing is read from device memory but the poses, nothing is shared between lanes,
 // nothing is allocated and no device value is read on the host.
-// The ray is float32 -- ps_pixel_ray restates raymarch.hip's pixel_ray operation for operation, and tests/test_gpu_procedural.py holds the two to each other
-// through rg_get_rays -- and everything behind it is float64.  The library is built with -ffp-contract=off (build.py's BASE_FLAGS): every operation below is
-// rounded on its own, in the order written.
-#include "common.h"
+// The ray is float32 -- rays.h's pixel_ray, the one every ray generator calls; tests/test_gpu_procedural.py compares with rg_get_rays -- and everything behind
+// it is float64.  The library is built with -ffp-contract=off (build.py's BASE_FLAGS): every operation below is rounded on its own, in the order written.
+#include "rays.h"
 
 namespace nsig {
 
@@ -20,18 +19,6 @@ struct PsPrims {                                     // by value in the kernel's
 struct PsShade {
     float light[3], ambient, bg[3];
 };
-
-// raymarch.hip's pixel_ray, word for word in its arithmetic (the header's "ray generation"): same operations, same order, same flags.
-__device__ inline void ps_pixel_ray(const float *__restrict__ Pm, float fx, float fy, float cx, float cy, float i, float j, float *__restrict__ o, float *__restrict__ d) {
-    const float x = (i - cx) / fx, y = (j - cy) / fy, z = 1.0f;
-    const float nrm = sqrtf(x * x + y * y + z * z);
-    const float dx = x / nrm, dy = y / nrm, dz = z / nrm;
-#pragma unroll
-    for (int r = 0; r < 3; ++r) {
-        d[r] = dx * Pm[4 * r] + dy * Pm[4 * r + 1] + dz * Pm[4 * r + 2];
-        o[r] = Pm[4 * r + 3];
-    }
-}
 
 struct PsHit {
     double t;
@@ -98,7 +85,7 @@ __global__ void __launch_bounds__(kPsThreads) k_ps_render_u8(const float *__rest
         for (uint32_t a = 0; a < S; ++a) {
             const float u = (float)i + (float)(2u * a + 1u) / twoS, v = (float)j + (float)(2u * b + 1u) / twoS;      // exact for S in {1, 2, 4}
             float of[3], df[3];
-            ps_pixel_ray(Pm, fx, fy, cx, cy, u, v, of, df);
+            pixel_ray(Pm, fx, fy, cx, cy, u, v, of, df);
             const double o[3] = {(double)of[0], (double)of[1], (double)of[2]}, d[3] = {(double)df[0], (double)df[1], (double)df[2]};
             PsHit best;
             best.t = INFINITY;

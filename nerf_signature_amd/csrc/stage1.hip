@@ -9,6 +9,7 @@
 //   * clean_loss     the MSE of nerf/utils.py:503 and its gradient in one launch.
 //
 // The level scatter of the base-table gradients lives beside its siblings in hashgrid.hip (hg_levels_plan / hg_levels_scatter).
+#include "draws.h"
 #include "hashgrid.h"
 #include "mfma.h"
 #include "planes.h"
@@ -209,12 +210,6 @@ __global__ void __launch_bounds__(256) k_wgrad_reduce(const float *__restrict__ 
 // The same single workgroup keeps a captured loop's books (every pointer optional): the march's (points, rays) totals into row step % 16 of a ring
 // -- what NeRFRenderer.step_counter holds for update_extra_state's mean_count (renderer_wtmk.py:282-284,533-536) --, the loss into a ring
 // the host reads whenever it likes, and the step count itself, advanced here: nothing of a step's tail reads it, the next replay's head does.
-__device__ inline uint64_t mix64(uint64_t z) {      // splitmix64's finaliser
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
-
 __global__ void __launch_bounds__(1024) k_clean_loss(const float *__restrict__ image, const float *__restrict__ gt, uint32_t n, float grad_scale,
                                                      float *__restrict__ loss, float *__restrict__ g_image, uint32_t *__restrict__ step_dev,
                                                      const int32_t *__restrict__ march_counter, int32_t *__restrict__ count_ring,
@@ -225,9 +220,8 @@ __global__ void __launch_bounds__(1024) k_clean_loss(const float *__restrict__ i
     // (seed, step + 1, ray) -- a replayed graph draws fresh values without a host-side generator (torch.rand under capture costs two
     // fill launches per replay for its seed / offset tensors).  This step's march has long consumed its own values.
     if (noise_next != nullptr) {
-        const uint64_t key = mix64(seed ^ (0x9E3779B97F4A7C15ull * ((uint64_t)(step_dev != nullptr ? *step_dev : 0u) + 2ull)));
-        for (uint32_t i = threadIdx.x; i < n_noise; i += 1024u)
-            noise_next[i] = (float)(uint32_t)(mix64(key + 0xD1B54A32D192ED03ull * ((uint64_t)i + 1ull)) >> 40) * (1.0f / 16777216.0f);
+        const uint64_t key = stream_key(seed, (uint64_t)(step_dev != nullptr ? *step_dev : 0u) + 1ull);      // (widened first: the step after 2^32 - 1 is 2^32)
+        for (uint32_t i = threadIdx.x; i < n_noise; i += 1024u) noise_next[i] = unit24((uint32_t)(draw64(key, i) >> 40));
     }
     __syncthreads();      // (every thread has read the step count before thread 0 advances it)
     float s = 0.0f;

@@ -19,7 +19,7 @@
 // flag swaps logf / sqrtf / cosf or the division for native approximations.
 #include <math.h>
 
-#include "common.h"
+#include "draws.h"
 
 namespace nsig {
 
@@ -228,20 +228,6 @@ __global__ void __launch_bounds__(256) k_tm_select_pick(TmSelect *__restrict__ s
 
 // ----------------------------------------------------------------------------- apply
 
-// The unit normal of (seed, tensor i, element j): the distortion layer's counter hash (distortion.hip mix64 / draw_noise, without its 0.316 factor)
-__device__ inline uint64_t tm_mix64(uint64_t z) {      // splitmix64's finaliser
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
-__device__ inline uint64_t tm_noise_key(uint64_t seed, uint32_t i) { return tm_mix64(seed ^ (0x9E3779B97F4A7C15ull * ((uint64_t)i + 1ull))); }
-__device__ inline float tm_unit_normal(uint64_t key, uint32_t j) {
-    const uint64_t h = tm_mix64(key + 0xD1B54A32D192ED03ull * ((uint64_t)j + 1ull));
-    const float u1 = ((float)(uint32_t)(h >> 40) + 1.0f) * (1.0f / 16777216.0f);                   // (0, 1]
-    const float u2 = (float)(uint32_t)((h >> 8) & 0xFFFFFFu) * (1.0f / 16777216.0f);              // [0, 1)
-    return sqrtf(-2.0f * logf(u1)) * cosf(6.28318530717958648f * u2);
-}
-
 struct TmScalars {      // per tensor of the launch, read from the statistics by the kernel itself
     float s, lo, step;
     bool pass;          // quantise: a constant tensor passes through
@@ -250,7 +236,7 @@ struct TmScalars {      // per tensor of the launch, read from the statistics by
 template <uint32_t KIND>
 __device__ __forceinline__ float tm_value(float x, uint32_t j, uint32_t threshold, uint64_t key, const TmScalars &c, float L) {
     if (KIND == NSIG_TAMPER_PRUNE) return (__float_as_uint(x) & 0x7fffffffu) <= threshold ? 0.0f : x;
-    if (KIND == NSIG_TAMPER_NOISE) return x + c.s * tm_unit_normal(key, j);
+    if (KIND == NSIG_TAMPER_NOISE) return x + c.s * unit_normal(draw64(key, j));      // word j of the key of (seed, tensor): draws.h
     if (KIND == NSIG_TAMPER_QUANTIZE) {
         if (c.pass || !tm_finite(x)) return x;
         const float q = fminf(L, fmaxf(0.0f, rintf((x - c.lo) / c.step)));
@@ -267,7 +253,7 @@ __global__ void __launch_bounds__(kTmApplyThreads) k_tm_apply(TmList a, uint32_t
     const float *x = a.src[t];      // (not __restrict__: src may be dst)
     float *y = a.dst[t];
     const uint32_t threshold = KIND == NSIG_TAMPER_PRUNE ? *threshold_bits : 0u;
-    const uint64_t key = KIND == NSIG_TAMPER_NOISE ? tm_noise_key(seed, first + t) : 0ull;
+    const uint64_t key = KIND == NSIG_TAMPER_NOISE ? stream_key(seed, first + t) : 0ull;
     const float L = (float)((1u << bits) - 1u);
     TmScalars c{0.0f, 0.0f, 1.0f, false};
     if (KIND == NSIG_TAMPER_NOISE) c.s = (float)((double)strength * stats[(size_t)(first + t) * 4 + 3]);

@@ -1,32 +1,10 @@
-"""Host mirror of the error-map sampler (csrc/raymarch.hip k_sample_rays_weighted): the counter hash in integers, the race's keys in float64, the
+"""Host mirror of the error-map sampler (csrc/raygen.hip k_sample_rays_weighted): the counter hash in integers (tests/draw_ref.py), the race's keys in float64, the
 selection as a sort -- and the statistic both generators are judged by (tests/test_gpu_error_map.py, tests/test_error_map_cpu.py)."""
 import functools
 
 import numpy as np
 
-_M = np.uint64(0xFFFFFFFF)
-
-
-def mix32(v):
-    v = np.asarray(v, dtype=np.uint64) & _M
-    v ^= v >> np.uint64(16)
-    v = (v * np.uint64(0x85EBCA6B)) & _M
-    v ^= v >> np.uint64(13)
-    v = (v * np.uint64(0xC2B2AE35)) & _M
-    v ^= v >> np.uint64(16)
-    return v
-
-
-def draw_base(seed, step, stream):
-    """(seed, step) -> the step's word of sequence `stream` (0: uniform pixel indices, 1: keys, 2 / 3: the row / column offset inside a cell)."""
-    lo, hi = np.uint64(seed & 0xFFFFFFFF), np.uint64((seed >> 32) & 0xFFFFFFFF)
-    b = mix32((mix32(lo ^ ((np.uint64(step) * np.uint64(0x9E3779B9)) & _M)) + hi) & _M)
-    return b if stream == 0 else mix32((b + np.uint64(stream) * np.uint64(0x7F4A7C15)) & _M)
-
-
-def draw_word(base, index):
-    index = np.asarray(index, dtype=np.uint64)
-    return mix32(base ^ ((index * np.uint64(0x85EBCA6B) + np.uint64(0x6B43A9B5)) & _M))
+from draw_ref import draw_base, draw_word, mix32, unit24, unit24_open0      # noqa: F401 (random_bg_ref and the tests import the hashes from here)
 
 
 def pose_of(step, stride, offset, P):
@@ -35,7 +13,7 @@ def pose_of(step, stride, offset, P):
 
 def key_uniforms(cells, seed, step):
     """u in (0, 1] of every cell, float64 (exact: 24 bits)."""
-    return ((draw_word(draw_base(seed, step, 1), np.arange(cells)) >> np.uint64(8)) + np.uint64(1)).astype(np.float64) / float(1 << 24)
+    return unit24_open0(draw_word(draw_base(seed, step, 1), np.arange(cells)) >> np.uint64(8))
 
 
 def keys(weights, seed, step):
@@ -59,8 +37,8 @@ def pixels(cells_drawn, G, H, W, seed, step):
     """Pixel index of ray n (drawn cell n) in the kernel's own float32 arithmetic."""
     n = np.arange(len(cells_drawn))
     f32 = np.float32
-    u1 = (draw_word(draw_base(seed, step, 2), n) >> np.uint64(8)).astype(f32) * f32(1.0 / (1 << 24))
-    u2 = (draw_word(draw_base(seed, step, 3), n) >> np.uint64(8)).astype(f32) * f32(1.0 / (1 << 24))
+    u1 = unit24(draw_word(draw_base(seed, step, 2), n) >> np.uint64(8)).astype(f32)
+    u2 = unit24(draw_word(draw_base(seed, step, 3), n) >> np.uint64(8)).astype(f32)
     sx, sy = f32(H) / f32(G), f32(W) / f32(G)
     c = np.asarray(cells_drawn)
     row = np.minimum(H - 1, ((c // G).astype(f32) * sx + u1 * sx).astype(np.int64))

@@ -7,36 +7,25 @@ int64 total.  Two things are not: the probe points (float64 here from the same f
 here in numpy's order; the device sums in double in another fixed order, so its float32 may sit one ulp away)."""
 import numpy as np
 
+from draw_ref import draw64, mix64, stream_key, unit24      # noqa: F401 (the tests read mix64 from here)
+
 MASK32 = (1 << 32) - 1
 _U = np.uint64
 
 
-def mix64(v):
-    """splitmix64's finaliser on numpy uint64 (wrapping), the idiom of tamper_ref.mix64."""
-    v = np.asarray(v, dtype=np.uint64)
-    with np.errstate(over="ignore"):
-        v = (v ^ (v >> _U(30))) * _U(0xBF58476D1CE4E5B9)
-        v = (v ^ (v >> _U(27))) * _U(0x94D049BB133111EB)
-        return v ^ (v >> _U(31))
-
-
 def stream(seed, it, cas, purpose):
     """The key of one (refresh count, cascade, purpose) stream: purpose 0 the uniform cells, 1 the occupied cells, 2 the jitter.  `it` is read as uint32."""
-    k = ((int(it) & MASK32) * 64 + int(cas) * 8 + int(purpose) + 1) & ((1 << 64) - 1)
-    with np.errstate(over="ignore"):
-        return mix64(_U(int(seed) & ((1 << 64) - 1)) ^ (_U(0x9E3779B97F4A7C15) * _U(k)))
+    return stream_key(seed, (int(it) & MASK32) * 64 + int(cas) * 8 + int(purpose))
 
 
 def draw(key, i):
     """64 bits of draw i (array of indices) of the stream `key`."""
-    i = np.asarray(i, dtype=np.uint64)
-    with np.errstate(over="ignore"):
-        return mix64(key + _U(0xD1B54A32D192ED03) * (i + _U(1)))
+    return draw64(key, np.asarray(i, dtype=np.uint64))
 
 
 def u01(bits):
     """The top 24 bits as a fraction: [0, 1) on the 2^-24 grid, exact in float32 and float64."""
-    return (np.asarray(bits, dtype=np.uint64) >> _U(40)).astype(np.float64) / 16777216.0
+    return unit24(np.asarray(bits, dtype=np.uint64) >> _U(40))
 
 
 def _spread3(v):

@@ -1,9 +1,9 @@
 """tests/orbit_ref.py -- TEST INFRASTRUCTURE, NOT PRODUCT CODE.
 
-Float64 mirror of the orbit sampler's draw and pose (csrc/raymarch.hip: draw_base / draw_word / orbit_pose, rg_sample_rays_orbit), and the bound the GPU
+Float64 mirror of the orbit sampler's draw and pose (csrc/draws.h: draw_base / draw_word; csrc/raygen.hip: orbit_pose, rg_sample_rays_orbit), and the bound the GPU
 test holds `pose_out` to.  numpy only; imports nothing of the product.
 
-The draw.  The counter hash of section 16: base = mix32(mix32(seed_lo ^ (k * 0x9e3779b9)) + seed_hi), a sequence s > 0 re-keys it as mix32(base + s * 0x7f4a7c15),
+The draw (tests/draw_ref.py states it in integers).  The counter hash of section 16: base = mix32(mix32(seed_lo ^ (k * 0x9e3779b9)) + seed_hi), a sequence s > 0 re-keys it as mix32(base + s * 0x7f4a7c15),
 word i of a sequence is mix32(base ^ (i * 0x85ebca6b + 0x6b43a9b5)) -- all modulo 2^32.  The orbit pose of camera k = step * stride + offset takes words 0 and 1
 of sequence 5 (0: uniform pixel indices, 1..3: the weighted sampler, 4: the RGBA backgrounds), each on torch.rand's grid: (word >> 8) * 2^-24.
 
@@ -23,34 +23,16 @@ import math
 
 import numpy as np
 
+from draw_ref import draw_base, draw_word, mix32, unit24      # noqa: F401 (the tests import the hashes from here)
+
 M32 = 0xFFFFFFFF
 ORBIT_SEQUENCE = 5
 TRIG_ULP = 1.0          # documented maximum ulp error of HIP's sinf / cosf (see above)
 
 
-def mix32(v):
-    v &= M32
-    v ^= v >> 16
-    v = (v * 0x85EBCA6B) & M32
-    v ^= v >> 13
-    v = (v * 0xC2B2AE35) & M32
-    v ^= v >> 16
-    return v
-
-
-def draw_base(seed, step, sequence):
-    seed_lo, seed_hi = seed & M32, (seed >> 32) & M32
-    b = mix32((mix32(seed_lo ^ ((step * 0x9E3779B9) & M32)) + seed_hi) & M32)
-    return b if sequence == 0 else mix32((b + sequence * 0x7F4A7C15) & M32)
-
-
-def draw_word(base, index):
-    return mix32(base ^ ((index * 0x85EBCA6B + 0x6B43A9B5) & M32))
-
-
 def uniform24(word):
     """torch.rand's grid: 24 bits * 2^-24, exact in fp32."""
-    return (word >> 8) * 2.0 ** -24
+    return unit24(word >> 8)
 
 
 def camera_index(step, stride, offset):

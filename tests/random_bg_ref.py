@@ -1,5 +1,5 @@
-"""Host mirror of the stage-1 RGBA step's background draw and blend (csrc/raymarch.hip blend_random_background): the counter hash in integers -- sequence 4
-of the hash the samplers draw from (tests/error_map_ref.py) -- and the blend gt = rgb * a + bg * (1 - a) in float32 with every operation rounded on its own
+"""Host mirror of the stage-1 RGBA step's background draw and blend (csrc/raygen.hip blend_random_background): the counter hash in integers -- sequence 4
+of the hash the samplers draw from (tests/draw_ref.py, through tests/error_map_ref.py) -- and the blend gt = rgb * a + bg * (1 - a) in float32 with every operation rounded on its own
 (tests/test_rgba_cpu.py, tests/test_gpu_rgba.py)."""
 import numpy as np
 

@@ -10,6 +10,8 @@ from fractions import Fraction
 
 import numpy as np
 
+from draw_ref import draw64, mix64, stream_key, unit24, unit24_open0      # noqa: F401 (mix64: importable from here as before)
+
 MASK64 = (1 << 64) - 1
 KINDS = {"prune": 0, "noise": 1, "quantize": 2, "half": 3}
 
@@ -17,24 +19,10 @@ Z_ERR_MEASURED = 1.0941252956975234e-06      # tools/tamper_bench.py --z-error, 
 EPS_Z = 4 * Z_ERR_MEASURED
 
 
-def mix64(v):
-    """splitmix64's finaliser on numpy uint64 (wrapping)."""
-    v = np.asarray(v, dtype=np.uint64)
-    with np.errstate(over="ignore"):
-        v = (v ^ (v >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
-        v = (v ^ (v >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
-        return v ^ (v >> np.uint64(31))
-
-
 def noise_uniforms(seed, i, n, first=0):
     """(u1 in (0, 1], u2 in [0, 1)) of elements first .. first + n - 1 of tensor i, as float64 (exact: multiples of 2^-24)."""
-    with np.errstate(over="ignore"):
-        key = mix64(np.uint64(seed & MASK64) ^ (np.uint64(0x9E3779B97F4A7C15) * np.uint64(i + 1)))
-        j = np.arange(first, first + n, dtype=np.uint64)
-        h = mix64(key + np.uint64(0xD1B54A32D192ED03) * (j + np.uint64(1)))
-    u1 = ((h >> np.uint64(40)).astype(np.float64) + 1.0) / 16777216.0
-    u2 = ((h >> np.uint64(8)) & np.uint64(0xFFFFFF)).astype(np.float64) / 16777216.0
-    return u1, u2
+    h = draw64(stream_key(seed, i), np.arange(first, first + n, dtype=np.uint64))
+    return unit24_open0(h >> np.uint64(40)), unit24((h >> np.uint64(8)) & np.uint64(0xFFFFFF))
 
 
 def unit_normal(seed, i, n, first=0):
