@@ -567,6 +567,27 @@ int rm_finish_bwd(const float *grad_image, const float *grad_depth, const float 
                   uint32_t bg_stride, uint32_t N, float *grad_weights_sum, float *grad_depth_in, nsig_stream_t stream);
 
 /*
+ * The render tail that writes STORE BYTES: a compositor's outputs -> pixels of the uint8 [P, H, W, C] image store the device samplers draw from (rg_sample_rays_u8;
+ * nerf_signature_amd/distill.py renders a teacher model's views into such a store).  image [N, 3]: the premultiplied sum of w_i c_i (a render against background 0);
+ * weights_sum [N]; out: uint8 [N, channels] at ANY byte address (a view of a store whose H W C is odd starts anywhere).  One launch, nothing allocated, nothing read
+ * back; one lane per ray, nothing shared: the bytes are a single-valued function of the arguments and tests/distill_ref.py restates them from this text.
+ *
+ * Arithmetic.  Every operation is fp32 and rounded on its own (the library is built with -ffp-contract=off: no FMA across the operations written here), division is
+ * IEEE, rint rounds half to even; max and min are fmaxf / fminf; clamp(x) = min(max(x, 0), 1).  Not-a-number inputs still finish and write only their own pixels, but
+ * their bytes are not specified.
+ *   all C:   a = min(max(weights_sum, 0), 1)
+ *   C = 4:   rgb_c = (a > 0) ? image_c / a : 0     (STRAIGHT alpha, as the Blender PNGs store it and as the reference's RGBA blend rgb a + bg (1 - a) reads the store)
+ *            bytes 0 .. 2 = rint(255 clamp(rgb_c)), byte 3 = rint(255 a); bg_* is ignored
+ *   C = 3:   m_c = (1 - a) bg_c;  s_c = image_c + m_c;  bytes = rint(255 clamp(s_c))     (two roundings: the product, then the sum)
+ * Refused (return 1, nsig_last_error): "rm_finish_u8: channels=%u is not 3 or 4" (checked first, at any N); with N > 0 a NULL image, weights_sum or out:
+ * "rm_finish_u8: null pointer".  N = 0 with 3 or 4 channels launches nothing and returns 0.
+ *
+ * The launch is bound by memory: 16 B read and 3 or 4 B written per ray; a store of 100 x 800 x 800 views is 64 M rays, 1.02 GB read and 0.19 / 0.26 GB written, about
+ * 1.3 GB in all (arithmetic, not a measurement).
+ */
+int rm_finish_u8(const float *image, const float *weights_sum, uint32_t N, uint32_t channels, float bg_r, float bg_g, float bg_b, uint8_t *out, nsig_stream_t stream);
+
+/*
  * Opening launch of a captured training step (the loop body of utils_wtmk_disen.py:1164-1181 replayed as a hipGraph): zero-fills
  * G [n_floats] (optimizer.zero_grad for the shared codebook gradient) and copies `width` floats of slot (*counter % slots) of a
  * ring in PINNED host memory (ring_dev = its device-side address, [slots][width]: this step's message and the next one's, :1165) into msg [width], then

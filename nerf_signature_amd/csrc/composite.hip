@@ -43,6 +43,74 @@ __global__ void __launch_bounds__(256) k_finish_bwd(const float *__restrict__ g_
     if (g_depth_in) g_depth_in[i] = (g_depth && depth[i] - nears[i] >= 0.0f) ? g_depth[i] / (fars[i] - nears[i]) : 0.0f;
 }
 
+// ----------------------------------------------------------------------------- the render tail as store bytes (rm_finish_u8; include/nerfsig.h pins the arithmetic)
+
+__device__ __forceinline__ float unit_clamp(float x) { return fminf(fmaxf(x, 0.0f), 1.0f); }
+__device__ __forceinline__ uint32_t unit_code(float x) { return (uint32_t)rintf(255.0f * unit_clamp(x)); }
+
+struct Bg3 {
+    float c[3];
+};
+
+// The pixel of ray i as a little-endian word: byte k in bits 8k .. 8k+7.  C = 4: straight (r, g, b) and alpha; C = 3: (r, g, b) over bg, the top byte 0.
+template <int C> __device__ __forceinline__ uint32_t finish_code(const float *__restrict__ image, const float *__restrict__ ws, size_t i, const Bg3 &bg) {
+    const float a = unit_clamp(ws[i]);
+    uint32_t word = 0;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const float v = image[i * 3 + c];
+        float x;
+        if (C == 4) {
+            x = a > 0.0f ? v / a : 0.0f;
+        } else {
+            const float behind = (1.0f - a) * bg.c[c];
+            x = v + behind;
+        }
+        word |= unit_code(x) << (8 * c);
+    }
+    if (C == 4) word |= unit_code(a) << 24;      // (a is in [0, 1] already: rint(255 a))
+    return word;
+}
+
+// One lane per ray, one 4-byte store per ray (byte stores when `out` is not 4-byte aligned: a uniform branch).
+__global__ void __launch_bounds__(256) k_finish_u8_rgba(const float *__restrict__ image, const float *__restrict__ ws, uint32_t N, uint8_t *__restrict__ out,
+                                                        uint32_t aligned) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= N) return;
+    const uint32_t word = finish_code<4>(image, ws, i, Bg3{});
+    if (aligned) {
+        reinterpret_cast<uint32_t *>(out)[i] = word;
+    } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) out[i * 4 + k] = (uint8_t)(word >> (8 * k));
+    }
+}
+
+// Three bytes per ray.  A lane that owned one ray would issue a 2-byte and a 1-byte store, and a store costs its issue slot whatever its width (the row loads of
+// DESIGN.md section 22 taught that for 4- / 2- / 1-byte words: the count binds, not the bytes) -- so a lane owns FOUR consecutive rays, 12 bytes = three aligned
+// 4-byte stores, a quarter of the lanes and 3 stores per 4 rays instead of 8.  The rays before the first 4-byte boundary of `out` (head = address mod 4 of them:
+// ray r starts at byte 3 r) and the (N - head) mod 4 rays behind the last whole group go to one lane each, behind the groups, with byte stores.
+__global__ void __launch_bounds__(256) k_finish_u8_rgb(const float *__restrict__ image, const float *__restrict__ ws, uint32_t N, Bg3 bg, uint8_t *__restrict__ out,
+                                                       uint32_t head, uint32_t groups) {
+    const uint32_t t = blockIdx.x * 256 + threadIdx.x;      // (groups + leftovers <= N: no wrap)
+    if (t < groups) {
+        const size_t r = (size_t)head + 4 * (size_t)t;
+        const uint32_t w0 = finish_code<3>(image, ws, r, bg), w1 = finish_code<3>(image, ws, r + 1, bg);
+        const uint32_t w2 = finish_code<3>(image, ws, r + 2, bg), w3 = finish_code<3>(image, ws, r + 3, bg);
+        uint32_t *o = reinterpret_cast<uint32_t *>(out + 3 * r);
+        o[0] = w0 | (w1 << 24);
+        o[1] = (w1 >> 8) | (w2 << 16);
+        o[2] = (w2 >> 16) | (w3 << 8);
+        return;
+    }
+    const uint32_t k = t - groups;
+    const size_t r = k < head ? (size_t)k : (size_t)head + 4 * (size_t)groups + (k - head);
+    if (r >= N) return;
+    const uint32_t word = finish_code<3>(image, ws, r, bg);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) out[3 * r + c] = (uint8_t)(word >> (8 * c));
+}
+
 // ----------------------------------------------------------------------------- compositing (training)
 //
 // One wave per ray.  The reference walks a ray's samples serially (raymarching.cu:540-567); here the 64 lanes take 64
@@ -338,6 +406,23 @@ NSIG_EXPORT int rm_finish_fwd(const float *image, const float *depth, const floa
     NSIG_REQUIRE(bg_stride == 0 || bg_stride == 3, "rm_finish_fwd: bg_stride is 0 (one colour) or 3 (per ray)");
     k_finish_fwd<<<ceil_div(N, 256u), 256, 0, as_stream(stream)>>>(image, depth, weights_sum, nears, fars, bg, bg_stride, N, image_out, depth_out);
     return check_launch("rm_finish_fwd");
+}
+
+NSIG_EXPORT int rm_finish_u8(const float *image, const float *weights_sum, uint32_t N, uint32_t channels, float bg_r, float bg_g, float bg_b, uint8_t *out,
+                             nsig_stream_t stream) {
+    NSIG_REQUIRE(channels == 3 || channels == 4, "rm_finish_u8: channels=%u is not 3 or 4", channels);
+    if (N == 0) return NSIG_OK;
+    NSIG_REQUIRE(image && weights_sum && out, "rm_finish_u8: null pointer");
+    const uint32_t phase = (uint32_t)(reinterpret_cast<uintptr_t>(out) & 3u);
+    if (channels == 4) {
+        k_finish_u8_rgba<<<(uint32_t)(((uint64_t)N + 255u) / 256u), 256, 0, as_stream(stream)>>>(image, weights_sum, N, out, phase == 0u ? 1u : 0u);
+    } else {
+        const uint32_t head = phase < N ? phase : N;
+        const uint32_t groups = (N - head) / 4u;
+        const uint32_t lanes = groups + (N - 4u * groups);      // one per group, one per ray outside the groups (at most 6)
+        k_finish_u8_rgb<<<(uint32_t)(((uint64_t)lanes + 255u) / 256u), 256, 0, as_stream(stream)>>>(image, weights_sum, N, Bg3{{bg_r, bg_g, bg_b}}, out, head, groups);
+    }
+    return check_launch("rm_finish_u8");
 }
 
 NSIG_EXPORT int rm_finish_bwd(const float *grad_image, const float *grad_depth, const float *depth, const float *nears, const float *fars,

@@ -437,6 +437,36 @@ def _constant_image_psnr(truth):
     return float(-10.0 * torch.log10(((truth - mean) ** 2).mean()))
 
 
+def train_clean_field(scene, bound=1.0, steps=1024, n_rays=4096, lr=README["lr"], ema_decay=0.95, seed=0, render_kwargs=None, lap=None):
+    """The stage-1 recipe, once, for sign_scene and distill.distill: torch.manual_seed(seed), a fresh stage1.CleanNeRFNetwork of `bound`, mark_untrained_grid over the
+    scene's cameras, Adam with betas (0.9, 0.99), stage1.GraphedCleanLoop over scene.sampler(n_rays, seed) with the grid refreshed on the device every 16 steps, the
+    learning rate decayed over `steps` and the moving average of the weights on; `steps` steps with an overflow poll every 256.  lap: called as lap("capture") after
+    the first step (set-up, sizing march and capture) and lap("train") after the last -- the caller's stopwatch, which synchronises.
+    -> (model, loop, record): the loop is left OPEN (the caller evaluates or checkpoints under loop.ema_weights() and closes it); record: steps, samples_per_ray (the
+    march's mean over the last 16 steps), overflowed."""
+    from . import stage1
+    dev = scene.poses.device
+    kw = dict(dt_gamma=0.0, max_steps=1024) if render_kwargs is None else dict(render_kwargs)
+    lap = (lambda name: None) if lap is None else lap
+    torch.manual_seed(seed)
+    clean = stage1.CleanNeRFNetwork(bound=bound, cuda_ray=True, density_scale=1, min_near=0.2, density_thresh=10, bg_radius=-1).to(dev).train()
+    clean.mark_untrained_grid(scene.poses, scene.intrinsics)
+    optimizer = torch.optim.Adam(clean.get_params(lr), betas=(0.9, 0.99), eps=1e-15)
+    loop = stage1.GraphedCleanLoop(clean, optimizer, kw, n_rays=n_rays, sampler=scene.sampler(n_rays, seed=seed), update_extra_interval=16, lr_lambda=lr_lambda(steps),
+                                   headroom=1.0, seed=seed, device_refresh=True, ema_decay=ema_decay)
+    loop.step()
+    lap("capture")
+    overflow = False
+    for k in range(1, steps):
+        loop.step()
+        if k % 256 == 255:
+            overflow = overflow or loop.overflowed()
+    overflow = overflow or loop.overflowed()
+    lap("train")
+    samples_per_ray = float(loop.count_ring[:min(16, steps), 0].float().mean()) / n_rays
+    return clean, loop, {"steps": steps, "samples_per_ray": samples_per_ray, "overflowed": bool(overflow)}
+
+
 def sign_scene(scene, message, bound=1.0, stage1_steps=1024, stage2_steps=README["iters"], ema_decay=0.95, seed=0, workdir=None, held_out=None, rows=16, cols=16,
                key_view=0, n_rays=4096, lr=README["lr"], n_messages=50):
     """From a dataset.Scene to a released, signed, verified model -- both stages in one run:
@@ -467,22 +497,8 @@ def sign_scene(scene, message, bound=1.0, stage1_steps=1024, stage2_steps=README
         phases[name], t0 = now - t0, now
 
     # ---- stage 1
-    torch.manual_seed(seed)
-    clean = stage1.CleanNeRFNetwork(bound=bound, cuda_ray=True, density_scale=1, min_near=0.2, density_thresh=10, bg_radius=-1).to(dev).train()
-    clean.mark_untrained_grid(scene.poses, scene.intrinsics)
-    optimizer = torch.optim.Adam(clean.get_params(lr), betas=(0.9, 0.99), eps=1e-15)
-    loop = stage1.GraphedCleanLoop(clean, optimizer, kw, n_rays=n_rays, sampler=scene.sampler(n_rays, seed=seed), update_extra_interval=16, lr_lambda=lr_lambda(stage1_steps),
-                                   headroom=1.0, seed=seed, device_refresh=True, ema_decay=ema_decay)
-    loop.step()
-    lap("stage1_capture_s")
-    overflow1 = False
-    for k in range(1, stage1_steps):
-        loop.step()
-        if k % 256 == 255:
-            overflow1 = overflow1 or loop.overflowed()
-    overflow1 = overflow1 or loop.overflowed()
-    lap("stage1_train_s")
-    samples_per_ray = float(loop.count_ring[:min(16, stage1_steps), 0].float().mean()) / n_rays
+    clean, loop, rec1 = train_clean_field(scene, bound, stage1_steps, n_rays, lr, ema_decay, seed, kw, lap=lambda name: lap(f"stage1_{name}_s"))
+    overflow1, samples_per_ray = rec1["overflowed"], rec1["samples_per_ray"]
     views = scene if held_out is None else held_out
     n_views = min(2, views.poses.shape[0]) if held_out is None else views.poses.shape[0]
     with tempfile.TemporaryDirectory() as tmp, loop.ema_weights():
@@ -525,6 +541,42 @@ def sign_scene(scene, message, bound=1.0, stage1_steps=1024, stage2_steps=README
               "train_views": int(scene.poses.shape[0]), "blocks": [rows, cols]}
     return {"released": released, "key": key, "stage": stage, "record": record,
             "clean": {"model": clean, "ema": ema, "missing": missing, "unexpected": unexpected}}
+
+
+def distillation_survival(stage_or_signed, message, views=(12, 50), steps=(1024,), H=None, W=None, channels=4, seed=0):
+    """Does the signature survive distillation?  The pirate never touches the released weights: they render pictures from the released model and train a field of their
+    own on them (distill.distill).  stage_or_signed: a stage (watermark_stage's / scene_stage's dict) or sign_scene's result.  The stage's model is released under
+    `message` (a copy), the key is stage_key's, and release.verify of the released FIELD is the yardstick.  Then, per (views, steps) cell: `views` orbit cameras
+    (distill.orbit_cameras at the mean distance of the stage's own cameras, seed `seed`; the key pose is not among them) of H x W pixels (default: the stage's; another
+    size scales the intrinsics) -> distill -> release.verify(distill.student_render(student), key).
+    -> {"field": the verdict on the released field, "cells": [one dict per cell: "views", "steps", "matches", "bit_accuracy", "p_value", "psnr_db" and "ssim" (the
+        student against the teacher's renders of two held-out cameras), "ms_per_step", "constant_psnr_db", "overflowed", "store_bytes"]}.
+    What survives is REPORTED here and asserted nowhere, as in mesh_survival."""
+    from . import distill as dst, release as rel
+    stage = stage_or_signed["stage"] if "stage" in stage_or_signed else stage_or_signed
+    model, dev, kw = stage["model"], stage["device"], stage["render_kwargs"]
+    message = torch.as_tensor(message).detach().float().reshape(-1)
+    released = rel.release(model, message.to(dev), copy=True)
+    key = stage_key(stage, message)
+    out = {"field": rel.verify(released, key), "cells": []}
+    H0, W0 = stage["H"], stage["W"]
+    H, W = (H0 if H is None else int(H)), (W0 if W is None else int(W))
+    fx, fy, cx, cy = stage["intr"]
+    intr = (fx * W / W0, fy * H / H0, cx * W / W0, cy * H / H0)
+    if stage.get("poses") is not None:
+        radius = float(stage["poses"][:, :3, 3].double().norm(dim=-1).mean())
+    else:
+        radius = float(stage["radius"])
+    for n_views in views:
+        for n_steps in steps:
+            got = dst.distill(released, dst.orbit_cameras(n_views, radius, seed), intr, H, W, steps=int(n_steps), channels=channels, bound=model.bound,
+                              n_rays=stage["n_rays"], seed=seed, render_kwargs=kw)
+            v, r = rel.verify(dst.student_render(got["student"], kw), key), got["record"]
+            out["cells"].append({"views": int(n_views), "steps": int(n_steps), "matches": v["matches"], "bit_accuracy": v["bit_accuracy"], "p_value": v["p_value"],
+                                 "psnr_db": r["psnr_db"], "ssim": r["ssim"], "ms_per_step": r["ms_per_step"], "constant_psnr_db": r["constant_psnr_db"],
+                                 "overflowed": r["overflowed"], "store_bytes": r["store_bytes"]})
+            del got
+    return out
 
 
 LAST_STAGE = None      # (tools/converge.py's two-rank run compares the ranks' final models)

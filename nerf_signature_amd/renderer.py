@@ -389,8 +389,9 @@ class NeRFRenderer(nn.Module):
         self._premarched = raymarching.MarchRecord(o, d, xyzs, dirs, deltas, rays, nears, fars).made_for(rays_o, rays_d, float(dt_gamma), int(max_steps), self.grid_key())
 
     def run_cuda(self, rays_o, rays_d, message, dt_gamma=0, bg_color=None, perturb=False, force_all_rays=False, max_steps=1024,
-                 T_thresh=1e-4, clean_twin=False, **kwargs):
-        """clean_twin (training path, with a message): results["clean_image"] is the image of the SAME samples through the field without the message -- the clean
+                 T_thresh=1e-4, clean_twin=False, return_weights_sum=False, **kwargs):
+        """return_weights_sum: results["weights_sum"] [N] in eval() mode too (the training path always carries it): what a caller that writes the render's own
+        alpha needs (distill.teacher_dataset).  clean_twin (training path, with a message): results["clean_image"] is the image of the SAME samples through the field without the message -- the clean
         field comes out of the watermarked render's own MLP launch (field_fwd_twin) and goes through the same compositing forward and render tail, with the same
         deltas, rays and background; no gradient flows through it.  Bit for bit the "image" of this call with message=None."""
         if clean_twin and not self.training:
@@ -439,8 +440,9 @@ class NeRFRenderer(nn.Module):
             weights_sum, depth, image = self._march_and_composite_eval(o, d, message, nears, fars, dt_gamma, perturb, max_steps, T_thresh)
         image, depth = self._finish(prefix, image, depth, weights_sum, bg_color, nears, fars)
         results = {"depth": depth, "image": image}
-        if self.training:
+        if self.training or return_weights_sum:
             results["weights_sum"] = weights_sum
+        if self.training:
             results.update(clean or {})
         return results
 
@@ -767,13 +769,16 @@ class NeRFRenderer(nn.Module):
         B, N = rays_o.shape[:2]
         device = rays_o.device
         if (staged and self.cuda_ray and self.training and not torch.is_grad_enabled() and rays_o.is_cuda and N > max_ray_batch
-                and kwargs.get("force_all_rays", False) and not kwargs.get("perturb", False) and self.point_capacity is None
+                and kwargs.get("force_all_rays", False) and not kwargs.get("perturb", False) and self.point_capacity is None and not kwargs.get("return_weights_sum")
                 and os.environ.get("NERFSIG_STAGED_FUSED", "1") != "0"):
             return self._render_staged_fused(rays_o, rays_d, message, max_ray_batch, **kwargs)
         if staged:
             lead = (message.shape[0],) if is_multi_message(message) else ()
             depth = torch.empty(lead + (B, N), device=device)
             image = torch.empty(lead + (B, N, 3), device=device)
+            alpha = torch.empty(B, N, device=device) if kwargs.get("return_weights_sum") else None      # (asked for: the staged result carries it too)
+            if alpha is not None and lead:
+                raise NotImplementedError("return_weights_sum on a staged render under K messages")
             for b in range(B):
                 head = 0
                 while head < N:
@@ -781,8 +786,10 @@ class NeRFRenderer(nn.Module):
                     results_ = _run(rays_o[b:b + 1, head:tail], rays_d[b:b + 1, head:tail], message, **kwargs)
                     depth[..., b:b + 1, head:tail] = results_["depth"]
                     image[..., b:b + 1, head:tail, :] = results_["image"]
+                    if alpha is not None:
+                        alpha[b, head:tail] = results_["weights_sum"].reshape(-1)
                     head += max_ray_batch
-            results = {"depth": depth, "image": image}
+            results = {"depth": depth, "image": image, **({} if alpha is None else {"weights_sum": alpha})}
         else:
             if getattr(self, "auto_fix_rays", False):
                 self._maybe_fix_rays(rays_o, rays_d, **kwargs)
